@@ -14,11 +14,17 @@ timed region is exactly K transitions with all inputs resident in HBM.
 One rank per GPU (torchrun); chains are independent (no data-path collective); the post-burn-in samples of all ranks
 are gathered once to rank 0 over RCCL after the timed region.
 
-After the headline region a one-GPU run (N = 1) also measures, untimed-setup style, the single-GPU figures of the other
-BASELINE configs -- config 1 (SEIR-4, N = 161, b = 80, one chain, 200 + 200 NUTS steps, next to the C-port CPU leg),
-config 3's per-GPU share (8 chains, N = 1024), one dataset of config 4's alpha sweep (8 chains, N = 161, b = 80) and
-config 5 (N = 8192 x 4: one pooled build with per-class device times, and the streaming kernel on 4.4 GB of operator
-blocks) -- plus the hyper-parameter fit's ms per Adam step -- and reports them as FLAT scalars inside `roofline`
+A plain run does only that: set-up, burn-in and warm-up, the K timed transitions, the gather and the result line (`roofline`,
+`cpu_baseline` and `hmc_L32` are null).  `--dump-outputs DIR` also writes what the timed path delivered for its last
+transition -- every chain's sample and rank 0's sampler diagnostics -- as DIR/<name>.npy (float64); the inputs are fixed by
+the arguments, so two builds can be compared array for array.
+
+`--full` adds, after the headline region, everything else the line used to carry: the in-sampler kernel durations and the
+roofline of the streaming kernel, fixed-L HMC, the CPU baseline legs and, on a one-GPU run (N = 1), untimed-setup style, the
+single-GPU figures of the other BASELINE configs -- config 1 (SEIR-4, N = 161, b = 80, one chain, 200 + 200 NUTS steps,
+next to the C-port CPU leg), config 3's per-GPU share (8 chains, N = 1024), one dataset of config 4's alpha sweep (8 chains,
+N = 161, b = 80) and config 5 (N = 8192 x 4: one pooled build with per-class device times, and the streaming kernel on
+4.4 GB of operator blocks) -- plus the hyper-parameter fit's ms per Adam step, reported as FLAT scalars inside `roofline`
 (`cfg1_*`, `mc8_*`, `cfg4_*`, `n8192_*`, `f1_*`).
 """
 import argparse
@@ -53,8 +59,13 @@ def parse():
                          "step size has flattened by then (1.3e-3 after 40 steps, 2.1e-3 after 100, 2.5e-3 after 200, 2.8e-3 after 400 on this "
                          "workload), i.e. the timed transitions are those of an adapted sampler (DESIGN.md section 5)")
     ap.add_argument("--band", type=int, default=-1, help="bandsize (-1 = dense)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra-configs", action="store_true", help="skip the config 1 / 3 / 4 / 5 legs of a one-GPU run")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline region also measure the kernel durations / roofline, fixed-L HMC, the CPU baseline and the "
+                         "config 1 / 3 / 4 / 5 legs (off: the line carries the headline figures only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the timed path's outputs of its last step to DIR/<name>.npy (float64, at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline legs")
+    ap.add_argument("--no-extra-configs", action="store_true", help="with --full: skip the config 1 / 3 / 4 / 5 legs of a one-GPU run")
     ap.add_argument("--cpu-steps", type=int, default=2, help="oracle NUTS transitions for the CPU baseline's numpy leg")
     ap.add_argument("--seed", type=int, default=20250103)
     ap.add_argument("--replicate-chains", action="store_true",
@@ -62,7 +73,7 @@ def parse():
                          "chains).  The default gives every chain of the job its own Philox stream -- independent chains, as "
                          "BASELINE config 3 asks -- so the max-over-ranks time includes the NUTS tree-size spread between chains")
     ap.add_argument("--cpu-threads", type=str, default="1,8,16,32,64,all", help="thread counts of the CPU baseline legs")
-    ap.add_argument("--profile-slots", type=int, default=512, help="leapfrog slots of the in-sampler kernel-duration leg")
+    ap.add_argument("--profile-slots", type=int, default=512, help="leapfrog slots of the in-sampler kernel-duration leg (--full)")
     ap.add_argument("--config", choices=["headline", "alpha-sweep"], default="headline",
                     help="headline: BASELINE configs[1] / configs[2] (see --chains-per-gpu).  alpha-sweep: BASELINE configs[3] -- the ten alpha-sweep "
                          "datasets x 8 chains = 80 (dataset, chain) units dealt to the GPUs by whole datasets (magi_v2_amd/sweep.py), total work fixed: "
@@ -129,6 +140,30 @@ def cpu_gradient_rates(pb, mats, band, drift, P, state, threads, max_seconds, le
     return pr, torch_cpu.time_gradients(pr, Xc, spc, tpc, threads, min_evals=200, max_seconds=max_seconds)
 
 
+DUMP_BUDGET_BYTES = 60 << 20        # --dump-outputs: below 64 MB in all, .npy headers included
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as <out_dir>/<name>.npy in float64.  Should they exceed the budget together, each is cut to its
+    share by one fixed (seeded) sample of its flattened elements, in order -- the same elements in every run of the same arguments."""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    for name, v in arrays.items():
+        if total > DUMP_BUDGET_BYTES:
+            keep = max(1, v.size * DUMP_BUDGET_BYTES // total)
+            if keep < v.size:
+                v = v.reshape(-1)[np.sort(np.random.default_rng(0).choice(v.size, keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+
+
+def last_sample_arrays(samples, N, D, P):
+    """The last transition of every chain in a gathered sample block [chains, results, N*D + D + P] (X, then sigma_sqs and theta
+    before their softplus), as the caller of the sampler receives them."""
+    last = samples[:, -1]
+    return {"X": last[:, :N * D].reshape(-1, N, D), "sig_pre": last[:, N * D:N * D + D], "th_pre": last[:, N * D + D:N * D + D + P]}
+
+
 def alpha_sweep_bench(a, rank, world, dev_index, red_dev):
     """BASELINE configs[3]: 10 datasets (alpha = 0.05 / 0.15, seeds 0-4; tests/golden/seir_alpha_sweep.npz holds the vignette thinning of the
     reference's data/*.csv) x 8 chains, N = 161, b = 80, reference defaults (stale cache as the reference).  Whole datasets are dealt to the
@@ -178,6 +213,8 @@ def alpha_sweep_bench(a, rank, world, dev_index, red_dev):
         return
     units = len(datasets) * cpd
     P = 3
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, last_sample_arrays(allsamp, (allsamp.shape[2] - 4 - P) // 4, 4, P))
     th = np.log1p(np.exp(allsamp[:, a.warmup:, -P:]))                        # [units, steps, P]
     per_ds = th.reshape(len(datasets), cpd * a.steps, P).mean(axis=1)
     out = {
@@ -199,7 +236,7 @@ def alpha_sweep_bench(a, rank, world, dev_index, red_dev):
         "theta_mean_per_dataset": [[round(float(x), 4) for x in row] for row in per_ds],
         "theta_last_per_unit": [[round(float(x), 10) for x in th[u, -1]] for u in range(units)],
         "roofline": None, "cpu_baseline": None,
-        "note": "secondary configuration of bench.py (the driver's N = 1 line is --config headline, which carries roofline and cpu_baseline; "
+        "note": "secondary configuration of bench.py (the driver's N = 1 line is --config headline, which carries roofline and cpu_baseline with --full; "
                 "its cfg4_* scalars time one dataset of this sweep on one GPU)",
     }
     print(json.dumps(out))
@@ -244,7 +281,7 @@ def main():
     pb = setup_problem(host, I, X_obs, P)
     eng = MagiEngine(dev_index)
     t0 = time.perf_counter()
-    want_host = (rank == 0 and world == 1 and not a.no_cpu_baseline)
+    want_host = (rank == 0 and world == 1 and a.full and not a.no_cpu_baseline)         # (host copies of the matrices: the CPU baseline's)
     mats = eng.build_matrices(I, pb["hp"]["phi1s"], pb["hp"]["phi2s"], 2.01, bandsize=band, want_host=want_host)
     build_ms = (time.perf_counter() - t0) * 1e3
     eng.set_problem(pb["mu"], pb["N_ds"], pb["idx"], pb["y"], pb["beta"], pb["LB"], "seir4")
@@ -311,7 +348,77 @@ def main():
     value = n_chains * a.steps / elapsed
     diag = eng.sampler_diag()
     post = diag.tree_depth[:, a.burnin + a.warmup:a.burnin + a.warmup + a.steps]
-    lf_rank0 = float(lf)
+    lf_per_sample = lf_total / (n_chains * a.steps)
+    if a.dump_outputs:
+        t_last = a.burnin + a.warmup + a.steps - 1        # the last timed transition on the diagnostics' time axis (burn-in included)
+        outs = last_sample_arrays(allsamp, N, D, P)
+        outs.update({"rank0_" + k: getattr(diag, k)[:, t_last] for k in
+                     ("target_log_prob", "step_size", "log_accept_ratio", "leapfrogs_taken", "tree_depth", "is_accepted")})
+        dump_outputs(a.dump_outputs, outs)
+
+    roofline = cpu = hmc = extra_note = None
+    if a.full:
+        roofline, cpu, hmc, extra_note = full_legs(a, eng, host, MagiEngine, pb, mats, rep, chain_ids, dev_index, world, elapsed,
+                                                   slots_issued, lf_total, lf_per_sample)
+    eng.close()
+
+    out = {
+        "metric": "HMC samples/sec (whole node) on SEIR, N grid pts x D comps",
+        "value": round(value, 4), "unit": "samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(elapsed / a.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
+        "config": {"workload": f"SEIR N={N} x 4 components, {'dense' if band is None else 'band ' + str(band)}, "
+                               f"NUTS(max depth 10)+dual averaging+log annealing, {cpg} chain(s)/GPU",
+                   "baseline_config": ("BASELINE configs[1] (SEIR N=1024 x 4, 1 chain, 1 GPU)" if cpg == 1 and world == 1 else
+                                       f"weak scaling of BASELINE configs[1]: one chain per GPU x {world} GPUs" if cpg == 1 else
+                                       f"BASELINE configs[2] ({cpg * world} independent chains, {cpg} per GPU x {world} GPUs)"),
+                   "grid": N, "components": D, "thetas": P, "chains_total": n_chains, "bandsize": band,
+                   "burnin_untimed": a.burnin,
+                   "burnin_note": "untimed transitions that adapt the step size before the timed region (the reference burns in 1000): DESIGN.md section 5",
+                   "parallelism": f"chains x{world}",
+                   "stale_cache": 0, "stale_cache_note": "the reference's annealed kernel reuses the previous step's cached target (computed at the "
+                                   "previous temperature); on this synthetic grid that offset rejects every proposal, so the bench recomputes at "
+                                   "the current temperature -- same arithmetic per leapfrog (DESIGN.md 4.2)",
+                   "chain_streams": "DIAGNOSTIC: every rank replicates rank 0's chain ids" if a.replicate_chains else
+                                    "independent: Philox stream = global chain id (rank * chains_per_gpu + local index)"},
+        "roofline": roofline, "cpu_baseline": cpu,
+        "leapfrogs_per_s": round(lf_total / elapsed, 1),
+        "leapfrogs_per_s_per_gpu": round(lf_total / elapsed / world, 1),
+        "per_rank_ms": [round(x[0], 2) for x in per_rank], "per_rank_leapfrogs": [int(x[1]) for x in per_rank],
+        "rank_balance": round(float(np.mean([x[0] for x in per_rank]) / max(x[0] for x in per_rank)), 4),
+        "rank_balance_note": "mean / max of the ranks' own times for their K NUTS transitions: chains build trees of different sizes (different leapfrog counts per "
+                             "rank above), the job ends with the slowest chain, and there is no communication inside the timed region -- this ratio, not the "
+                             "interconnect, is what an N-GPU efficiency below 1 consists of (fixed-L HMC, hmc_L32, has no such spread)",
+        "us_per_leapfrog_slot": round(elapsed / (lf_total / n_chains) * 1e6, 2),
+        "us_per_slot_issued": round(elapsed / max(slots_issued, 1) * 1e6, 3), "slots_issued_rank0": int(slots_issued),
+        "slot_overhead_rank0": round(slots_issued / max(float(diag.leapfrogs_taken[:, a.burnin + a.warmup:a.burnin + a.warmup + a.steps].sum(axis=1).max()), 1.0), 4),
+        "slot_note": "us_per_leapfrog_slot = elapsed / (leapfrogs per chain, mean); us_per_slot_issued = elapsed / kernel pairs [stream, point] "
+                     "actually issued on rank 0 (device counter); slot_overhead = slots issued / leapfrogs of the busiest chain (skip / set-up slots)",
+        "mean_tree_depth": round(float(post.mean()), 2), "device_ms": round(dev_ms, 2), "build_ms": round(build_ms, 1),
+        "leapfrogs_per_sample": round(lf_per_sample, 1),
+        "gather_ms": round(gather_ms, 3), "hmc_L32": hmc,
+        "theta_mean": [round(float(x), 4) for x in np.log1p(np.exp(th_all)).reshape(-1, P).mean(axis=0)],
+    }
+    if n_chains <= 64:       # what the final gather delivered: global unit ids in order, and each chain's last theta (distinct chains differ)
+        out["gathered_unit_ids"] = [int(g_) for g_ in gids]
+        out["theta_last_per_chain"] = [[round(float(x), 10) for x in np.log1p(np.exp(th_all[c, -1]))] for c in range(n_chains)]
+    if extra_note:
+        out["extra_configs"] = extra_note
+    if cpu:
+        out["speedup_vs_cpu_port"] = round(value / cpu["value"], 1)          # against the BEST thread count of the C + OpenMP leg
+    print(json.dumps(out))
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_legs(a, eng, host, MagiEngine, pb, mats, rep, chain_ids, dev_index, world, elapsed, slots_issued, lf_total, lf_per_sample):
+    """--full: what the line carries beyond the headline figures, measured after the headline region on rank 0's engine -- the
+    in-sampler kernel durations, fixed-L HMC, the roofline of the streaming kernel, the CPU baseline and (one-GPU run) the other
+    BASELINE configs.  Returns (roofline, cpu_baseline, hmc_L32, extra_configs note)."""
+    N, D, P = a.grid, 4, 3
+    cpg = a.chains_per_gpu
+    band = None if a.band < 0 else a.band
+    n_chains = cpg * world
     state = eng.sampler_state()          # before the profiling / timing launches clobber it
 
     # ---- in-sampler kernel durations (HIP events attached to every launch of the streaming kernel and of k_point: the kernels'
@@ -411,7 +518,6 @@ def main():
             cpu_model = next(l.split(":", 1)[1].strip() for l in fh if l.startswith("model name"))
     except (OSError, StopIteration):
         cpu_model = "unknown"
-    lf_per_sample = lf_total / (n_chains * a.steps)
     if world == 1 and not a.no_cpu_baseline:
         from oracle import magi_oracle as orc
         import threadpoolctl
@@ -455,55 +561,7 @@ def main():
     extra_note = None
     if world == 1 and not a.no_extra_configs and N == 1024 and cpg == 1 and band is None:
         extra_note = extra_configs(a, eng, host, MagiEngine, pb, roofline, threads, dev_index)
-    eng.close()
-
-    out = {
-        "metric": "HMC samples/sec (whole node) on SEIR, N grid pts x D comps",
-        "value": round(value, 4), "unit": "samples/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(elapsed / a.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f64", "data": "synthetic",
-        "config": {"workload": f"SEIR N={N} x 4 components, {'dense' if band is None else 'band ' + str(band)}, "
-                               f"NUTS(max depth 10)+dual averaging+log annealing, {cpg} chain(s)/GPU",
-                   "baseline_config": ("BASELINE configs[1] (SEIR N=1024 x 4, 1 chain, 1 GPU)" if cpg == 1 and world == 1 else
-                                       f"weak scaling of BASELINE configs[1]: one chain per GPU x {world} GPUs" if cpg == 1 else
-                                       f"BASELINE configs[2] ({cpg * world} independent chains, {cpg} per GPU x {world} GPUs)"),
-                   "grid": N, "components": D, "thetas": P, "chains_total": n_chains, "bandsize": band,
-                   "burnin_untimed": a.burnin,
-                   "burnin_note": "untimed transitions that adapt the step size before the timed region (the reference burns in 1000): DESIGN.md section 5",
-                   "parallelism": f"chains x{world}",
-                   "stale_cache": 0, "stale_cache_note": "the reference's annealed kernel reuses the previous step's cached target (computed at the "
-                                   "previous temperature); on this synthetic grid that offset rejects every proposal, so the bench recomputes at "
-                                   "the current temperature -- same arithmetic per leapfrog (DESIGN.md 4.2)",
-                   "chain_streams": "DIAGNOSTIC: every rank replicates rank 0's chain ids" if a.replicate_chains else
-                                    "independent: Philox stream = global chain id (rank * chains_per_gpu + local index)"},
-        "roofline": roofline, "cpu_baseline": cpu,
-        "leapfrogs_per_s": round(lf_total / elapsed, 1),
-        "leapfrogs_per_s_per_gpu": round(lf_total / elapsed / world, 1),
-        "per_rank_ms": [round(x[0], 2) for x in per_rank], "per_rank_leapfrogs": [int(x[1]) for x in per_rank],
-        "rank_balance": round(float(np.mean([x[0] for x in per_rank]) / max(x[0] for x in per_rank)), 4),
-        "rank_balance_note": "mean / max of the ranks' own times for their K NUTS transitions: chains build trees of different sizes (different leapfrog counts per "
-                             "rank above), the job ends with the slowest chain, and there is no communication inside the timed region -- this ratio, not the "
-                             "interconnect, is what an N-GPU efficiency below 1 consists of (fixed-L HMC, hmc_L32, has no such spread)",
-        "us_per_leapfrog_slot": round(elapsed / (lf_total / n_chains) * 1e6, 2),
-        "us_per_slot_issued": round(elapsed / max(slots_issued, 1) * 1e6, 3), "slots_issued_rank0": int(slots_issued),
-        "slot_overhead_rank0": round(slots_issued / max(float(diag.leapfrogs_taken[:, a.burnin + a.warmup:a.burnin + a.warmup + a.steps].sum(axis=1).max()), 1.0), 4),
-        "slot_note": "us_per_leapfrog_slot = elapsed / (leapfrogs per chain, mean); us_per_slot_issued = elapsed / kernel pairs [stream, point] "
-                     "actually issued on rank 0 (device counter); slot_overhead = slots issued / leapfrogs of the busiest chain (skip / set-up slots)",
-        "mean_tree_depth": round(float(post.mean()), 2), "device_ms": round(dev_ms, 2), "build_ms": round(build_ms, 1),
-        "leapfrogs_per_sample": round(lf_per_sample, 1),
-        "gather_ms": round(gather_ms, 3), "hmc_L32": hmc,
-        "theta_mean": [round(float(x), 4) for x in np.log1p(np.exp(th_all)).reshape(-1, P).mean(axis=0)],
-    }
-    if n_chains <= 64:       # what the final gather delivered: global unit ids in order, and each chain's last theta (distinct chains differ)
-        out["gathered_unit_ids"] = [int(g_) for g_ in gids]
-        out["theta_last_per_chain"] = [[round(float(x), 10) for x in np.log1p(np.exp(th_all[c, -1]))] for c in range(n_chains)]
-    if extra_note:
-        out["extra_configs"] = extra_note
-    if cpu:
-        out["speedup_vs_cpu_port"] = round(value / cpu["value"], 1)          # against the BEST thread count of the C + OpenMP leg
-    print(json.dumps(out))
-    if world > 1:
-        dist.destroy_process_group()
+    return roofline, cpu, hmc, extra_note
 
 
 def extra_configs(a, eng, host, MagiEngine, pb2, roofline, threads, dev_index):

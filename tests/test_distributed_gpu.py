@@ -8,6 +8,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -27,7 +28,7 @@ def test_bench_two_ranks_on_one_gpu_gathers_four_distinct_chains_in_global_order
     env = dict(os.environ, MAGI_BENCH_REHEARSE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--chains-per-gpu", "2", "--steps", "3",
-           "--warmup", "1", "--burnin", "5", "--no-cpu-baseline", "--no-extra-configs", "--profile-slots", "64"]
+           "--warmup", "1", "--burnin", "5", "--full", "--no-cpu-baseline", "--no-extra-configs", "--profile-slots", "64"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -41,10 +42,10 @@ def test_bench_two_ranks_on_one_gpu_gathers_four_distinct_chains_in_global_order
 
 
 def test_bench_line_carries_every_contract_field_on_one_gpu():
-    """`python bench.py` (short run: 3 timed transitions, no CPU legs, no extra configs) prints ONE JSON line with the driver's contract
+    """`python bench.py --full` (short run: 3 timed transitions, no CPU legs, no extra configs) prints ONE JSON line with the driver's contract
     fields, BASELINE.json's metric and the roofline object; `frac` is the live in-sampler figure (HIP events on every launch)."""
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--burnin", "6", "--no-cpu-baseline", "--no-extra-configs",
-           "--profile-slots", "64"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--burnin", "6", "--full", "--no-cpu-baseline",
+           "--no-extra-configs", "--profile-slots", "64"]
     r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -67,6 +68,30 @@ def test_bench_line_carries_every_contract_field_on_one_gpu():
     if rf["traffic"] is not None:          # committed PMC passes: the byte model the fraction rests on is what the counters saw
         assert abs(rf["traffic"] - rf["bytes_per_launch"]) < 0.05 * rf["bytes_per_launch"]
     assert abs(out["value"] - out["config"]["chains_total"] * out["steps"] / (out["ms_per_step"] * 1e-3 * out["steps"])) < 1e-2 * out["value"]
+
+
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain `python bench.py` carries the headline fields only (no roofline, CPU or HMC legs), and `--dump-outputs DIR` writes the last
+    timed transition as the caller receives it: every chain's sample, whose theta is the line's `theta_last_per_chain`, and rank 0's diagnostics."""
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--burnin", "6",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup"):
+        assert k in out, k
+    assert out["steps"] == 3 and out["warmup"] == 1 and out["unit"] == "samples/s" and out["dtype"] == "f64"
+    assert out["roofline"] is None and out["cpu_baseline"] is None and out["hmc_L32"] is None and "extra_configs" not in out
+    assert abs(out["value"] - out["config"]["chains_total"] / (out["ms_per_step"] * 1e-3)) < 1e-2 * out["value"]
+    got = {f[:-4]: np.load(tmp_path / f) for f in os.listdir(tmp_path)}
+    assert set(got) == {"X", "sig_pre", "th_pre", "rank0_target_log_prob", "rank0_step_size", "rank0_log_accept_ratio",
+                        "rank0_leapfrogs_taken", "rank0_tree_depth", "rank0_is_accepted"}
+    assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in got.values())
+    assert got["X"].shape == (1, out["config"]["grid"], 4) and got["sig_pre"].shape == (1, 4) and got["th_pre"].shape == (1, 3)
+    assert np.allclose(np.log1p(np.exp(got["th_pre"])), out["theta_last_per_chain"], rtol=0, atol=1e-9)
+    assert got["rank0_leapfrogs_taken"].shape == (1,) and got["rank0_leapfrogs_taken"][0] >= 1 and got["rank0_step_size"][0] > 0
 
 
 def _run_bench(extra, nproc):
