@@ -269,15 +269,26 @@ int magi_gradient_bytes(magi_handle* h, int n_chains, double* phase_bytes);
  * "k_stream<1>", "k_stream<2>" (VALU), "k_stream_sep<CW=8|16>" (matrix cores, separable drift), "k_stream_mc". */
 int magi_stream_kernel_name(magi_handle* h, int n_chains, char* buf, int cap);
 
-/* Tuning / test switches of a handle (csrc/magi_internal.h: MagiOptions).  The environment variables MAGI_STREAM_FAMILY,
- * MAGI_FAMILY_CHAINS, MAGI_SEP_PAIR_MIN, MAGI_FUSED_PARITY, MAGI_GEMM_REMAP_MIN, MAGI_POTRF_PANELS, MAGI_NO_GRAPH, MAGI_FIT_HOST_LOOP,
- * MAGI_FIT_PER_COMPONENT, MAGI_BUILD_PROFILE, MAGI_BUILD_SERIAL are read ONCE, by magi_create; afterwards only this call
- * changes an option (no getenv on a compute path).  Names: "stream_family" (0 auto, 1 mc, 2 valu; takes effect at the next
- * magi_sampler_init / log-posterior call), "family_chains" (> 0: "auto" chooses the kernel family as if the batch had this many chains -- a
- * sharded job passes its largest per-GPU share on every rank, so that a chain's samples do not depend on how many chains share its GPU),
- * "sep_pair_min" (next packing), "fused_parity", "gemm_remap_min", "potrf_panels", "potrf_lookahead_min",
- * "no_graph", "fit_host_loop", "fit_per_component", "build_profile", "build_serial", and the test hook
- * "slot_budget_graphs" (cap on the graph launches of one magi_sampler_run; 0 = the computed bound; no environment variable). */
+/* Tuning / test switches of a handle (csrc/magi_internal.h: MagiOptions; one table in csrc/capi.hip).  The environment variables
+ * are read ONCE, by magi_create; afterwards only this call changes an option (no getenv on a compute path).  A variable outside an
+ * option's range keeps the default, as this call rejects such a value (MAGI_E_BADARG).  A flag is on for a non-zero value; its
+ * variable turns it on by being present, whatever its value.  Options, with their variables:
+ *   "stream_family"       MAGI_STREAM_FAMILY        0 auto, 1 mc, 2 valu (variable: "mc" / "valu"); takes effect at the next
+ *                                                   magi_sampler_init / log-posterior call
+ *   "family_chains"       MAGI_FAMILY_CHAINS        0..4096; > 0: "auto" chooses the kernel family as if the batch had this many
+ *                                                   chains -- a sharded job passes its largest per-GPU share on every rank, so that a
+ *                                                   chain's samples do not depend on how many chains share its GPU
+ *   "sep_pair_min"        MAGI_SEP_PAIR_MIN         clamped to 0..2^30; read at the next packing
+ *   "fused_parity"        MAGI_FUSED_PARITY         1: magi_logpost_grad_fused evaluates as an odd leapfrog slot
+ *   "gemm_remap_min"      MAGI_GEMM_REMAP_MIN       clamped to 0..2^30
+ *   "potrf_panels"        MAGI_POTRF_PANELS         1..16
+ *   "potrf_lookahead_min" MAGI_POTRF_LOOKAHEAD_MIN  >= 0
+ *   "no_graph"            MAGI_NO_GRAPH             flag
+ *   "fit_host_loop"       MAGI_FIT_HOST_LOOP        flag
+ *   "fit_per_component"   MAGI_FIT_PER_COMPONENT    flag
+ *   "build_profile"       MAGI_BUILD_PROFILE        flag
+ *   "build_serial"        MAGI_BUILD_SERIAL         flag
+ *   "slot_budget_graphs"  (none: a test hook)       cap on the graph launches of one magi_sampler_run; 0 = the computed bound */
 int magi_set_option(magi_handle* h, const char* name, int64_t value);
 
 /* Diagnostics: per-class device time of the last magi_build_matrices run with option "build_profile" set

@@ -3,6 +3,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 #include "magi_internal.h"
 
@@ -107,23 +108,49 @@ int build_graph(magi_handle* h) {
     return MAGI_OK;
 }
 
+// doubles of tpart for n chains: the larger of the two streaming paths' layouts
+size_t tpart_elems(const magi_handle* h, int n) {
+    return std::max(magi_sep_tpart_elems(h->pb, n), (size_t)n * 4 * h->pb.D * h->pb.nb * h->pb.Np);
+}
+
+// The options of a handle (MagiOptions), one row each: the name magi_set_option takes, the environment variable magi_create reads
+// (none for the test hook slot_budget_graphs: it must not be reachable from a job's environment), the rule of a value, the member.
+//   RANGE   a number in [lo, hi]: magi_set_option rejects any other value, a variable outside it keeps the default
+//   CLAMP   a number, clamped to [lo, hi]
+//   ONE     on when the value is 1;  FLAG  on when it is non-zero (a variable: when it is present, whatever its value)
+//   FAMILY  as RANGE; the variable: "mc" -> 1, "valu" -> 2, anything else 0
+enum OptRule { RANGE, CLAMP, ONE, FLAG, FAMILY };
+struct OptRow { const char *name, *env; OptRule rule; int64_t lo, hi; void (*store)(MagiOptions&, int64_t); };
+template <auto M> void store(MagiOptions& o, int64_t v) { o.*M = (std::remove_reference_t<decltype(o.*M)>)v; }
+const OptRow kOptions[] = {
+    {"stream_family",       "MAGI_STREAM_FAMILY",       FAMILY, 0, 2,         store<&MagiOptions::stream_family>},
+    {"family_chains",       "MAGI_FAMILY_CHAINS",       RANGE,  0, 4096,      store<&MagiOptions::family_chains>},
+    {"sep_pair_min",        "MAGI_SEP_PAIR_MIN",        CLAMP,  0, 1 << 30,   store<&MagiOptions::sep_pair_min>},
+    {"fused_parity",        "MAGI_FUSED_PARITY",        ONE,    0, 1,         store<&MagiOptions::fused_parity>},
+    {"gemm_remap_min",      "MAGI_GEMM_REMAP_MIN",      CLAMP,  0, 1 << 30,   store<&MagiOptions::gemm_remap_min>},
+    {"potrf_panels",        "MAGI_POTRF_PANELS",        RANGE,  1, 16,        store<&MagiOptions::potrf_panels>},
+    {"potrf_lookahead_min", "MAGI_POTRF_LOOKAHEAD_MIN", RANGE,  0, INT64_MAX, store<&MagiOptions::potrf_lookahead_min>},
+    {"no_graph",            "MAGI_NO_GRAPH",            FLAG,   0, 1,         store<&MagiOptions::no_graph>},
+    {"fit_host_loop",       "MAGI_FIT_HOST_LOOP",       FLAG,   0, 1,         store<&MagiOptions::fit_host_loop>},
+    {"fit_per_component",   "MAGI_FIT_PER_COMPONENT",   FLAG,   0, 1,         store<&MagiOptions::fit_per_component>},
+    {"build_profile",       "MAGI_BUILD_PROFILE",       FLAG,   0, 1,         store<&MagiOptions::build_profile>},
+    {"build_serial",        "MAGI_BUILD_SERIAL",        FLAG,   0, 1,         store<&MagiOptions::build_serial>},
+    {"slot_budget_graphs",  nullptr,                    CLAMP,  0, INT64_MAX, store<&MagiOptions::slot_budget_graphs>},
+};
+
+// false (the option unchanged) for a RANGE / FAMILY value out of bounds
+bool set_option(MagiOptions& o, const OptRow& r, int64_t v) {
+    if ((r.rule == RANGE || r.rule == FAMILY) && (v < r.lo || v > r.hi)) return false;
+    r.store(o, r.rule == CLAMP ? std::clamp(v, r.lo, r.hi) : r.rule == ONE ? v == 1 : r.rule == FLAG ? v != 0 : v);
+    return true;
+}
+
 }  // namespace
 
 void magi_options_from_env(MagiOptions& o) {
-    auto num = [](const char* name, long long dflt) { const char* e = getenv(name); return e ? atoll(e) : dflt; };
-    if (const char* e = getenv("MAGI_STREAM_FAMILY")) o.stream_family = std::string(e) == "mc" ? 1 : std::string(e) == "valu" ? 2 : 0;
-    o.sep_pair_min = (int)num("MAGI_SEP_PAIR_MIN", o.sep_pair_min);
-    o.fused_parity = num("MAGI_FUSED_PARITY", 0) == 1;
-    o.gemm_remap_min = (int)num("MAGI_GEMM_REMAP_MIN", o.gemm_remap_min);
-    o.family_chains = (int)num("MAGI_FAMILY_CHAINS", o.family_chains);
-    o.potrf_panels = (int)num("MAGI_POTRF_PANELS", o.potrf_panels);
-    o.potrf_lookahead_min = (int)num("MAGI_POTRF_LOOKAHEAD_MIN", o.potrf_lookahead_min);
-    o.no_graph = getenv("MAGI_NO_GRAPH") != nullptr;
-    o.fit_host_loop = getenv("MAGI_FIT_HOST_LOOP") != nullptr;
-    o.fit_per_component = getenv("MAGI_FIT_PER_COMPONENT") != nullptr;
-    o.build_profile = getenv("MAGI_BUILD_PROFILE") != nullptr;
-    o.build_serial = getenv("MAGI_BUILD_SERIAL") != nullptr;
-    // (slot_budget_graphs has no variable: a test hook must not be reachable from a job's environment)
+    for (const OptRow& r : kOptions)
+        if (const char* e = r.env ? getenv(r.env) : nullptr)
+            (void)set_option(o, r, r.rule == FLAG ? 1 : r.rule == FAMILY ? (!strcmp(e, "mc") ? 1 : !strcmp(e, "valu") ? 2 : 0) : atoll(e));
 }
 
 double* magi_workspace(magi_handle* h, int k, size_t n) {
@@ -157,14 +184,13 @@ int magi_ensure_chains(magi_handle* h, int n) {
         h->ch.n_wg = magi_leap_wgs(h->pb);
         MAGI_HIP_CHECK(h, hipMalloc(&h->ch.part, sizeof(double) * PART_K * h->ch.n_wg * n));
         MAGI_HIP_CHECK(h, hipMemset(h->ch.part, 0, sizeof(double) * PART_K * h->ch.n_wg * n));
-        const bool sep = magi_drift_separable(h->pb.drift);
-        const size_t tpn = std::max(sep ? magi_sep_tpart_elems(h->pb, n) : (size_t)0, (size_t)n * 4 * h->pb.D * h->pb.nb * h->pb.Np);      // (either layout)
+        const size_t tpn = tpart_elems(h, n);
         MAGI_HIP_CHECK(h, hipMalloc(&h->ch.tpart, sizeof(double) * tpn));
         MAGI_HIP_CHECK(h, hipMemset(h->ch.tpart, 0, sizeof(double) * tpn));     // slots outside the block band stay zero
         const size_t opn = (size_t)2 * ((n + 15) / 16) * h->pb.D * h->pb.Np * 16;
         MAGI_HIP_CHECK(h, hipMalloc(&h->ch.xop, sizeof(double) * opn));
         MAGI_HIP_CHECK(h, hipMemset(h->ch.xop, 0, sizeof(double) * opn));
-        h->vop_elems = sep ? magi_sep_vop_elems(h->pb, n) : 16;
+        h->vop_elems = magi_drift_separable(h->pb.drift) ? magi_sep_vop_elems(h->pb, n) : 16;
         MAGI_HIP_CHECK(h, hipMalloc(&h->ch.vop, sizeof(double) * h->vop_elems));
         MAGI_HIP_CHECK(h, hipMemset(h->ch.vop, 0, sizeof(double) * h->vop_elems));
         MAGI_HIP_CHECK(h, hipMalloc(&h->ch.gctl, sizeof(GlobalCtl)));
@@ -173,21 +199,18 @@ int magi_ensure_chains(magi_handle* h, int n) {
         MAGI_HIP_CHECK(h, hipMalloc(&h->d_fin, sizeof(double) * 8 * n));
         h->cap_chains = n;
     }
-    const bool fam = magi_stream_family_mc(h, n);
-    if (h->n_chains != n || fam != h->family_mc) drop_graph(h);
+    const StreamKernel k = magi_stream_kernel(h, n);
+    if (h->n_chains != n || k != h->stream_kernel) drop_graph(h);
     if (h->n_chains != n && h->ch.vop)       // the mirror's layout depends on the chain count: entries the new layout never writes must read zero
         MAGI_HIP_CHECK(h, hipMemsetAsync(h->ch.vop, 0, sizeof(double) * h->vop_elems, h->stream));
     h->n_chains = n;
     h->ch.n_chains = n;
-    h->family_mc = fam;
-    const bool sepk = fam && magi_drift_separable(h->pb.drift);
-    if ((h->ch.sep != 0) != sepk && h->ch.tpart) {      // the two streaming paths lay tpart out differently: slots the new one never writes must read zero
-        const size_t tpn = std::max(magi_drift_separable(h->pb.drift) ? magi_sep_tpart_elems(h->pb, h->cap_chains) : (size_t)0,
-                                    (size_t)h->cap_chains * 4 * h->pb.D * h->pb.nb * h->pb.Np);
-        MAGI_HIP_CHECK(h, hipMemsetAsync(h->ch.tpart, 0, sizeof(double) * tpn, h->stream));
-    }
+    h->stream_kernel = k;
+    const bool sepk = k == StreamKernel::Sep8 || k == StreamKernel::Sep16;
+    if ((h->ch.sep != 0) != sepk && h->ch.tpart)      // the two streaming paths lay tpart out differently: slots the new one never writes must read zero
+        MAGI_HIP_CHECK(h, hipMemsetAsync(h->ch.tpart, 0, sizeof(double) * tpart_elems(h, h->cap_chains), h->stream));
     h->ch.sep = sepk ? 1 : 0;
-    h->ch.mc = (fam && !sepk) ? 1 : 0;
+    h->ch.mc = k == StreamKernel::Mc ? 1 : 0;
     return MAGI_OK;
 }
 
@@ -888,23 +911,12 @@ int magi_fit_hparams(magi_handle* h, const double* I, int N, int D, const double
 
 int magi_set_option(magi_handle* h, const char* name, int64_t value) {
     if (!h || !name) return MAGI_E_BADARG;
-    const std::string k(name);
-    MagiOptions& o = h->opt;
-    if (k == "stream_family") { if (value < 0 || value > 2) return magi_fail(h, MAGI_E_BADARG, "stream_family: 0 auto, 1 mc, 2 valu"); o.stream_family = (int)value; }
-    else if (k == "sep_pair_min") o.sep_pair_min = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
-    else if (k == "family_chains") { if (value < 0 || value > 4096) return magi_fail(h, MAGI_E_BADARG, "family_chains in [0, 4096]"); o.family_chains = (int)value; }
-    else if (k == "fused_parity") o.fused_parity = value == 1;
-    else if (k == "gemm_remap_min") o.gemm_remap_min = (int)std::max<int64_t>(0, std::min<int64_t>(value, 1 << 30));
-    else if (k == "potrf_lookahead_min") { if (value < 0) return magi_fail(h, MAGI_E_BADARG, "potrf_lookahead_min >= 0"); o.potrf_lookahead_min = (int)value; }
-    else if (k == "potrf_panels") { if (value < 1 || value > 16) return magi_fail(h, MAGI_E_BADARG, "potrf_panels in [1, 16]"); o.potrf_panels = (int)value; }
-    else if (k == "slot_budget_graphs") o.slot_budget_graphs = std::max<int64_t>(0, value);
-    else if (k == "no_graph") o.no_graph = value != 0;
-    else if (k == "fit_host_loop") o.fit_host_loop = value != 0;
-    else if (k == "fit_per_component") o.fit_per_component = value != 0;
-    else if (k == "build_profile") o.build_profile = value != 0;
-    else if (k == "build_serial") o.build_serial = value != 0;
-    else return magi_fail(h, MAGI_E_BADARG, "unknown option '" + k + "'");
-    return MAGI_OK;
+    for (const OptRow& r : kOptions) {
+        if (std::strcmp(r.name, name) != 0) continue;
+        if (set_option(h->opt, r, value)) return MAGI_OK;
+        return magi_fail(h, MAGI_E_BADARG, std::string(r.name) + " in [" + std::to_string(r.lo) + ", " + std::to_string(r.hi) + "]");
+    }
+    return magi_fail(h, MAGI_E_BADARG, std::string("unknown option '") + name + "'");
 }
 
 int magi_build_profile(magi_handle* h, double* flops, double* ms, int64_t* calls) {
@@ -938,7 +950,8 @@ int magi_gradient_bytes(magi_handle* h, int n_chains, double* phase_bytes) {
     phase_bytes[4] = tiles + 2.0 * (double)n_chains * pb.n_tasks * MAGI_TB * 8.0;   // k_stream / k_stream_mc: + 2 TB partials per block and chain
     phase_bytes[5] = (double)n_chains * magi_leap_wgs(pb) * PART_K * 8.0; // tail: the workgroup partials
     phase_bytes[6] = 4.0 * vec * nslot + 10.0 * vec;                       // k_point: block partials of the four products; X, yobs, p, rho, g, p_leaf, p', x'
-    if (h->have_problem && magi_stream_family_mc(h, n_chains) && magi_drift_separable(pb.drift)) {
+    const StreamKernel k = magi_stream_kernel(h, n_chains);
+    if (h->have_problem && (k == StreamKernel::Sep8 || k == StreamKernel::Sep16)) {
         // k_stream_sep writes a block vector per (task, product, matrix-core column in use) and reads its operands from the mirror planes
         // (once per XCD at the fabric); its point kernel re-reads the product slots and writes the next slot's mirror
         double st = 0.0, op = 0.0, pr = 0.0, mw = 0.0;
@@ -953,12 +966,8 @@ int magi_gradient_bytes(magi_handle* h, int n_chains, double* phase_bytes) {
 int magi_stream_kernel_name(magi_handle* h, int n_chains, char* buf, int cap) {
     if (!h || !buf || cap < 2) return MAGI_E_BADARG;
     if (!h->have_matrices || !h->have_problem) return magi_fail(h, MAGI_E_STATE, "set matrices and problem first");
-    std::string s;
-    if (magi_stream_family_mc(h, n_chains))
-        s = magi_drift_separable(h->pb.drift) ? (n_chains <= 8 ? "k_stream_sep<CW=8>" : "k_stream_sep<CW=16>") : "k_stream_mc";
-    else
-        s = n_chains >= 2 ? "k_stream<2>" : "k_stream<1>";
-    std::snprintf(buf, (size_t)cap, "%s", s.c_str());
+    static const char* const names[] = {"k_stream<1>", "k_stream<2>", "k_stream_mc", "k_stream_sep<CW=8>", "k_stream_sep<CW=16>"};   // (StreamKernel order)
+    std::snprintf(buf, (size_t)cap, "%s", names[(int)magi_stream_kernel(h, n_chains)]);
     return MAGI_OK;
 }
 

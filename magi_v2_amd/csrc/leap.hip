@@ -1063,57 +1063,43 @@ __global__ __launch_bounds__(MAGI_TAIL_THREADS) void k_leap_finalize(DevProblem 
     }
 }
 
-template <int NC, int DRIFT>
-int launch_stream_nd(magi_handle* h, int n_chains, int parity, bool with_decisions, hipStream_t s) {
-    const DevProblem& pb = h->pb;
-    const dim3 grid(pb.n_tasks + (with_decisions ? NC : 0), (n_chains + NC - 1) / NC);      // + one decision workgroup per chain
-    {
-    if (h->prof_e0) hipExtLaunchKernelGGL((k_stream<NC, DRIFT>), grid, dim3(64 * ST_WAVES), 0, s, h->prof_e0, h->prof_e1, 0, pb, h->ch, h->cfg, parity);
-    else hipLaunchKernelGGL((k_stream<NC, DRIFT>), grid, dim3(64 * ST_WAVES), 0, s, pb, h->ch, h->cfg, parity);
-    }
+// Launches kernel k (`what` heads the error message); while magi_sampler_profile has set the handle's event pair, as an extended
+// launch that records the kernel's own begin / end in them.
+template <typename... P, typename... A>
+int launch(magi_handle* h, const char* what, void (*k)(P...), dim3 grid, dim3 block, hipStream_t s, A... args) {
+    if (h->prof_e0) hipExtLaunchKernelGGL(k, grid, block, 0, s, h->prof_e0, h->prof_e1, 0, args...);
+    else hipLaunchKernelGGL(k, grid, block, 0, s, args...);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("stream launch: ") + hipGetErrorString(e));
+    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string(what) + hipGetErrorString(e));
     return MAGI_OK;
 }
 
-template <int NC>
-int launch_stream_nc(magi_handle* h, int n_chains, int parity, bool with_decisions, hipStream_t s) {
-#define MAGI_CALL(DR) return launch_stream_nd<NC, DR>(h, n_chains, parity, with_decisions, s)
-    MAGI_DRIFT_DISPATCH(h->pb.drift, MAGI_CALL);
-#undef MAGI_CALL
-    return MAGI_OK;
+template <int NC, int DRIFT>
+int launch_stream_valu(magi_handle* h, int n_chains, int parity, bool with_decisions, hipStream_t s) {
+    const dim3 grid(h->pb.n_tasks + (with_decisions ? NC : 0), (n_chains + NC - 1) / NC);      // + one decision workgroup per chain
+    return launch(h, "stream launch: ", k_stream<NC, DRIFT>, grid, dim3(64 * ST_WAVES), s, h->pb, h->ch, h->cfg, parity);
+}
+
+// (k_stream_sep exists for separable drifts only, k_stream_mc for the others: magi_stream_kernel never picks the missing one)
+template <int DRIFT>
+int launch_stream_mc(magi_handle* h, int n_chains, int parity, bool with_decisions, hipStream_t s) {
+    const DevProblem& pb = h->pb;
+    const int dec = with_decisions ? MC : 0, groups = (n_chains + MC - 1) / MC;
+    const char* what = "stream (matrix-core) launch: ";
+    if constexpr (DriftT<DRIFT>::SEP) {          // grid.z = basis planes
+        if (h->stream_kernel == StreamKernel::Sep8)
+            return launch(h, what, k_stream_sep<DRIFT, 8>, dim3(pb.n_stasks + dec, groups, SepLayout<DRIFT>::gz(8)), dim3(256), s, pb, h->ch, h->cfg, parity);
+        return launch(h, what, k_stream_sep<DRIFT, 16>, dim3(pb.n_stasks + dec, groups, SepLayout<DRIFT>::gz(16)), dim3(256), s, pb, h->ch, h->cfg, parity);
+    } else {
+        return launch(h, what, k_stream_mc<DRIFT>, dim3(pb.n_tasks + dec, groups), dim3(256), s, pb, h->ch, h->cfg, parity);
+    }
 }
 
 }  // namespace
 
 int magi_leap_wgs(const DevProblem& pb) { return (pb.N + PT_POINTS - 1) / PT_POINTS; }
 
-template <int DRIFT>
-int launch_stream_mc(magi_handle* h, int n_chains, int parity, bool with_decisions, hipStream_t s) {
-    const DevProblem& pb = h->pb;
-    const int groups = (n_chains + MC - 1) / MC;
-    if constexpr (DriftT<DRIFT>::SEP) {
-        // separable drifts: ONE kernel family for every chain count; grid.z = basis planes
-        if (n_chains <= 8) {
-            const dim3 grid(pb.n_stasks + (with_decisions ? MC : 0), groups, SepLayout<DRIFT>::gz(8));
-            if (h->prof_e0) hipExtLaunchKernelGGL((k_stream_sep<DRIFT, 8>), grid, dim3(256), 0, s, h->prof_e0, h->prof_e1, 0, pb, h->ch, h->cfg, parity);
-            else hipLaunchKernelGGL((k_stream_sep<DRIFT, 8>), grid, dim3(256), 0, s, pb, h->ch, h->cfg, parity);
-        } else {
-            const dim3 grid(pb.n_stasks + (with_decisions ? MC : 0), groups, SepLayout<DRIFT>::gz(16));
-            if (h->prof_e0) hipExtLaunchKernelGGL((k_stream_sep<DRIFT, 16>), grid, dim3(256), 0, s, h->prof_e0, h->prof_e1, 0, pb, h->ch, h->cfg, parity);
-            else hipLaunchKernelGGL((k_stream_sep<DRIFT, 16>), grid, dim3(256), 0, s, pb, h->ch, h->cfg, parity);
-        }
-    } else {
-    const dim3 grid(pb.n_tasks + (with_decisions ? MC : 0), groups);
-    if (h->prof_e0) hipExtLaunchKernelGGL((k_stream_mc<DRIFT>), grid, dim3(256), 0, s, h->prof_e0, h->prof_e1, 0, pb, h->ch, h->cfg, parity);
-    else hipLaunchKernelGGL((k_stream_mc<DRIFT>), grid, dim3(256), 0, s, pb, h->ch, h->cfg, parity);
-    }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("stream (matrix-core) launch: ") + hipGetErrorString(e));
-    return MAGI_OK;
-}
-
-// Which kernel family streams the operator blocks: one or two chains -> the VALU kernel k_stream<1 | 2>, three or more -> a
+// Which kernel streams the operator blocks: one or two chains -> the VALU kernel k_stream<1 | 2>, three or more -> a
 // matrix-core kernel (k_stream_sep for separable drifts, k_stream_mc otherwise).  The two sum in different orders, so a chain's rounding depends on the size of the batch it
 // runs in (1-2 against >= 3).  MAGI_STREAM_FAMILY=mc routes EVERY batch size through the matrix-core kernel: a chain's samples
 // are then bit-identical whatever shares the GPU with it (uneven shards, e.g. 5 chains on 2 GPUs = 3 + 2), at the price of the
@@ -1123,12 +1109,15 @@ int launch_stream_mc(magi_handle* h, int n_chains, int parity, bool with_decisio
 // as long as its longest workgroup, and the matrix-core kernels' workgroups are long (prologue + 8 dependent steps + stores).  Slot time,
 // VALU against matrix-core kernel: N = 161, b = 80, 8 chains 12.9 / 16.0 us; N = 256, 8 chains 13.0 / 16.0; N = 512, 3 and 4 chains
 // (288 workgroups) 14.6 / 16.0 and 14.9 / 16.2; N = 512, 8 chains (576) 20.0 / 17.0; N = 1024, 3 chains 30.7 / 23.5.
-// stream_family = valu forces the VALU kernel for every batch (A/B).
-bool magi_stream_family_mc(const magi_handle* h, int n_chains) {
-    if (h->opt.stream_family == 1) return true;
-    if (h->opt.stream_family == 2) return false;
+// stream_family = valu forces the VALU kernel for every batch (A/B).  k_stream_sep's chain columns per operand line: xop_width.
+// A function of (options, problem, n_chains) alone: magi_stream_kernel_name and magi_gradient_bytes ask it about other batch sizes.
+StreamKernel magi_stream_kernel(const magi_handle* h, int n_chains) {
     const int n = h->opt.family_chains > 0 ? std::max(n_chains, h->opt.family_chains) : n_chains;
-    return n >= 3 && (long)h->pb.n_tasks * ((n + 1) / 2) > 320;
+    const bool matrix_cores = h->opt.stream_family == 1 ||
+                              (h->opt.stream_family != 2 && n >= 3 && (long)h->pb.n_tasks * ((n + 1) / 2) > 320);
+    if (!matrix_cores) return n_chains >= 2 ? StreamKernel::Valu2 : StreamKernel::Valu1;
+    if (!magi_drift_separable(h->pb.drift)) return StreamKernel::Mc;
+    return xop_width(n_chains) == 8 ? StreamKernel::Sep8 : StreamKernel::Sep16;
 }
 
 bool magi_drift_separable(int drift) {
@@ -1200,57 +1189,56 @@ void magi_sep_traffic(const DevProblem& pb, int n_chains, double* stores, double
 int magi_launch_mirror(magi_handle* h, int n_chains, hipStream_t s) {
     if (!h->ch.sep) return MAGI_OK;
     const dim3 g((h->pb.N + 255) / 256, n_chains), b(256);
-#define MAGI_CALL(DR) hipLaunchKernelGGL(k_mirror<DR>, g, b, 0, s, h->pb, h->ch)
+#define MAGI_CALL(DR) return launch(h, "mirror launch: ", k_mirror<DR>, g, b, s, h->pb, h->ch)
     MAGI_DRIFT_DISPATCH(h->pb.drift, MAGI_CALL);
 #undef MAGI_CALL
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("mirror launch: ") + hipGetErrorString(e));
     return MAGI_OK;
 }
 
 int magi_launch_stream(magi_handle* h, int n_chains, int parity, bool with_decisions, hipStream_t s) {
-    if (h->family_mc) {          // (separable drifts: k_stream_sep, else k_stream_mc)
+    switch (h->stream_kernel) {        // (the order of the cases is the order of the kernels in the code object)
+    case StreamKernel::Mc:
+    case StreamKernel::Sep8:
+    case StreamKernel::Sep16:
 #define MAGI_CALL(DR) return launch_stream_mc<DR>(h, n_chains, parity, with_decisions, s)
         MAGI_DRIFT_DISPATCH(h->pb.drift, MAGI_CALL);
 #undef MAGI_CALL
+        break;
+    case StreamKernel::Valu2:          // (chain pairs on grid.y)
+#define MAGI_CALL(DR) return launch_stream_valu<2, DR>(h, n_chains, parity, with_decisions, s)
+        MAGI_DRIFT_DISPATCH(h->pb.drift, MAGI_CALL);
+#undef MAGI_CALL
+        break;
+    case StreamKernel::Valu1:
+#define MAGI_CALL(DR) return launch_stream_valu<1, DR>(h, n_chains, parity, with_decisions, s)
+        MAGI_DRIFT_DISPATCH(h->pb.drift, MAGI_CALL);
+#undef MAGI_CALL
+        break;
     }
-    if (n_chains >= 2) return launch_stream_nc<2>(h, n_chains, parity, with_decisions, s);       // (chain pairs on grid.y)
-    return launch_stream_nc<1>(h, n_chains, parity, with_decisions, s);
+    return MAGI_OK;
 }
 
 int magi_launch_point(magi_handle* h, int n_chains, int parity, hipStream_t s) {
-    const DevProblem& pb = h->pb;
-    const dim3 g(magi_leap_wgs(pb), n_chains), b(PT_THREADS);
-#define MAGI_CALL(DR) do { if (h->prof_e0) hipExtLaunchKernelGGL(k_point<DR>, g, b, 0, s, h->prof_e0, h->prof_e1, 0, pb, h->ch, parity); \
-                           else hipLaunchKernelGGL(k_point<DR>, g, b, 0, s, pb, h->ch, parity); } while (0)
-    MAGI_DRIFT_DISPATCH(pb.drift, MAGI_CALL);
+    const dim3 g(magi_leap_wgs(h->pb), n_chains), b(PT_THREADS);
+#define MAGI_CALL(DR) return launch(h, "point launch: ", k_point<DR>, g, b, s, h->pb, h->ch, parity)
+    MAGI_DRIFT_DISPATCH(h->pb.drift, MAGI_CALL);
 #undef MAGI_CALL
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("point launch: ") + hipGetErrorString(e));
     return MAGI_OK;
 }
 
 int magi_launch_read_tiles(magi_handle* h, int rev, hipStream_t s) {
-    hipLaunchKernelGGL(k_read_tiles, dim3(h->pb.n_tasks), dim3(256), 0, s, reinterpret_cast<const double2*>(h->pb.tiles), h->d_fin, rev);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("read_tiles launch: ") + hipGetErrorString(e));
-    return MAGI_OK;
+    return launch(h, "read_tiles launch: ", k_read_tiles, dim3(h->pb.n_tasks), dim3(256), s, reinterpret_cast<const double2*>(h->pb.tiles), h->d_fin, rev);
 }
 
 int magi_launch_plan_eval(magi_handle* h, int n_chains, hipStream_t s, int parity) {
-    hipLaunchKernelGGL(k_plan_eval, dim3((n_chains + 63) / 64), dim3(64), 0, s, h->ch, parity);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("plan launch: ") + hipGetErrorString(e));
-    return MAGI_OK;
+    return launch(h, "plan launch: ", k_plan_eval, dim3((n_chains + 63) / 64), dim3(64), s, h->ch, parity);
 }
 
 int magi_launch_leap_finalize(magi_handle* h, int n_chains, double* d_out, hipStream_t s, int parity) {
     const dim3 g(n_chains), b(MAGI_TAIL_THREADS);
-#define MAGI_CALL(DR) hipLaunchKernelGGL(k_leap_finalize<DR>, g, b, 0, s, h->pb, h->ch, d_out, parity)
+#define MAGI_CALL(DR) return launch(h, "leap_finalize launch: ", k_leap_finalize<DR>, g, b, s, h->pb, h->ch, d_out, parity)
     MAGI_DRIFT_DISPATCH(h->pb.drift, MAGI_CALL);
 #undef MAGI_CALL
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("leap_finalize launch: ") + hipGetErrorString(e));
     return MAGI_OK;
 }
 

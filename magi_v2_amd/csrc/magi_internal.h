@@ -845,7 +845,7 @@ __device__ inline FinalizeOut finalize_gradient(const DevProblem& pb, double* vb
 // launch, and a stray variable cannot change what a running job computes between two calls).
 #define MAGI_GEMM_REMAP_MIN_DEFAULT 10
 struct MagiOptions {
-    int stream_family = 0;              // 0 auto (leap.hip: magi_stream_family_mc), 1 "mc": every batch on the matrix-core kernel, 2 "valu"
+    int stream_family = 0;              // 0 auto (leap.hip: magi_stream_kernel), 1 "mc": every batch on the matrix-core kernel, 2 "valu"
     int family_chains = 0;              // > 0: "auto" decides as if the batch had this many chains (the largest per-GPU share of a sharded job:
                                         // every rank then runs the same kernel family, whatever its own share -- shard.family_chains_for)
     int sep_pair_min = 256;             // pack.hip: pair the diagonal blocks FH_bb + FK_bb when there are more tasks than this
@@ -860,6 +860,9 @@ struct MagiOptions {
     int build_profile = 0, build_serial = 0;           // build.hip: per-class device times (serialises), one component per group
 };
 void magi_options_from_env(MagiOptions& o);               // capi.hip
+
+// The streaming kernels: k_stream<1>, k_stream<2> (VALU), k_stream_mc, k_stream_sep<CW = 8 | 16> (matrix cores)
+enum class StreamKernel { Valu1, Valu2, Mc, Sep8, Sep16 };
 
 struct magi_handle {
     int device = 0;
@@ -892,7 +895,7 @@ struct magi_handle {
     DevChains ch{};
     SamplerCfgDev cfg{};
     bool sampler_ready = false;
-    bool family_mc = false;          // magi_stream_family_mc(n_chains) at the last magi_ensure_chains
+    StreamKernel stream_kernel = StreamKernel::Valu1;      // magi_stream_kernel(n_chains) at the last magi_ensure_chains
     int num_results = 0;
     // graph of G leapfrog slots
     hipGraph_t graph = nullptr;
@@ -946,7 +949,7 @@ int magi_launch_stream(magi_handle* h, int n_chains, int parity, bool with_decis
 int magi_launch_point(magi_handle* h, int n_chains, int parity, hipStream_t s);                            // k_point: leapfrog epilogue per grid point
 int magi_launch_leap_finalize(magi_handle* h, int n_chains, double* d_out, hipStream_t s, int parity = 0);
 int magi_leap_wgs(const DevProblem& pb);
-bool magi_stream_family_mc(const magi_handle* h, int n_chains);        // leap.hip
+StreamKernel magi_stream_kernel(const magi_handle* h, int n_chains);    // leap.hip: the streaming kernel that serves a batch of n_chains
 int magi_build_profile_get(const magi_handle* h, double* flops, double* ms, long* calls);           // build.hip
 int magi_fit_hparams_device(magi_handle* h, const double* I, int N, int D, const double* X, const double* mu, const double* mu_phi2,
                             const double* sd_phi2, const double* sig_loc, double nu, int iters, double lr, double jitter,

@@ -109,16 +109,25 @@ def test_build_multi_block_inverse_property(eng, N):
         assert np.abs(K_inv[d] @ K_ref - np.eye(N)).max() < 200 * cond * EPS * condK ** 0.5
 
 
-def test_concurrent_and_serial_component_builds_are_identical(eng, monkeypatch):
+def test_concurrent_and_serial_component_builds_are_identical(eng):
     """The D components are built on D streams / work spaces by default, one after the other on one work space with
-    MAGI_BUILD_SERIAL=1 (also the path taken when HBM is short): same kernels, same operands, so the matrices must
-    be bit-identical -- any difference would be a missing dependency between streams."""
+    option build_serial (also the path taken when HBM is short): same kernels, same operands, so the matrices must
+    be bit-identical -- any difference would be a missing dependency between streams.  The profiled launch counts show
+    that the serial path ran: the three m / K products are one launch per group of components, so D times as many."""
     N = 300
     I = np.arange(N) * 0.025
     phi1, phi2 = np.array([0.03, 0.2, 1.1, 0.5]), np.array([0.3, 0.15, 0.4, 0.22])
-    conc = eng.build_matrices(I, phi1, phi2, 2.01)
-    monkeypatch.setenv("MAGI_BUILD_SERIAL", "1")
-    ser = eng.build_matrices(I, phi1, phi2, 2.01)
+    try:
+        eng.set_option("build_profile", 1)
+        conc = eng.build_matrices(I, phi1, phi2, 2.01)
+        conc_calls = eng.build_profile()["m_K_products"][2]
+        eng.set_option("build_serial", 1)
+        ser = eng.build_matrices(I, phi1, phi2, 2.01)
+        ser_calls = eng.build_profile()["m_K_products"][2]
+    finally:
+        eng.set_option("build_serial", 0)
+        eng.set_option("build_profile", 0)
+    assert (conc_calls, ser_calls) == (3, 3 * len(phi1))
     for a, b in zip(conc, ser):
         assert np.array_equal(a, b)
 

@@ -18,9 +18,9 @@ def data():
     return g["seir3_I"][:, 0], g["seir3_X_interp"], g
 
 
-def test_device_resident_loop_equals_host_loop(data, monkeypatch):
+def test_device_resident_loop_equals_host_loop(data):
     """The fit replays one captured graph per Adam step with the scalar tail (likelihood, priors, Adam) in a one-thread
-    kernel; MAGI_FIT_HOST_LOOP=1 runs the same kernels with that tail on the host.  Same arithmetic up to libm."""
+    kernel; option fit_host_loop runs the same kernels with that tail on the host.  Same arithmetic up to libm."""
     from magi_v2_amd.engine import MagiEngine
     I, X, g = data
     I, X = I[:161], X[:161]
@@ -28,9 +28,8 @@ def test_device_resident_loop_equals_host_loop(data, monkeypatch):
     init = orc.hparams_initial(X)
     outs = []
     for host_loop in (False, True):
-        if host_loop:
-            monkeypatch.setenv("MAGI_FIT_HOST_LOOP", "1")
         eng = MagiEngine(0)
+        eng.set_option("fit_host_loop", int(host_loop))
         outs.append(eng.fit_hparams(I, X, X.mean(axis=0), [p[0] for p in pri], [p[1] for p in pri], init["sigma_sqs"],
                                     init["phi1s"], init["phi2s"], init["sigma_sqs"], num_iters=60, want_trace=True))
         eng.close()

@@ -130,23 +130,6 @@ def test_config5_sampler_runs_at_n8192():
     eng.close()
 
 
-class _env:
-    """Environment switches of csrc/build.hip for the duration of a block (read by the library at every launch)."""
-    def __init__(self, **kv):
-        self.kv = {k: str(v) for k, v in kv.items() if v is not None}
-
-    def __enter__(self):
-        self.old = {k: os.environ.get(k) for k in self.kv}
-        os.environ.update(self.kv)
-
-    def __exit__(self, *a):
-        for k, v in self.old.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-
-
 @pytest.mark.parametrize("N,remap,panels,lookahead", [(1024, None, None, None), (2048, None, None, None), (2048, 1, 2, None), (2048, 1, 8, None), (2048, None, None, 1024),
                                                       (2048, 1, 4, 1024)],
                          ids=["1024", "2048", "2048-remap-2panels", "2048-remap-8panels", "2048-lookahead", "2048-remap-4panels-lookahead"])

@@ -14,6 +14,28 @@ def header_functions():
     return sorted(set(re.findall(r"\b(magi_[a-z_0-9]+)\s*\(", src)))
 
 
+def option_table():
+    """(name, environment variable or None) of every row of the option table in csrc/capi.hip"""
+    src = open(os.path.join(ROOT, "magi_v2_amd", "csrc", "capi.hip")).read()
+    table = src[src.index("const OptRow kOptions[] = {"):]
+    table = table[:table.index("};")]
+    return sorted((n, None if e == "nullptr" else e.strip('"')) for n, e in re.findall(r'\{"([a-z_]+)",\s*("MAGI_[A-Z_]+"|nullptr)', table))
+
+
+def header_options():
+    """(name, environment variable or None) of every option the comment above magi_set_option in include/magi_hip.h lists"""
+    src = open(os.path.join(ROOT, "include", "magi_hip.h")).read()
+    doc = src[:src.index("int magi_set_option(")]
+    doc = doc[doc.rindex("/*"):]
+    return sorted((n, e or None) for n, e in re.findall(r'^\s*\*\s+"([a-z_]+)"\s+(?:(MAGI_[A-Z_]+)|\(none)', doc, flags=re.M))
+
+
+def test_header_lists_every_option_of_the_table():
+    table = option_table()
+    assert len(table) >= 13 and ("slot_budget_graphs", None) in table
+    assert header_options() == table
+
+
 def test_library_builds_and_exports_every_declared_symbol():
     from magi_v2_amd import build, engine
     build.build_lib()

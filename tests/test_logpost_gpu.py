@@ -117,3 +117,29 @@ def test_error_paths():
         eng.sampler_init(cfg, X, g["state_sig_pre"][0], g["state_th_pre"][0], seed=1)
     assert ei.value.code == -4
     eng.close()
+
+
+def test_set_option_takes_every_option_of_the_table_and_checks_ranges():
+    """magi_set_option on a live handle: every option of the table in csrc/capi.hip takes values inside its range (clamped
+    options and flags take any value), the ranged options reject values outside it, and an unknown name is an error."""
+    from magi_v2_amd.engine import MagiEngine, MagiHipError
+    from tests.test_library_cpu import option_table
+    valid = {"stream_family": (0, 2), "family_chains": (0, 4096), "sep_pair_min": (-1, 1 << 31), "fused_parity": (0, 1),
+             "gemm_remap_min": (-1, 1 << 31), "potrf_panels": (1, 16), "potrf_lookahead_min": (0, 1 << 40), "no_graph": (0, 7),
+             "fit_host_loop": (0, 1), "fit_per_component": (0, 1), "build_profile": (0, 1), "build_serial": (0, 1),
+             "slot_budget_graphs": (-1, 0)}
+    rejected = {"stream_family": (-1, 3), "family_chains": (-1, 4097), "potrf_panels": (0, 17), "potrf_lookahead_min": (-1,)}
+    assert sorted(valid) == [name for name, _ in option_table()]
+    eng = MagiEngine(0)
+    for name, values in valid.items():
+        for v in values:
+            eng.set_option(name, v)
+    for name, values in rejected.items():
+        for v in values:
+            with pytest.raises(MagiHipError) as ei:
+                eng.set_option(name, v)
+            assert ei.value.code == -1 and name in str(ei.value)
+    with pytest.raises(MagiHipError) as ei:
+        eng.set_option("no_such_option", 1)
+    assert ei.value.code == -1 and "unknown option" in str(ei.value)
+    eng.close()

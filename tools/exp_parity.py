@@ -1,5 +1,5 @@
 """Dev: the fused log posterior evaluated as an even and as an odd leapfrog slot, 1 / 2 / 3 states, against the three-phase path."""
-import os, sys
+import sys
 import numpy as np
 sys.path.insert(0, ".")
 from oracle import magi_oracle as orc
@@ -13,7 +13,7 @@ for tag in sys.argv[1:] or ["sirw_N41", "seir4_N81", "seir3_N161"]:
         eng = engine_for(pr, None)
         ref = eng.logpost_grad(X, sp, tp, 1.0)
         for par in (0, 1):
-            os.environ["MAGI_FUSED_PARITY"] = str(par)
+            eng.set_option("fused_parity", par)
             f = eng.logpost_grad(X, sp, tp, 1.0, fused=True)
             print(tag, "states", n, "parity", par, "logp rel %.2e  gX %.2e  gsig %.2e  gth %.2e" % (np.abs((f[0] - ref[0]) / ref[0]).max(),
                   np.abs(f[1] - ref[1]).max() / np.abs(ref[1]).max(), np.abs(f[2] - ref[2]).max() / np.abs(ref[2]).max(), np.abs(f[3] - ref[3]).max() / np.abs(ref[3]).max()))
