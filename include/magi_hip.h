@@ -303,7 +303,7 @@ int magi_set_option(magi_handle* h, const char* name, int64_t value);
 int magi_build_profile(magi_handle* h, double* flops, double* ms, int64_t* calls);
 
 /* Diagnostics: the 64-double transformed-parameter block of a chain (softplus / sigmoid / log
- * terms of the state in flight; in a -DMAGI_TAIL_STAMPS build entries 40.. hold timing stamps). */
+ * terms of the state in flight; in a -DMAGI_STAMPS=<kernel> dev build entries 40.. hold timing stamps, csrc/stamps.h). */
 int magi_debug_par(magi_handle* h, int chain, double* out64);
 
 #ifdef __cplusplus

@@ -1,5 +1,9 @@
 """Build libmagi_hip.so (hipcc, gfx950) in-tree.  Used by __graft_entry__.build() and by hand:
-    python -m magi_v2_amd.build
+    python -m magi_v2_amd.build [--force]
+This is the library's one compile recipe: the product, the drift-specialised builds (jit.py), the host-sanitizer build
+(tools/sanitize_host.py) and the dev variants all take their hipcc commands from compile_command and build through build_library.
+A dev variant (device time stamps, csrc/stamps.h; tuning switches) never touches the product:
+    python -m magi_v2_amd.build --variant NAME [-DFLAG ...]   ->  build_variants/NAME/libmagi_hip.so   (select with MAGI_HIP_LIB)
 """
 import glob
 import os
@@ -9,18 +13,45 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmagi_hip.so")
+OBJDIR = os.path.join(HERE, "build")
+VARIANTS = os.path.join(os.path.dirname(HERE), "build_variants")
+FLAGS_FILE = "flags.txt"          # beside the objects: the extra flags they were compiled with, one per line
+BASE_FLAGS = ["-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function"]
+
+
+def hipcc():
+    return os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 
 def sources():
     return sorted(glob.glob(os.path.join(CSRC, "*.hip")))
 
 
+def headers():
+    return glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "magi_hip.h")]
+
+
+def compile_command(src, extra=()):
+    """The hipcc command (without -c / -o / --save-temps) for one translation unit; `extra` flags go last."""
+    # -ffp-contract=on: fused multiply-adds are formed per source expression (front end), not by the optimiser, so
+    # every instantiation of a kernel (1, 2, 4 chains per matrix pass) rounds a chain's arithmetic identically
+    contract = [] if os.path.basename(src) == "build.hip" else ["-ffp-contract=on"]     # (the matrix build keeps the default)
+    return [hipcc()] + BASE_FLAGS + contract + list(extra)
+
+
+def _built_flags(objdir):
+    try:
+        with open(os.path.join(objdir, FLAGS_FILE)) as fh:
+            return fh.read()
+    except OSError:
+        return None
+
+
 def needs_build():
-    if not os.path.exists(LIB):
+    if not os.path.exists(LIB) or _built_flags(OBJDIR) != "":
         return True
     t = os.path.getmtime(LIB)
-    deps = sources() + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "magi_hip.h")]
-    return any(os.path.getmtime(p) > t for p in deps)
+    return any(os.path.getmtime(p) > t for p in sources() + headers())
 
 
 def isa_path(obj):
@@ -68,35 +99,64 @@ def compile_checked(jobs, verbose=True):
                 os.remove(junk)
 
 
-def build_lib(force=False, verbose=True):
-    if not force and not needs_build():
-        return LIB
-    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    objs = []
-    objdir = os.path.join(HERE, "build")
+def build_library(units, objdir, out, extra=(), reuse=None, link_flags=(), force=False, verbose=True):
+    """Compiles `units` (csrc/*.hip) with compile_command(unit, extra) into `objdir` through compile_checked and links them into `out`;
+    reuse = {unit: object} are linked as they are.  An object is recompiled when it is older than its source or a header, or when
+    `extra` is not the flag list it was compiled with (FLAGS_FILE in `objdir`)."""
+    reuse = reuse or {}
     os.makedirs(objdir, exist_ok=True)
-    jobs = []
-    for src in sources():
+    flags = "\n".join(extra)
+    stale = force or _built_flags(objdir) != flags
+    objs, jobs = [], []
+    for src in units:
+        if src in reuse:
+            objs.append(reuse[src])
+            continue
         obj = os.path.join(objdir, os.path.basename(src) + ".o")
         objs.append(obj)
-        hdrs = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "magi_hip.h")]
-        if (not force and os.path.exists(obj) and os.path.getmtime(obj) > os.path.getmtime(src)
-                and all(os.path.getmtime(obj) > os.path.getmtime(hh) for hh in hdrs)):
+        if (not stale and os.path.exists(obj) and os.path.exists(isa_path(obj))
+                and all(os.path.getmtime(obj) > os.path.getmtime(p) for p in [src] + headers())):
             continue
-        # -ffp-contract=on: fused multiply-adds are formed per source expression (front end), not by the optimiser, so
-        # every instantiation of a kernel (1, 2, 4 chains per matrix pass) rounds a chain's arithmetic identically
-        contract = [] if os.path.basename(src) == "build.hip" else ["-ffp-contract=on"]     # (the matrix build keeps the default)
-        cmd = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wall", "-Wno-unused-function"] + contract + \
-            os.environ.get("MAGI_EXTRA_CFLAGS", "").split()
-        jobs.append((cmd, src, obj))
+        jobs.append((compile_command(src, extra), src, obj))
     compile_checked(jobs, verbose)
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", LIB] + objs + ["-Wl,-rpath,/opt/rocm/lib"]
-    if verbose:
-        print(" ".join(cmd), flush=True)
-    subprocess.check_call(cmd)
-    return LIB
+    with open(os.path.join(objdir, FLAGS_FILE), "w") as fh:
+        fh.write(flags)
+    if jobs or not os.path.exists(out) or any(os.path.getmtime(o) > os.path.getmtime(out) for o in objs):
+        cmd = [hipcc(), "--offload-arch=gfx950", "-shared", "-fPIC"] + list(link_flags) + ["-o", out] + objs + ["-Wl,-rpath,/opt/rocm/lib"]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    return out
+
+
+def build_lib(force=False, verbose=True):
+    """The product library: the recipe with no extra flags (it takes none from the environment)."""
+    if not force and not needs_build():
+        return LIB
+    return build_library(sources(), OBJDIR, LIB, force=force, verbose=verbose)
+
+
+def variant_dir(name):
+    if not name or name in (".", "..") or os.sep in name or (os.altsep and os.altsep in name):
+        raise ValueError(f"variant name {name!r}: one plain directory name under build_variants/")
+    return os.path.join(VARIANTS, name)
+
+
+def build_variant(name, extra, force=False, verbose=True):
+    """Every unit compiled with `extra` into build_variants/NAME/: objects, each unit's device ISA, libmagi_hip.so.  Never the product."""
+    d = variant_dir(name)
+    out = os.path.join(d, "libmagi_hip.so")
+    assert os.path.abspath(out) != os.path.abspath(LIB)
+    return build_library(sources(), d, out, extra=extra, force=force, verbose=verbose)
 
 
 if __name__ == "__main__":
-    build_lib(force="--force" in sys.argv)
-    print(LIB)
+    args = sys.argv[1:]
+    force = "--force" in args
+    args = [a for a in args if a != "--force"]
+    if args[:1] == ["--variant"] and len(args) >= 2:
+        print(build_variant(args[1], args[2:], force=force))
+    elif not args:
+        print(build_lib(force=force))
+    else:
+        sys.exit("usage: python -m magi_v2_amd.build [--force]  |  python -m magi_v2_amd.build [--force] --variant NAME [-DFLAG ...]")

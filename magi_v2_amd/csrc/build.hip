@@ -21,6 +21,7 @@
 #include <cstdlib>
 
 #include "magi_internal.h"
+#include "stamps.h"
 
 namespace {
 
@@ -510,13 +511,6 @@ __device__ __forceinline__ int dg_factor16(double* S, int b0, double* X, int x0)
     return fail;
 }
 
-#ifdef MAGI_DIAG_STAMPS      // dev: s_memtime at the phase boundaries of k_diag_chol_inv, printed by thread 0
-#define DG_STAMP(i) do { if (threadIdx.x == 0) dg_st[i] = __builtin_amdgcn_s_memtime(); } while (0)
-#define DG_STAMP_PRINT() do { if (threadIdx.x == 0 && block_row0 == 0) { printf("diag stamps (cycles from start):"); for (int q = 1; q < 16; ++q) printf(" %d:%lld", q, (long long)(dg_st[q] - dg_st[0])); printf("\n"); } } while (0)
-#else
-#define DG_STAMP(i) do {} while (0)
-#define DG_STAMP_PRINT() do {} while (0)
-#endif
 // grid.x = components of a batch: matrix, inverse block and status word of component z at z * bsA / bsL / bsS
 //
 // Schedule (round 4).  The register factorisation of a 32 x 32 diagonal sub-block (step 1) is a dependent chain on ONE wave -- 25 k of
@@ -532,9 +526,7 @@ __device__ __forceinline__ int dg_factor16(double* S, int b0, double* X, int x0)
 __global__ __launch_bounds__(256) void k_diag_chol_inv(double* A, long lda, int n, double* Linv /* [128][128] */, int* status, int block_row0,
                                                        long bsA, long bsL, int bsS) {
     A += (long)blockIdx.x * bsA; Linv += (long)blockIdx.x * bsL; status += (long)blockIdx.x * bsS;
-#ifdef MAGI_DIAG_STAMPS
-    unsigned long long dg_st[16] = {0};
-#endif
+    MAGI_STAMPS_DECL(diag, 16);
     extern __shared__ __attribute__((aligned(16))) double lds[];
     double* S = lds;                               // [128][DG_LD]
     double* dinv = lds + 128 * DG_LD;              // diagonal of the inverse
@@ -545,7 +537,7 @@ __global__ __launch_bounds__(256) void k_diag_chol_inv(double* A, long lda, int 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 15, lj = lane >> 4;
     if (tid == 0) bad = -1;
-    DG_STAMP(0);
+    MAGI_STAMP(diag, 0);
     const int nsb = (n + 31) >> 5, nl = 32 * nsb;          // live 32-wide sub-blocks (the identity padding behind them factors to itself)
 
     // ---- pieces --------------------------------------------------------------------------------------------------------------------
@@ -691,7 +683,7 @@ __global__ __launch_bounds__(256) void k_diag_chol_inv(double* A, long lda, int 
             }
         }
         __syncthreads();
-        DG_STAMP(2 + 3 * kb);
+        MAGI_STAMP(diag, 2 + 3 * kb);
         if (bad >= 0) break;
         publish(c0);
         if (kb == nsb - 1) break;
@@ -709,7 +701,7 @@ __global__ __launch_bounds__(256) void k_diag_chol_inv(double* A, long lda, int 
             }
         }
         __syncthreads();
-        DG_STAMP(3 + 3 * kb);
+        MAGI_STAMP(diag, 3 + 3 * kb);
     }
     if (bad >= 0) {
         if (tid == 0) atomicCAS(status, -1, block_row0 + bad);
@@ -724,14 +716,14 @@ __global__ __launch_bounds__(256) void k_diag_chol_inv(double* A, long lda, int 
         if (job < 2 * (nsb - 1)) xjob(nsb - 1, job >> 1, job & 1);
     }
     __syncthreads();
-    DG_STAMP(14);
+    MAGI_STAMP(diag, 14);
     store_L_cols(nsb - 1, tid, 256);
     if (nsb == 1) store_Linv_rows(0, tid, 256);
     if (nsb >= 3) store_Linv_rows(nsb - 2, tid, 256);
     if (nsb >= 2) store_Linv_rows(nsb - 1, tid, 256);
     for (int rb = nsb; rb < 4; ++rb) store_Linv_rows(rb, tid, 256);           // rows >= n of the dense inverse are zeros
-    DG_STAMP(15);
-    DG_STAMP_PRINT();
+    MAGI_STAMP(diag, 15);
+    MAGI_STAMPS_FLUSH(diag, threadIdx.x == 0 && block_row0 == 0 && blockIdx.x == MAGI_STAMP_WG, nullptr, 16);
 }
 
 // helpers --------------------------------------------------------------------------------------

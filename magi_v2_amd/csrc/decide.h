@@ -122,7 +122,7 @@ template <int DRIFT>
 __device__ __forceinline__ void decide_block(const DevProblem& pb, const DevChains& ch, const SamplerCfgDev& cfg, int chain, int parity, int all_done,
                                              double* sh /* 25*16 */, double* shs /* 24 */, ChainCtl* s_ctl, int* s_g, double* s_par /* PAR_COUNT */, double* s_ops /* OPS_COUNT * OPS_W */, double* s_cst /* 3 * MAGI_MAX_D: N_ds, LB, mu */) {
     const int tid = threadIdx.x;
-    MAGI_STAMP(ch.par, 8);
+    MAGI_STAMP(decide, 8);
     // ONE round of loads with no dependence on anything: control state, the previous plan, the state's parameter block
     // and the point phase's partial sums.  These decisions run next to a stream that saturates the memory system, where
     // every dependent round trip costs several microseconds -- their number, not the instruction count, is what matters.
@@ -153,9 +153,9 @@ __device__ __forceinline__ void decide_block(const DevProblem& pb, const DevChai
         for (int k = 0; k < MAGI_MAX_D; ++k) { s_cst[k] = pb.N_ds[k]; s_cst[MAGI_MAX_D + k] = pb.LB[k]; s_cst[2 * MAGI_MAX_D + k] = pb.mu[k]; }      // (static indices)
     }
     reduce_prefetch_ops_store<OPS_PER>(ops_v, s_ops);
-    MAGI_STAMP(ch.par, 2);
+    MAGI_STAMP(decide, 2);
     __syncthreads();
-    MAGI_STAMP(ch.par + (size_t)chain * PAR_COUNT, 0);
+    MAGI_STAMP(decide, 0);
     ChainCtl c = *s_ctl;
     const int dim = pb.dim;
     const int stop_k = min(s_g[0], cfg.total);
@@ -233,11 +233,11 @@ __device__ __forceinline__ void decide_block(const DevProblem& pb, const DevChai
         return;
     } else {
         const bool leaf = lp.leaf != 0;
-        MAGI_STAMP(par, 1);
+        MAGI_STAMP(decide, 1);
         if (!leaf && tid == 64) shs[16] = cfg.anneal ? temperature(0, cfg.min_temp) : 1.0;
         // ---- add the streaming kernel's partial sums, finish the parameter entries -----------------------
         const ReduceOut ro = leap_reduce<DRIFT>(pb, ch, chain, vb, par, s_par, lp, pre, sh, shs, s_ops, s_cst);
-        MAGI_STAMP(par, 4);
+        MAGI_STAMP(decide, 4);
         const double L = ro.L;
         double* qcur = vb + (size_t)(V_Q + lp.cur) * sv;      // the state that was evaluated
         double* pleaf = vb + (size_t)V_PLEAF * sv;
@@ -301,7 +301,7 @@ __device__ __forceinline__ void decide_block(const DevProblem& pb, const DevChai
                 shs[21 + (tid - 128)] = m_log1p(-rng_uniform(tid == 128 ? lp.leaf_ctr : lp.depth, lp.step_k, lp.chain_id, tid == 128 ? STREAM_LEAF : STREAM_MERGE, lp.seed));
             leap_next_par<DRIFT>(pb, par, sh, s_cst + MAGI_MAX_D);
             __syncthreads();
-            MAGI_STAMP(par, 5);
+            MAGI_STAMP(decide, 5);
             const double u_leaf = shs[21], u_merge = shs[22];
             const double wsum_leaf = shs[18];
             const bool accept_leaf = !hmc && (u_leaf <= ediff - wsum_leaf);
@@ -330,8 +330,8 @@ __device__ __forceinline__ void decide_block(const DevProblem& pb, const DevChai
                     plan_store(plan_out, pn);
                     ch.ctl[chain] = c;
                 }
-                MAGI_STAMP(par, 6);
-                MAGI_STAMP_FLUSH(par);
+                MAGI_STAMP(decide, 6);
+                MAGI_STAMPS_FLUSH(decide, threadIdx.x == 0, par, 11);
                 return;
             }
 

@@ -12,32 +12,9 @@
 #include "leap_reduce.h"
 #include "leap_point.h"
 #include "decide.h"
+#include "stamps.h"
 
 namespace {
-
-// dev (-DMAGI_WG_TRACE): begin / end (100 MHz real-time counter), hardware placement and a tag of EVERY workgroup of the last launch of
-// the streaming kernel [0] and of k_point [1] (tools/exp_wg_trace.py: where a launch's time goes across the grid)
-#ifdef MAGI_WG_TRACE
-__device__ unsigned long long g_wg_trace[2][4096][4];
-struct WgTrace {
-    int kern, wg;
-    __device__ __forceinline__ WgTrace(int kern_, int tag) : kern(kern_) {
-        wg = (int)(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z));
-        if (threadIdx.x == 0 && wg < 4096) {
-            g_wg_trace[kern][wg][0] = __builtin_amdgcn_s_memrealtime();
-            g_wg_trace[kern][wg][2] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) | (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-            g_wg_trace[kern][wg][3] = (unsigned long long)(long long)tag;
-        }
-    }
-    __device__ __forceinline__ ~WgTrace() {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // (the workgroup's stores have retired)
-        if ((threadIdx.x & 63) == 0 && wg < 4096) atomicMax(&g_wg_trace[kern][wg][1], (unsigned long long)__builtin_amdgcn_s_memrealtime());
-    }
-};
-#define WG_TRACE(kern, tag) WgTrace wg_trace_((kern), (tag))
-#else
-#define WG_TRACE(kern, tag) do { } while (0)
-#endif
 
 // Transposed butterfly: v[0..8) per lane -> every lane returns the 64-lane sum of v[lane >> 3].
 // Halving steps hand half of the values to the partner (v_permlane32/16_swap move both halves in one
@@ -84,19 +61,6 @@ constexpr int ST_RW = MAGI_TB / ST_WAVES;      // rows of the block per wave
 //   column-type products (A^T v_row)[c] -> per-lane accumulators, combined over the waves in LDS
 // where v is xc = X_d - mu_d or f_d = drift_d(X, theta) as the operator requires (evaluated on the fly from the
 // state vector).  The partials go to tpart[chain][vec][d][other block][i]; k_point adds them in fixed order.
-#ifdef MAGI_ST_STAMPS      // dev: 100 MHz time stamps of ONE stream workgroup (task MAGI_ST_STAMPS, wave MAGI_ST_STAMP_WAVE) into par[40 ..] of chain 0
-#ifndef MAGI_ST_STAMP_WAVE //      (tools/exp_st_stamps.py); kept in scalar registers and written once at the end -- a store per stamp spills the kernel (12 -> 27 us)
-#define MAGI_ST_STAMP_WAVE 1
-#endif
-#define ST_STAMP_DECL unsigned long long st_stamps[8] = {0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull, 0ull}
-#define ST_STAMP(i) do { st_stamps[(i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#define ST_STAMP_FLUSH() do { if ((int)blockIdx.x - n_dec == (MAGI_ST_STAMPS) && blockIdx.y == 0 && threadIdx.x == 64 * (MAGI_ST_STAMP_WAVE)) \
-    for (int _i = 0; _i < 8; ++_i) reinterpret_cast<unsigned long long*>(ch.par + 40)[_i] = st_stamps[_i]; } while (0)
-#else
-#define ST_STAMP_DECL do { } while (0)
-#define ST_STAMP(i) do { } while (0)
-#define ST_STAMP_FLUSH() do { } while (0)
-#endif
 template <int NC, int DRIFT>
 __global__ __launch_bounds__(64 * ST_WAVES) __attribute__((amdgpu_waves_per_eu(3)))
 void k_stream(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
@@ -125,8 +89,8 @@ void k_stream(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
     }
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
     const int tix = (int)blockIdx.x - n_dec;
-    ST_STAMP_DECL;
-    ST_STAMP(0);
+    MAGI_STAMPS_DECL(stream, 8);
+    MAGI_STAMP(stream, 0);
     // (the descriptor table is read-only for the lifetime of the matrices: fetched through the constant address space it is a
     //  scalar load on its own counter, so waiting for it does not wait for the tile loads issued below and vice versa)
     typedef const int __attribute__((address_space(4))) * const_int_ptr;
@@ -194,7 +158,7 @@ void k_stream(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
             thp = ch.par[(size_t)cc * PAR_COUNT + PAR_TH + lane];
         }
         if (lane < P) th_s[c][lane] = thp;
-        ST_STAMP(1);
+        MAGI_STAMP(stream, 1);
     }
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
@@ -208,13 +172,11 @@ void k_stream(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
     }
 
     if (all_done) return;
-#ifdef MAGI_TAIL_STAMPS
-    if (tix == 0 && threadIdx.x == 0) {
+    MAGI_STAMPS_ON(decide, if (tix == 0 && threadIdx.x == 0) {
         unsigned long long* st = reinterpret_cast<unsigned long long*>(ch.par + (size_t)c0 * PAR_COUNT + 40 + 11);
         st[1] = __builtin_amdgcn_s_memrealtime();      // [12] first stream workgroup's start
         st[0] = 0ull;                                    // [11] latest stream workgroup end (atomicMax below)
-    }
-#endif
+    })
     if (wave < NC) {                 // (the waves that derived theta' issue their first chunks now)
 #pragma unroll
         for (int r = 0; r < 8; ++r) a0[r] = A[(size_t)(pc0 * 8 + r) * (TB / 2)];
@@ -223,10 +185,10 @@ void k_stream(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
     }
     __builtin_amdgcn_sched_barrier(0);
     double thv[NC][P];
-    ST_STAMP(2);
+    MAGI_STAMP(stream, 2);
     if (kind != TK_FH) {
         __syncthreads();             // th_s
-        ST_STAMP(3);
+        MAGI_STAMP(stream, 3);
 #pragma unroll
         for (int c = 0; c < NC; ++c)
 #pragma unroll
@@ -248,7 +210,7 @@ void k_stream(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
         if (t < 2 * TB) (isrow ? vrow : vcol)[c][loc] = val;
     }
     __syncthreads();
-    ST_STAMP(4);
+    MAGI_STAMP(stream, 4);
 
     constexpr int NACC = ALT ? NCK : 1;            // column accumulators per physical chunk (direction-independent sums)
     double2 vc[NC], cacc[NC][NACC];
@@ -301,9 +263,9 @@ void k_stream(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
         }
         *reinterpret_cast<double2*>(&colacc[wave][c][2 * lane]) = tot;
     }
-    ST_STAMP(5);
+    MAGI_STAMP(stream, 5);
     __syncthreads();
-    ST_STAMP(6);
+    MAGI_STAMP(stream, 6);
 
     // partials: threads [0, TB) the row-type output (block row bi, slot bj), threads [TB, 2 TB) the
     // column-type output (block row bj, slot bi; the diagonal blocks of FH / FK are complete by rows)
@@ -324,13 +286,10 @@ void k_stream(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
             tp[((size_t)(cvec * D + d) * pb.nb + bi) * pb.Np + bj * TB + loc] = sum;
         }
     }
-    ST_STAMP(7);
-    ST_STAMP_FLUSH();
-#ifdef MAGI_TAIL_STAMPS
-    __syncthreads();
-    if (threadIdx.x == 0)
-        atomicMax(reinterpret_cast<unsigned long long*>(ch.par + (size_t)c0 * PAR_COUNT + 40 + 11), (unsigned long long)__builtin_amdgcn_s_memrealtime());
-#endif
+    MAGI_STAMP(stream, 7);
+    MAGI_STAMPS_FLUSH(stream, tix == MAGI_STAMP_WG && blockIdx.y == 0 && threadIdx.x == 64 * MAGI_STAMP_WAVE, ch.par, 8);
+    MAGI_STAMPS_ON(decide, __syncthreads(); if (threadIdx.x == 0)
+        atomicMax(reinterpret_cast<unsigned long long*>(ch.par + (size_t)c0 * PAR_COUNT + 40 + 11), (unsigned long long)__builtin_amdgcn_s_memrealtime());)
 }
 
 // ---- multi-chain streaming kernel on the matrix cores -----------------------------------------------------------------------
@@ -360,12 +319,6 @@ using mc_d4 = __attribute__((ext_vector_type(4))) double;
 #endif
 constexpr int MC_RING = MAGI_MC_RING;                    // steps of tile loads in flight per wave + 1 (ring of register buffers; 3: 22.7 us, 4: 23.2, 5: 23.6 at 8 chains)
 
-#ifdef MAGI_MC_STAMPS      // dev: 100 MHz time stamps of ONE stream workgroup (task MAGI_MC_STAMPS) into par[40 ..] of chain 0 (tools/exp_mc_stamps.py)
-#define MC_STAMP(i) do { if ((int)blockIdx.x - n_dec == (MAGI_MC_STAMPS) && blockIdx.y == 0 && threadIdx.x == 0) \
-    reinterpret_cast<unsigned long long*>(ch.par + 40)[(i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define MC_STAMP(i) do { } while (0)
-#endif
 template <int DRIFT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3)))
 void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
@@ -398,7 +351,6 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
     const int li = lane & 15, lj = lane >> 4;
     double* stage = smem + MC_SM_ST + wave * 16 * MC_PITCH;
     const int tix = (int)blockIdx.x - n_dec;
-    MC_STAMP(0);
     typedef const int __attribute__((address_space(4))) * const_int_ptr;
     const_int_ptr tk = (const_int_ptr)(unsigned long long)(pb.tasks + 4 * (size_t)tix);
     const int d = tk[0], kind = tk[1], bi = tk[2], bj = tk[3];
@@ -414,7 +366,6 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
     double2 tl[MC_RING][4];
     const bool coltype = (kind == TK_FE) || (bi != bj);      // (diagonal blocks of FH / FK are stored full: complete by rows)
     const bool colf = kind == TK_FK, rowf = kind != TK_FH;   // which operand slices are drift values (else xc = x - mu)
-    MC_STAMP(13);
 
     // Order of the prologue's loads.  Every workgroup of the grid starts at about the same time, and once the tile loads are out
     // (tens of MB across the device) anything issued behind them -- by anyone -- queues for microseconds; a wave's loads also
@@ -464,7 +415,6 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
             parv = ch.par[(size_t)cc * PAR_COUNT + PAR_TH + li];
         }
     }
-    MC_STAMP(14);
     // which of the 16 chain columns take part in this slot (bit c): every lane fetches its own chain's flag now, not at the stores
     const bool valid = li < ngrp;
     const unsigned long long actb = __ballot(valid && ch.plan[(size_t)(parity ^ 1) * nch + min(c0 + li, nch - 1)].active != 0);
@@ -514,7 +464,6 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
         }
     }
     __builtin_amdgcn_sched_barrier(0);
-    MC_STAMP(10);
     // ---- (3) theta' ----
     if (kind != TK_FH) {
         double tpp = 0.0;
@@ -528,7 +477,6 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
                 }
             }
         }
-        MC_STAMP(11);
         double thp = parv;
         if (lder && mine) {
             const double qv = lcur ? qv1 : qv0, pv = lcur ? pv1 : pv0;
@@ -540,9 +488,7 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
         if (mine) th_s[cg * 8 + li] = thp;
     }
     if (all_done) return;
-    MC_STAMP(1);
     __syncthreads();                 // th_s
-    MC_STAMP(2);
 
     // ---- (4) column slice -> LDS, [column pair][chain]; row slice W[32 wave + 16 cidx + 4 q + lj][chain li] -> registers ----
     const double mud = MAGI_SEL_D(pb.mu, d);
@@ -566,7 +512,6 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
     // ---- the tile ring: behind every operand load (the raw column slice has left its registers to it; one or two steps of it
     //      in front of the operand loads were measured: 23.2 / 26.2 us against 22.7 -- they delay every workgroup's operands) ----
     __builtin_amdgcn_sched_barrier(0);
-    MC_STAMP(12);
 #pragma unroll
     for (int s = 0; s < MC_RING - 1; ++s)
 #pragma unroll
@@ -582,9 +527,7 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
             if (valid && coltype) w0 = rowf ? DR::f1(d, xrow[cidx][q], thv) : xrow[cidx][q][0] - mud;
             wf[cidx][q] = (i < pb.N) ? w0 : 0.0;
         }
-    MC_STAMP(3);
     __syncthreads();                 // operand image complete
-    MC_STAMP(4);
 
     mc_d4 accc[2], accr[2];
     accr[0] = mc_d4{0.0, 0.0, 0.0, 0.0}; accr[1] = mc_d4{0.0, 0.0, 0.0, 0.0};
@@ -634,7 +577,6 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
             __syncthreads();
         }
         __builtin_amdgcn_sched_barrier(0);      // (keeps the next steps' fragment reads out of this one: they would not fit the register file)
-        if (s & 1) MC_STAMP(5 + (s >> 1));
     }
 
     // ---- partials.  Accumulator layout: register r of lane (li, lj) = chain lj + 4 r, free index li. ----
@@ -651,7 +593,7 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
             if (act)
                 ch.tpart[(size_t)(c0 + c) * cstride + ((size_t)(rvec * D + d) * pb.nb + bj) * pb.Np + bi * TB + 32 * wave + 16 * cidx + li] = accr[cidx][r];
     }
-    if (!coltype) { MC_STAMP(9); return; }
+    if (!coltype) return;
     // column-type: complete in LDS after the last phase's barrier; thread = (chain t >> 4, eight columns)
     {
         const int c = t >> 4, col = 8 * (t & 15);
@@ -663,7 +605,6 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
             for (int k = 0; k < 4; ++k) dst[k] = src[k];
         }
     }
-    MC_STAMP(9);
 }
 
 // ---- streaming kernel for SEPARABLE drifts: no parameter, no plan, no drift evaluation in front of the tile stream ------------------
@@ -704,13 +645,8 @@ void k_stream_sep(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
     using DR = DriftT<DRIFT>;
     using SL = SepLayout<DRIFT>;
     constexpr int D = DR::D, TB = MAGI_TB, PLANES = SL::planes(CW), PST = SL::PS_TOTAL;
-#ifdef MAGI_SEP_STAMPS      // dev: 100 MHz time stamps of ONE task's workgroup, kept in scalar registers, written at the end to par[40 ..] of chain 0 (tools/exp_sep_stamps.py)
-    unsigned long long sst[16] = {0ull};
-#define SEP_STAMP(i) do { sst[(i)] = __builtin_amdgcn_s_memrealtime(); } while (0)
-#else
-#define SEP_STAMP(i) do { } while (0)
-#endif
-    SEP_STAMP(0);
+    MAGI_STAMPS_DECL(sep, 16);
+    MAGI_STAMP(sep, 0);
     WG_TRACE(0, 0);
     const int all_done = ch.gctl->all_done;
     kernarg_prefetch<sizeof(DevProblem) + sizeof(DevChains) + sizeof(SamplerCfgDev) + sizeof(int)>();
@@ -739,19 +675,11 @@ void k_stream_sep(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
     const int li = lane & 15, lj = lane >> 4;
     double* stage = smem + MC_SM_ST + wave * 16 * MC_PITCH;
     const int tix = (int)blockIdx.x - n_dec;
-#ifdef MAGI_SEP_STAGGER      // dev A/B: half of the workgroups enter MAGI_SEP_STAGGER x 64 cycles late (mode 0: odd tasks, 1: the second half of the grid)
-#ifndef MAGI_SEP_STAGGER_MODE
-#define MAGI_SEP_STAGGER_MODE 0
-#endif
-    if (MAGI_SEP_STAGGER_MODE == 0 ? (tix & 1) != 0 : tix >= pb.n_stasks / 2) {
-        for (int k_ = 0; k_ < (MAGI_SEP_STAGGER); k_ += 100) __builtin_amdgcn_s_sleep(100);
-    }
-#endif
     typedef const int __attribute__((address_space(4))) * const_int_ptr;
     const_int_ptr tk = (const_int_ptr)(unsigned long long)(pb.stasks + 8 * (size_t)tix);
     const int d = tk[0], bi = tk[2], bj = tk[3];
     int kind = tk[1], tile0 = tk[4], tile1 = tk[5], kind1 = tk[6];
-    SEP_STAMP(1);              // task descriptor known
+    MAGI_STAMP(sep, 1);              // task descriptor known
     const int nch = ch.n_chains, ngrp = min(nch - c0, MC);
     // which products this (task, basis plane) has: the row-type product multiplies xc (FH, FE: plane 0 only) or the basis plane z (FK);
     // the column-type product xc (FH) or the basis plane z (FK, FE); diagonal blocks of FH / FK are complete by rows.  A pair task
@@ -786,7 +714,7 @@ void k_stream_sep(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
         return double2{v.x, v.y};
     };
     // (The ring goes out FIRST, right behind the task descriptor, then the operand slices.  Device time stamps of a workgroup
-    //  (-DMAGI_SEP_STAMPS, tools/exp_sep_stamps.py; 8 chains, kernel 19-20 us): task known 0.5 us after entry, the ~30 vector-memory
+    //  (-DMAGI_STAMPS=sep, tools/stamps.py sep; 8 chains, kernel 19-20 us): task known 0.5 us after entry, the ~30 vector-memory
     //  instructions of the prologue take 2.4 us to ISSUE on a CU whose other waves are streaming -- which is why a deeper ring makes
     //  the kernel slower (3 steps: 23.7 us, 4: 29.8) --, operands in LDS at 3.4 us, then 1.0-1.8 us per step (4 KB per wave and step:
     //  the CU's 8 waves draw ~26 GB/s, the device 6.7 TB/s: the steps run at the memory system's rate), stores out at 15 us.)
@@ -836,17 +764,17 @@ void k_stream_sep(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
         }
     }
     __builtin_amdgcn_sched_barrier(0);
-    SEP_STAMP(2);              // operand loads issued
+    MAGI_STAMP(sep, 2);              // operand loads issued
     if (all_done) return;
 
-    SEP_STAMP(3);              // ring issued
+    MAGI_STAMP(sep, 3);              // ring issued
     if (rowt) {
 #pragma unroll
         for (int k = 0; k < 4; ++k) reinterpret_cast<double2*>(smem + MC_SM_V)[((t >> 4) + 16 * k) * MC + li] = vv[k];
     }
-    SEP_STAMP(4);              // operands arrived, image written
+    MAGI_STAMP(sep, 4);              // operands arrived, image written
     __syncthreads();                 // operand image complete
-    SEP_STAMP(5);
+    MAGI_STAMP(sep, 5);
 
     unsigned long long actb = 0ull;          // bit c: chain c of the group takes part in this slot (set before the first store)
     // matrix-core column c of a product -> (basis function k, chain of the group)
@@ -911,9 +839,6 @@ void k_stream_sep(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
                 rv[q] = vimg[(16 * g + 4 * q + lj) * MC + li];
             }
         }
-#ifdef MAGI_SEP_PIPE
-        __builtin_amdgcn_sched_barrier(0);
-#endif
         if (colt) {
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
@@ -936,7 +861,7 @@ void k_stream_sep(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
         }
         }
         __builtin_amdgcn_sched_barrier(0);
-        if (s < 8) SEP_STAMP(6 + s);      // steps 0 .. 7 done: 6 .. 13
+        if (s < 8) MAGI_STAMP(sep, 6 + s);      // steps 0 .. 7 done: 6 .. 13
     });
 
     // ---- partials ----
@@ -954,13 +879,10 @@ void k_stream_sep(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
             for (int kk = 0; kk < 4; ++kk) dst[kk] = src[kk];
         }
     }
-#ifdef MAGI_SEP_STAMPS
-    SEP_STAMP(14);
-    __builtin_amdgcn_s_waitcnt(0);
-    SEP_STAMP(15);             // stores retired
-    if (tix == (MAGI_SEP_STAMPS) && blockIdx.y == 0 && z == 0 && threadIdx.x == 0)
-        for (int i_ = 0; i_ < 16; ++i_) reinterpret_cast<unsigned long long*>(ch.par + 40)[i_ < 12 ? i_ : i_] = sst[i_];
-#endif
+    MAGI_STAMP(sep, 14);
+    MAGI_STAMPS_ON(sep, __builtin_amdgcn_s_waitcnt(0);)
+    MAGI_STAMP(sep, 15);             // stores retired
+    MAGI_STAMPS_FLUSH(sep, tix == MAGI_STAMP_WG && blockIdx.y == 0 && z == 0 && threadIdx.x == 0, ch.par, 16);
 }
 
 // operand mirror (both slot parities) of the states in V_Q: API path and sampler start (the stream then finds its operands as it does

@@ -11,17 +11,7 @@
 // PART layout: [0] t12  [1 .. MAX_D] ss_d  [PK_TP ..] tp_p  [PK_PP] p.p  [PK_DOT + 2k, + 2k + 1] U-turn dots of check k
 #pragma once
 #include "magi_internal.h"
-
-#ifdef MAGI_TAIL_STAMPS
-// timing stamps (dev builds): staged in LDS, copied to par[40..55] only when a HOT leaf finishes, so a run that
-// ends on a slow path still reports the last hot leaf
-static __shared__ double g_stamps[16];
-#define MAGI_STAMP(par, i) do { if (threadIdx.x == 0) g_stamps[(i)] = (double)__builtin_amdgcn_s_memrealtime(); } while (0)
-#define MAGI_STAMP_FLUSH(par) do { if (threadIdx.x == 0) for (int _i = 0; _i < 11; ++_i) (par)[40 + _i] = g_stamps[_i]; } while (0)   /* 11, 12: written by the stream workgroups */
-#else
-#define MAGI_STAMP_FLUSH(par) do { } while (0)
-#define MAGI_STAMP(par, i) do { } while (0)
-#endif
+#include "stamps.h"
 
 constexpr int PK_T12 = 0, PK_SS = 1, PK_TP = 1 + MAGI_MAX_D, PK_PP = PK_TP + MAGI_MAX_P, PK_DOT = PK_PP + 1;
 static_assert(PK_DOT + 8 <= PART_K, "PART layout");
@@ -179,7 +169,7 @@ __device__ __forceinline__ ReduceOut leap_reduce(const DevProblem& pb, const Dev
         for (int k = 0; k < K0 + 8; ++k) red[k] = (k < K0 || dots) ? sh[k] : 0.0;
         __syncthreads();                     // sh is reused below (parking block) and by the caller
     }
-    MAGI_STAMP(par, 3);
+    MAGI_STAMP(decide, 3);
 
     // ---- parameter entries: gradient, momentum step, checkpoint, U-turn terms, speculative next state ----
     if (threadIdx.x < 64) {

@@ -21,17 +21,24 @@ _DRIFT_FREE = ("build.hip", "pack.hip")          # translation units without dri
 
 
 def _hipcc() -> str:
-    return os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    return _build.hipcc()
 
 
-def _source_digest() -> str:
+def _source_digest(extra=()) -> str:
     """Sources + extra flags: what a cached library depends on besides the drift header and the compiler."""
     h = hashlib.sha256()
-    for f in sorted(_build.sources() + glob.glob(os.path.join(_build.CSRC, "*.h")) + [os.path.join(_build.HERE, "..", "include", "magi_hip.h")]):
+    for f in sorted(_build.sources() + _build.headers()):
         with open(f, "rb") as fh:
             h.update(fh.read())
-    h.update(os.environ.get("MAGI_EXTRA_CFLAGS", "").encode())
+    h.update(" ".join(extra).encode())          # ("" without extra flags: the digest of every default build so far)
     return h.hexdigest()[:12]
+
+
+def drift_flags(drift, header_path, extra=()) -> list:
+    """The flags a build for `drift` adds to the recipe (build.compile_command): its header, wider lane groups / parameter blocks than
+    the base build's where it needs them, then the caller's `extra`."""
+    return ([f'-DMAGI_USER_DRIFT_HEADER="{header_path}"'] + (["-DMAGI_MAX_D=8"] if drift.D > 4 else [])
+            + (["-DMAGI_MAX_P=8"] if drift.P > 6 else []) + list(extra))
 
 
 def _compiler_version() -> str:
@@ -86,15 +93,16 @@ def prune(keep_latest: int = 1) -> None:
             shutil.rmtree(d, ignore_errors=True)
 
 
-def library_for(drift, verbose: bool = False) -> str:
-    """Path of the specialised library for ``drift`` (a user Drift), building it if needed.
+def library_for(drift, verbose: bool = False, extra=()) -> str:
+    """Path of the specialised library for ``drift`` (a user Drift), building it if needed; ``extra``: more hipcc flags (dev builds,
+    part of the cache key).
 
     Safe under concurrent callers (torchrun ranks, pytest-xdist workers constructing the same model): the check-build-publish
     sequence holds an exclusive ``flock`` on a per-key lock file, objects are compiled in a private temporary directory and the
     finished library is moved into place with one ``os.replace``."""
     if drift.header is None:
         raise ValueError("built-in drifts use the base library")
-    key = hashlib.sha256((drift.header + _source_digest()).encode()).hexdigest()[:16]       # (the compiler is NOT in the key: it is in the library's file name)
+    key = hashlib.sha256((drift.header + _source_digest(extra)).encode()).hexdigest()[:16]       # (the compiler is NOT in the key: it is in the library's file name)
     d = os.path.join(CACHE, f"{drift.name}_{key}")
     found = _find_cached_library(d)
     if found:
@@ -116,28 +124,17 @@ def library_for(drift, verbose: bool = False) -> str:
             os.replace(tmp_hdr, hdr)
             work = tempfile.mkdtemp(prefix="build_", dir=d)
             try:
-                hipcc = _hipcc()
                 wide = drift.D > 4 or drift.P > 6         # wider per-point lane groups / parameter blocks than the base build's
-                objs, jobs = [], []
-                for src in _build.sources():
-                    base = os.path.basename(src)
-                    shared = os.path.join(_build.HERE, "build", base + ".o")
-                    if base in _DRIFT_FREE and not wide and os.path.exists(shared) and not _build.needs_build():
-                        objs.append(shared)
-                        continue
-                    obj = os.path.join(work, base + ".o")
-                    objs.append(obj)
-                    contract = [] if base == "build.hip" else ["-ffp-contract=on"]
-                    cmd = [hipcc, "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-Wno-unused-function",
-                           f'-DMAGI_USER_DRIFT_HEADER="{hdr}"'] + ((["-DMAGI_MAX_D=8"] if drift.D > 4 else []) + (["-DMAGI_MAX_P=8"] if drift.P > 6 else [])) + \
-                        contract + os.environ.get("MAGI_EXTRA_CFLAGS", "").split()
-                    jobs.append((cmd, src, obj))
-                try:
-                    _build.compile_checked(jobs, verbose)          # (keeps each unit's ISA and runs the EXEC-prologue check on it, build.py)
+                reuse = {}
+                if not wide and not extra and not _build.needs_build():
+                    for src in _build.sources():
+                        if os.path.basename(src) in _DRIFT_FREE:
+                            reuse[src] = os.path.join(_build.OBJDIR, os.path.basename(src) + ".o")
+                tmp = os.path.join(work, "libmagi_hip_user.so")
+                try:                                      # (compile_checked keeps each unit's ISA and runs the EXEC-prologue check on it, build.py)
+                    _build.build_library(_build.sources(), work, tmp, extra=drift_flags(drift, hdr, extra), reuse=reuse, verbose=verbose)
                 except RuntimeError as e:
                     raise RuntimeError("build for the traced drift failed:\n" + str(e)) from None
-                tmp = os.path.join(work, "libmagi_hip_user.so")
-                subprocess.check_call([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", tmp] + objs + ["-Wl,-rpath,/opt/rocm/lib"])
                 os.replace(tmp, lib)                      # (the one publication: the name says which compiler built it)
             finally:
                 shutil.rmtree(work, ignore_errors=True)

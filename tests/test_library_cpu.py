@@ -73,12 +73,11 @@ def test_stream_kernels_spill_no_vector_register(tmp_path):
     decision path is where round 3's register-allocation heisenbug lived).  hipcc cross-compiles without a GPU."""
     import shutil
     import subprocess
-    hipcc = "/opt/rocm/bin/hipcc"
-    if not os.path.exists(hipcc) and shutil.which("hipcc") is None:
+    from magi_v2_amd import build
+    if shutil.which(build.hipcc()) is None:
         pytest.skip("no hipcc")
-    src = os.path.join(ROOT, "magi_v2_amd", "csrc", "leap.hip")
-    r = subprocess.run([hipcc if os.path.exists(hipcc) else "hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=on",
-                        "-Wno-unused-function", "-Rpass-analysis=kernel-resource-usage", "-c", src, "-o", str(tmp_path / "leap.o")],
+    src = os.path.join(build.CSRC, "leap.hip")
+    r = subprocess.run(build.compile_command(src, ["-Rpass-analysis=kernel-resource-usage"]) + ["-c", src, "-o", str(tmp_path / "leap.o")],
                        capture_output=True, text=True, cwd=str(tmp_path))
     assert r.returncode == 0, r.stderr[-2000:]
     blocks = re.split(r"remark: [^\n]*Function Name: ", r.stderr)[1:]
@@ -155,3 +154,38 @@ def test_exec_prologue_guard_flags_the_round3_miscompile_and_the_build_is_clean(
         assert isa_check.check_file(isa) == [], isa
         n += 1
     assert n >= 7
+
+
+def test_recipe_takes_no_flags_from_the_environment(monkeypatch):
+    """The product and the drift-specialised builds compile with the recipe's flags alone: MAGI_EXTRA_CFLAGS (once read by both) changes
+    neither their commands nor the JIT cache key; extra flags reach a build only as an argument."""
+    import types
+    from magi_v2_amd import build, jit
+    drift = types.SimpleNamespace(D=8, P=3)
+
+    def commands():
+        return ([build.compile_command(s) for s in build.sources()],
+                [build.compile_command(s, jit.drift_flags(drift, "/x/user_drift.h")) for s in build.sources()], jit._source_digest())
+
+    monkeypatch.delenv("MAGI_EXTRA_CFLAGS", raising=False)
+    plain = commands()
+    monkeypatch.setenv("MAGI_EXTRA_CFLAGS", "-DMAGI_STAMPS=decide -O0")
+    assert commands() == plain
+    assert all("-DMAGI_STAMPS=decide" not in c for cmds in plain[:2] for cmd in cmds for c in cmd)
+    assert ["-ffp-contract=on" in c for c in plain[0]] == [os.path.basename(s) != "build.hip" for s in build.sources()]
+    assert jit._source_digest(["-DX"]) != plain[2]
+
+
+def test_variant_build_never_targets_the_product(monkeypatch):
+    from magi_v2_amd import build
+    seen = []
+    monkeypatch.setattr(build, "build_library", lambda units, objdir, out, **kw: seen.append((objdir, out, kw)) or out)
+    out = build.build_variant("s_decide", ["-DMAGI_STAMPS=decide"])
+    objdir, out_, kw = seen[0]
+    assert out == out_ == os.path.join(build.VARIANTS, "s_decide", "libmagi_hip.so") and objdir == os.path.dirname(out)
+    assert os.path.abspath(out) != os.path.abspath(build.LIB) and os.path.abspath(objdir) != os.path.abspath(build.OBJDIR)
+    assert kw["extra"] == ["-DMAGI_STAMPS=decide"]
+    for bad in ("", ".", "..", "../magi_v2_amd", "a/b"):
+        with pytest.raises(ValueError):
+            build.build_variant(bad, [])
+    assert len(seen) == 1

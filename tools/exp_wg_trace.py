@@ -1,5 +1,5 @@
 """Dev: where a launch of the streaming kernel / k_point spends its time ACROSS the grid (needs a -DMAGI_WG_TRACE build:
-    python tools/build_variant.py wgtrace -DMAGI_WG_TRACE;  MAGI_HIP_LIB=build_variants/wgtrace.so python tools/exp_wg_trace.py [chains] [N]
+    python -m magi_v2_amd.build --variant wgtrace -DMAGI_WG_TRACE;  MAGI_HIP_LIB=build_variants/wgtrace/libmagi_hip.so python tools/exp_wg_trace.py [chains] [N]
 Every workgroup leaves begin / end (100 MHz counter), XCC / SE / CU ids; the script prints the launch's time line, the spread of
 workgroup lives by task kind, and the bytes each CU streamed."""
 import ctypes as C

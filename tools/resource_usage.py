@@ -3,8 +3,11 @@
 import re, subprocess, sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.chdir("/tmp")
-r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=on", "-Rpass-analysis=kernel-resource-usage",
-                    "-c", os.path.join(ROOT, "magi_v2_amd/csrc/leap.hip"), "-o", "/tmp/leap_ru.o", "--save-temps"], capture_output=True, text=True)
+sys.path.insert(0, ROOT)
+from magi_v2_amd import build
+src = os.path.join(build.CSRC, "leap.hip")
+r = subprocess.run(build.compile_command(src, ["-Rpass-analysis=kernel-resource-usage"]) + ["-c", src, "-o", "/tmp/leap_ru.o", "--save-temps"],
+                   capture_output=True, text=True)
 txt = r.stderr
 blocks = re.split(r"remark: [^\n]*Function Name: ", txt)[1:]
 print("# hipcc -O3 --offload-arch=gfx950 -ffp-contract=on -Rpass-analysis=kernel-resource-usage magi_v2_amd/csrc/leap.hip  (ROCm 7.2)")

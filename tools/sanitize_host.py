@@ -16,23 +16,15 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 OUT = os.path.join(ROOT, "build_variants", "san")
 LIB = os.path.join(OUT, "libmagi_hip_san.so")
-HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 SAN = ["-fsanitize=address,undefined", "-fno-gpu-sanitize", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
 
 
 def build():
     from magi_v2_amd import build as b
     b.build_lib(verbose=False)
-    os.makedirs(OUT, exist_ok=True)
     src = os.path.join(b.CSRC, "capi.hip")
-    obj = os.path.join(OUT, "capi.san.o")
-    deps = [src, os.path.join(b.CSRC, "magi_internal.h"), os.path.join(ROOT, "include", "magi_hip.h")]
-    if not os.path.exists(LIB) or any(os.path.getmtime(d) > os.path.getmtime(LIB) for d in deps):
-        subprocess.check_call([HIPCC, "-O1", "-g", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-ffp-contract=on", "-Wno-unused-function"] + SAN +
-                              ["-c", src, "-o", obj])
-        others = [os.path.join(b.HERE, "build", os.path.basename(s) + ".o") for s in b.sources() if not s.endswith("capi.hip")]
-        subprocess.check_call([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-shared-libsan"] + SAN + ["-o", LIB, obj] + others + ["-Wl,-rpath,/opt/rocm/lib"])
-    return LIB
+    reuse = {s: os.path.join(b.OBJDIR, os.path.basename(s) + ".o") for s in b.sources() if s != src}
+    return b.build_library(b.sources(), OUT, LIB, extra=["-O1", "-g"] + SAN, reuse=reuse, link_flags=["-shared-libsan"] + SAN, verbose=False)
 
 
 def asan_runtime():
