@@ -192,6 +192,26 @@ int magi_sampler_get_diag(magi_handle* h, double* step_size, double* log_accept_
                           int32_t* reach_max_depth, int32_t* is_accepted,
                           double* target_log_prob, double* energy, double* beta_temp);
 
+/* Problem groups: ONE sampler over the chains of n_members problems of the same shape on one GPU -- one captured graph, one
+ * [stream, point] kernel pair per leapfrog slot for all of them, one host thread (many small datasets: the GPU is mostly idle in one
+ * problem's slot at N = 161).  members: handles of this library on one device, each with its matrices built / set and packed and
+ * magi_set_problem done; they must agree in every shape (N, D, P, band, drift and what follows from them) and may differ in all their
+ * data (matrices, observations, mu, N_ds, LB, beta).  *out receives a handle flagged as a group; on failure *out is NULL, the return
+ * value is negative and magi_last_error(NULL) gives the message (mismatched shapes, a member without a problem, NULL members).
+ *   - magi_sampler_init on a group takes n_chains = n_members x C states and chain ids, problem-major (C per member, ids may repeat
+ *     across members), one cfg and one seed: the chains of member m then reproduce magi_sampler_init(member m, cfg, C, <its states>,
+ *     seed, <its ids>) bit for bit.  It reads the members' problems as they stand at that call (a member changed later takes effect at
+ *     the next magi_sampler_init), and rejects (MAGI_E_BADARG) n_chains that is not a multiple of n_members and a member whose own
+ *     rule (magi_stream_kernel_name, option stream_family) would stream C chains on a matrix-core kernel: a group runs the VALU kernels
+ *     k_stream_group<2> (C even) / k_stream_group<1> (C odd) only -- at N = 161, band 80 up to C = 16.
+ *   - magi_sampler_run, _steps_done, _get_samples, _get_diag, _get_state, _run_stats, _profile, magi_sample, magi_set_option and
+ *     magi_stream_kernel_name work on a group as on a handle, over all n_chains chains.
+ *   - the calls that need matrices of their own return MAGI_E_STATE: matrix builds, magi_set_matrices, magi_set_problem, magi_logpost_grad*,
+ *     the dense-stack calls, magi_fit_hparams, magi_theta_init, magi_time_gradient, magi_sampler_get_checkpoint / _set_checkpoint.
+ *   - the group owns its chain buffers, stream, graph and a device copy of the members' problems, not the members: they must outlive
+ *     it (magi_destroy(group) frees only what the group owns) and must not be re-built while it samples. */
+int magi_group_create(magi_handle* const* members, int n_members, magi_handle** out);
+
 /* Current state of every chain (checkpoint / hand-over to the CPU oracle in tests):
  * X[n_chains][N][D], sig_pre, th_pre, step_size[n_chains] (the dual-averaging "new step
  * size"), beta_cache[n_chains] (temperature at which the cached target was computed). */

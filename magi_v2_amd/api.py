@@ -22,7 +22,12 @@ import numpy as np
 
 from . import drift as _drift
 from . import host
-from .engine import DRIFT_SHAPES, MagiEngine
+from .engine import DRIFT_SHAPES, MagiEngine, MagiGroup
+
+
+def _fresh_seed() -> int:
+    """A 64-bit seed from the operating system's entropy (predict's seed when none is given)."""
+    return int(np.random.SeedSequence().generate_state(2, dtype=np.uint32).astype(np.uint64) @ np.array([1, 1 << 32], dtype=np.uint64))
 
 
 def logarithmic_temperature_schedule(step, min_temp: float = 0.1):
@@ -336,7 +341,29 @@ class MAGI_v2:
                 family_chains: Optional[int] = None):
         """magi_v2.py:286-425.  Returns the reference's results dictionary; with n_chains > 1 every
         sample array gains a leading chain axis.  ``family_chains``: in a job sharded over GPUs, the largest per-GPU share
-        (shard.family_chains_for) -- every rank then samples with the same kernel family whatever its own share."""
+        (shard.family_chains_for) -- every rank then samples with the same kernel family whatever its own share.
+        Many datasets on one GPU: ``predict_many``."""
+        sigma_sqs_LB, sig_pre0, th_pre0 = self._predict_prepare(sigma_sqs_LB, family_chains)
+        eng = self.engine
+        if seed is None:                 # the reference calls sample_chain unseeded (magi_v2.py:389-395)
+            seed = _fresh_seed()
+        cfg = eng.default_cfg(num_results=num_results, num_burnin_steps=num_burnin_steps, stale_cache=int(stale_cache),
+                              anneal=int(anneal), max_tree_depth=max_tree_depth, step_size=step_size)
+        rep = lambda a: np.repeat(np.asarray(a, dtype=np.float64)[None], n_chains, axis=0)
+        if verbose:
+            print("Starting NUTS posterior sampling ...")
+        start = time.time()
+        eng.sampler_init(cfg, rep(self.Xhat_init), rep(sig_pre0), rep(th_pre0), seed=seed, chain_ids=chain_ids)
+        eng.sampler_run(num_results + num_burnin_steps)
+        X_samps, sig_pre, th_pre = eng.sampler_samples()
+        end = time.time()
+        minutes = np.round((end - start) / 60, 2)
+        if verbose:
+            print(f"Finished sampling in {minutes} minutes.")
+        return self._predict_results(X_samps, sig_pre, th_pre, eng.sampler_diag(), sigma_sqs_LB, seed, n_chains, num_burnin_steps, minutes)
+
+    def _predict_prepare(self, sigma_sqs_LB, family_chains=None):
+        """predict's set-up up to the sampler: matrices on the device, the problem set; returns (sigma_sqs_LB, sig_pre0, th_pre0)."""
         assert ~np.any(np.isnan(self.Xhat_init)), "Please make sure Xhat_init does not have NaNs."
         assert ~np.any(np.isnan(self.sigma_sqs_init)), "Please make sure sigma_sqs_init does not have NaNs."
         assert ~np.any(np.isnan(self.thetas_init)), "Please make sure thetas_init does not have NaNs."
@@ -352,22 +379,10 @@ class MAGI_v2:
                         np.asarray(self.y_tau_ds_observed), float(self.beta), sigma_sqs_LB, self.drift)
         sig_pre0, th_pre0 = host.softplus_inverse_inits(np.asarray(self.sigma_sqs_init, dtype=np.float64),
                                                         np.asarray(self.thetas_init, dtype=np.float64), sigma_sqs_LB)
-        if seed is None:                 # the reference calls sample_chain unseeded (magi_v2.py:389-395)
-            seed = int(np.random.SeedSequence().generate_state(2, dtype=np.uint32).astype(np.uint64) @ np.array([1, 1 << 32], dtype=np.uint64))
-        cfg = eng.default_cfg(num_results=num_results, num_burnin_steps=num_burnin_steps, stale_cache=int(stale_cache),
-                              anneal=int(anneal), max_tree_depth=max_tree_depth, step_size=step_size)
-        rep = lambda a: np.repeat(np.asarray(a, dtype=np.float64)[None], n_chains, axis=0)
-        if verbose:
-            print("Starting NUTS posterior sampling ...")
-        start = time.time()
-        eng.sampler_init(cfg, rep(self.Xhat_init), rep(sig_pre0), rep(th_pre0), seed=seed, chain_ids=chain_ids)
-        eng.sampler_run(num_results + num_burnin_steps)
-        X_samps, sig_pre, th_pre = eng.sampler_samples()
-        end = time.time()
-        minutes = np.round((end - start) / 60, 2)
-        if verbose:
-            print(f"Finished sampling in {minutes} minutes.")
-        diag = eng.sampler_diag()
+        return sigma_sqs_LB, sig_pre0, th_pre0
+
+    def _predict_results(self, X_samps, sig_pre, th_pre, diag, sigma_sqs_LB, seed, n_chains, num_burnin_steps, minutes):
+        """predict's results dictionary from the chains' samples [n_chains, results, ...] and diagnostics."""
         sig_samps, th_samps = host.transform_samples(sig_pre, th_pre, sigma_sqs_LB)
         sq = (lambda a: a[0]) if n_chains == 1 else (lambda a: a)
         B = num_burnin_steps
@@ -407,3 +422,83 @@ class MAGI_v2:
 
     def cv_cubic_smoother(self, I, X_filled):
         return host.cubic_smoother(I, X_filled)
+
+
+# ------------------------------------------------------------------------------------------
+# many datasets on one GPU
+# ------------------------------------------------------------------------------------------
+def group_key(model, n_chains: int):
+    """What decides whether ``model`` (its problem set: MAGI_v2._predict_prepare) can share a problem group (include/magi_hip.h:
+    magi_group_create) with another: its engine's library and device and the problem's shape -- grid points, components, parameters,
+    drift, band.  None when it cannot join any group: its own rule would stream ``n_chains`` chains on a matrix-core kernel."""
+    eng = model.engine
+    if not eng.stream_kernel_name(n_chains).startswith("k_stream<"):
+        return None
+    return (id(eng._lib), eng.device, model.mag_I, model.D, model.D_thetas, getattr(model.drift, "name", str(model.drift)), model.BANDSIZE)
+
+
+def partition_for_groups(keys):
+    """Index lists, in the order of first appearance: the models of one key (not None) together, every other model alone.  A key met once
+    is alone too (a group of one gains nothing over the model's own predict)."""
+    by_key, order = {}, []
+    for k, key in enumerate(keys):
+        if key is None:
+            order.append([k])
+        elif key in by_key:
+            by_key[key].append(k)
+        else:
+            by_key[key] = [k]
+            order.append(by_key[key])
+    return [g for grp in order for g in ([grp] if len(grp) > 1 else [[i] for i in grp])]
+
+
+def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_steps: int = 1000, sigma_sqs_LB=None, verbose=False, *,
+                 n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[Sequence[int]]] = None,
+                 stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1):
+    """``predict`` for several models (after their ``initial_fit``) at once.  Models of one library, device and problem shape are sampled
+    as one problem group on their GPU -- one captured graph, one kernel pair per leapfrog slot for all their chains -- and the others by
+    their own ``predict``.  ``sigma_sqs_LB``: None (each model's default) or one entry per model; ``chain_ids``: None (0 .. n_chains - 1
+    for every model, as predict) or one id list per model.  Returns one results dictionary per model, in order: element k equals
+    ``models[k].predict(<same arguments>, seed=<the seed used>)`` array for array, bit for bit; ``minutes_elapsed`` is the group's."""
+    models = list(models)
+    n = len(models)
+    lbs = [None] * n if sigma_sqs_LB is None else list(sigma_sqs_LB)
+    ids = [None] * n if chain_ids is None else [None if c is None else list(c) for c in chain_ids]
+    if len(lbs) != n or len(ids) != n:
+        raise ValueError("sigma_sqs_LB and chain_ids take one entry per model")
+    if seed is None:
+        seed = _fresh_seed()
+    kw = dict(n_chains=n_chains, seed=seed, stale_cache=stale_cache, anneal=anneal, max_tree_depth=max_tree_depth, step_size=step_size)
+    prep = [m._predict_prepare(lb) for m, lb in zip(models, lbs)]
+    out = [None] * n
+    for grp in partition_for_groups([group_key(m, n_chains) for m in models]):
+        if len(grp) == 1:
+            k = grp[0]
+            out[k] = models[k].predict(num_results, num_burnin_steps, lbs[k], verbose, chain_ids=ids[k], **kw)
+            continue
+        g = MagiGroup([models[k].engine for k in grp])
+        try:
+            cfg = g.default_cfg(num_results=num_results, num_burnin_steps=num_burnin_steps, stale_cache=int(stale_cache),
+                                anneal=int(anneal), max_tree_depth=max_tree_depth, step_size=step_size)
+            rep = lambda a: np.repeat(np.asarray(a, dtype=np.float64)[None], n_chains, axis=0)
+            X0 = np.concatenate([rep(models[k].Xhat_init) for k in grp])
+            s0 = np.concatenate([rep(prep[k][1]) for k in grp])
+            t0 = np.concatenate([rep(prep[k][2]) for k in grp])
+            gids = np.concatenate([np.arange(n_chains) if ids[k] is None else np.asarray(ids[k]) for k in grp]).astype(np.int64)
+            if verbose:
+                print(f"Starting NUTS posterior sampling of {len(grp)} models as one group ...")
+            start = time.time()
+            g.sampler_init(cfg, X0, s0, t0, seed=seed, chain_ids=gids)
+            g.sampler_run(num_results + num_burnin_steps)
+            X_samps, sig_pre, th_pre = g.sampler_samples()
+            minutes = np.round((time.time() - start) / 60, 2)
+            if verbose:
+                print(f"Finished sampling in {minutes} minutes.")
+            diag = g.sampler_diag()
+        finally:
+            g.close()
+        for j, k in enumerate(grp):
+            sl = slice(j * n_chains, (j + 1) * n_chains)
+            dk = type(diag)(*[getattr(diag, f)[sl] for f in diag.__dataclass_fields__])
+            out[k] = models[k]._predict_results(X_samps[sl], sig_pre[sl], th_pre[sl], dk, prep[k][0], seed, n_chains, num_burnin_steps, minutes)
+    return out

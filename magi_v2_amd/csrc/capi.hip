@@ -145,6 +145,49 @@ bool set_option(MagiOptions& o, const OptRow& r, int64_t v) {
     return true;
 }
 
+// calls that need matrices of their own (magi_hip.h: magi_group_create)
+int refuse_group(magi_handle* h, const char* what) {
+    return magi_fail(h, MAGI_E_STATE, std::string(what) + " needs a handle with matrices of its own: this handle is a problem group (magi_group_create)");
+}
+
+// "" when handle m can join a group whose shape is `ref`, else why not
+std::string member_mismatch(const DevProblem& ref, const magi_handle* m) {
+    if (!m->have_matrices || !m->have_problem) return "has no problem set (magi_set_matrices / magi_build_matrices, then magi_set_problem)";
+    // (what the caller chose first, then what follows from it)
+    const DevProblem& p = m->pb;
+    const struct { const char* name; int a, b; } f[] = {
+        {"N", p.N, ref.N}, {"D", p.D, ref.D}, {"P", p.P, ref.P}, {"drift", p.drift, ref.drift}, {"band", p.band, ref.band}, {"ld", p.ld, ref.ld},
+        {"n_tasks", p.n_tasks, ref.n_tasks}, {"nb", p.nb, ref.nb}, {"Np", p.Np, ref.Np}, {"wb", p.wb, ref.wb}, {"bandf", p.bandf, ref.bandf},
+        {"dim", p.dim, ref.dim}, {"dimp", p.dimp, ref.dimp}};
+    for (const auto& x : f)
+        if (x.a != x.b) return std::string("differs in shape: ") + x.name + " = " + std::to_string(x.a) + ", the first member's is " + std::to_string(x.b);
+    return "";
+}
+
+// The members as they stand now, for n_chains = G x per: each has a problem of the group's shape and its own rule puts `per` chains on a
+// VALU streaming kernel; their problems go to the device table the group kernels read.
+int group_refresh(magi_handle* h, int n_chains) {
+    const int G = h->group_n;
+    if (n_chains <= 0 || n_chains % G != 0)
+        return magi_fail(h, MAGI_E_BADARG, "n_chains = " + std::to_string(n_chains) + " is not a positive multiple of the group's " + std::to_string(G) + " members");
+    const int per = n_chains / G;
+    std::vector<DevProblem> tab(G);
+    for (int m = 0; m < G; ++m) {
+        const magi_handle* s = h->members[m];
+        const std::string why = member_mismatch(h->pb, s);
+        if (!why.empty()) return magi_fail(h, MAGI_E_BADARG, "group member " + std::to_string(m) + " " + why);
+        const StreamKernel k = magi_stream_kernel(s, per);
+        if (k != StreamKernel::Valu1 && k != StreamKernel::Valu2)
+            return magi_fail(h, MAGI_E_BADARG, "group member " + std::to_string(m) + " would stream " + std::to_string(per) +
+                                               " chains on a matrix-core kernel (its problem size or its option stream_family): a group runs the VALU kernels only");
+        tab[m] = s->pb;
+        if (s->stream) MAGI_HIP_CHECK(h, hipStreamSynchronize(s->stream));       // (the member's matrices are complete)
+    }
+    MAGI_HIP_CHECK(h, hipMemcpy(h->d_members, tab.data(), sizeof(DevProblem) * G, hipMemcpyHostToDevice));
+    h->group_per = per;
+    return MAGI_OK;
+}
+
 }  // namespace
 
 void magi_options_from_env(MagiOptions& o) {
@@ -168,7 +211,7 @@ double* magi_workspace(magi_handle* h, int k, size_t n) {
 }
 
 int magi_ensure_chains(magi_handle* h, int n) {
-    if (!h->have_matrices || !h->have_problem) return magi_fail(h, MAGI_E_STATE, "set matrices and problem first");
+    if (!h->group_n && (!h->have_matrices || !h->have_problem)) return magi_fail(h, MAGI_E_STATE, "set matrices and problem first");
     if (n <= 0 || n > 4096) return magi_fail(h, MAGI_E_BADARG, "n_chains out of range");
     if (n > h->cap_chains) {
         free_chains(h);
@@ -268,6 +311,7 @@ void magi_destroy(magi_handle* h) {
     drop_graph(h);
     free_chains(h);
     free_matrices(h);
+    free_dev(h->d_members);          // (a group's members are the caller's)
     for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     if (h->ev_t0) (void)hipEventDestroy(h->ev_t0);
     if (h->ev_t1) (void)hipEventDestroy(h->ev_t1);
@@ -281,9 +325,39 @@ void magi_destroy(magi_handle* h) {
     delete h;
 }
 
+int magi_group_create(magi_handle* const* members, int n_members, magi_handle** out) {
+    if (out) *out = nullptr;
+    if (!members || !out || n_members < 1 || n_members > 4096) return magi_fail(nullptr, MAGI_E_BADARG, "magi_group_create: need 1 to 4096 members and an out pointer");
+    for (int m = 0; m < n_members; ++m) {
+        const magi_handle* s = members[m];
+        if (!s) return magi_fail(nullptr, MAGI_E_BADARG, "group member " + std::to_string(m) + " is NULL");
+        if (s->group_n) return magi_fail(nullptr, MAGI_E_BADARG, "group member " + std::to_string(m) + " is itself a group");
+        if (s->device != members[0]->device)
+            return magi_fail(nullptr, MAGI_E_BADARG, "group member " + std::to_string(m) + " is on device " + std::to_string(s->device) + ", the first member on " +
+                                                     std::to_string(members[0]->device));
+        const std::string why = member_mismatch(members[0]->pb, s);
+        if (!why.empty()) return magi_fail(nullptr, MAGI_E_BADARG, "group member " + std::to_string(m) + " " + why);
+    }
+    magi_handle* g = magi_create(members[0]->device);
+    if (!g) return MAGI_E_HIP;                    // (magi_create has set the message)
+    g->group_n = n_members;
+    g->members.assign(members, members + n_members);
+    g->pb = members[0]->pb;                        // the shape; the data of every member is read from the device table
+    g->pb.Csym = g->pb.M = g->pb.Mt = g->pb.Ksym = g->pb.yobs = g->pb.tiles = nullptr;
+    g->pb.tasks = g->pb.stasks = nullptr;
+    hipError_t e = hipMalloc(&g->d_members, sizeof(DevProblem) * n_members);
+    if (e != hipSuccess) {
+        magi_destroy(g);
+        return magi_fail(nullptr, MAGI_E_HIP, std::string("group table: ") + hipGetErrorString(e));
+    }
+    *out = g;
+    return MAGI_OK;
+}
+
 int magi_set_matrices(magi_handle* h, int N, int D, int bandsize, const double* C_inv, const double* m,
                       const double* K_inv) {
     if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_set_matrices");
     if (!C_inv || !m || !K_inv) return magi_fail(h, MAGI_E_BADARG, "null matrix pointer");
     if (N < 2 || D < 1 || D > MAGI_MAX_D) return magi_fail(h, MAGI_E_BADARG, "need N >= 2 and 1 <= D <= " + std::to_string(MAGI_MAX_D));
     (void)hipSetDevice(h->device);
@@ -302,6 +376,7 @@ int magi_set_matrices(magi_handle* h, int N, int D, int bandsize, const double* 
 
 int magi_build_dense(magi_handle* h, const double* I, int N, int D, int n_sel, const int32_t* sel, const double* phi1, const double* phi2, double nu) {
     if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_build_dense");
     if (!I || !sel || !phi1 || !phi2) return magi_fail(h, MAGI_E_BADARG, "null pointer");
     if (N < 2 || D < 1 || D > MAGI_MAX_D || n_sel < 1 || n_sel > D) return magi_fail(h, MAGI_E_BADARG, "need N >= 2, 1 <= D <= " + std::to_string(MAGI_MAX_D) + " and 1 <= n_sel <= D");
     if (!(nu > 1.0)) return magi_fail(h, MAGI_E_BADARG, "nu must exceed 1 (once-differentiable Matern)");
@@ -314,6 +389,7 @@ int magi_build_dense(magi_handle* h, const double* I, int N, int D, int n_sel, c
 
 int magi_pack_resident(magi_handle* h, int bandsize) {
     if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_pack_resident");
     if (!h->dDense[0] || h->dense_N <= 0) return magi_fail(h, MAGI_E_STATE, "no resident matrices: build or set them first");
     (void)hipSetDevice(h->device);
     int rc = magi_pack_matrices(h, h->dense_N, h->dense_D, bandsize, h->dDense[0], h->dDense[1], h->dDense[2]);
@@ -323,6 +399,7 @@ int magi_pack_resident(magi_handle* h, int bandsize) {
 
 int magi_get_dense(magi_handle* h, int bandsize, double* C_inv, double* m, double* K_inv) {
     if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_get_dense");
     if (!h->dDense[0] || h->dense_N <= 0) return magi_fail(h, MAGI_E_STATE, "no resident matrices");
     (void)hipSetDevice(h->device);
     const int N = h->dense_N, D = h->dense_D;
@@ -344,6 +421,7 @@ int magi_get_dense(magi_handle* h, int bandsize, double* C_inv, double* m, doubl
 
 int magi_dense_apply(magi_handle* h, int which, int transpose, int nv, const double* V, double* Y) {
     if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_dense_apply");
     if (!h->dDense[0] || h->dense_N <= 0) return magi_fail(h, MAGI_E_STATE, "no resident matrices");
     if (which < 0 || which > 2 || nv < 1 || nv > 8 || !V || !Y) return magi_fail(h, MAGI_E_BADARG, "which in 0..2, 1 <= nv <= 8, non-null vectors");
     (void)hipSetDevice(h->device);
@@ -372,6 +450,7 @@ int magi_dense_apply(magi_handle* h, int which, int transpose, int nv, const dou
 int magi_theta_init(magi_handle* h, int drift_id, int P, const double* Xhat, const double* mu, int num_iters, double learning_rate,
                     double* theta, double* loss_trace) {
     if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_theta_init");
     if (!Xhat || !mu || !theta) return magi_fail(h, MAGI_E_BADARG, "null pointer");
     if (!h->dDense[0] || h->dense_N <= 0) return magi_fail(h, MAGI_E_STATE, "no resident matrices: build or set them first");
     if (num_iters < 0 || !(learning_rate > 0.0)) return magi_fail(h, MAGI_E_BADARG, "num_iters >= 0 and learning_rate > 0");
@@ -389,6 +468,7 @@ int magi_theta_init(magi_handle* h, int drift_id, int P, const double* Xhat, con
 int magi_build_matrices(magi_handle* h, const double* I, int N, int D, const double* phi1, const double* phi2,
                         double nu, int bandsize, double* C_inv, double* m, double* K_inv) {
     if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_build_matrices");
     if (!I || !phi1 || !phi2) return magi_fail(h, MAGI_E_BADARG, "null pointer");
     if (N < 2 || D < 1 || D > MAGI_MAX_D) return magi_fail(h, MAGI_E_BADARG, "need N >= 2 and 1 <= D <= " + std::to_string(MAGI_MAX_D));
     if (!(nu > 1.0)) return magi_fail(h, MAGI_E_BADARG, "nu must exceed 1 (once-differentiable Matern)");
@@ -399,6 +479,7 @@ int magi_build_matrices(magi_handle* h, const double* I, int N, int D, const dou
 int magi_matern_blocks(magi_handle* h, const double* I, int N, double phi1, double phi2, double nu, double* Kappa,
                        double* p_Kappa, double* Kappa_pp) {
     if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_matern_blocks");
     if (!I || N < 2) return magi_fail(h, MAGI_E_BADARG, "bad grid");
     (void)hipSetDevice(h->device);
     return magi_matern_blocks_device(h, I, N, phi1, phi2, nu, Kappa, p_Kappa, Kappa_pp);
@@ -407,6 +488,7 @@ int magi_matern_blocks(magi_handle* h, const double* I, int N, double phi1, doub
 int magi_set_problem(magi_handle* h, const double* mu, const double* N_ds, const int64_t* obs_idx, const double* y,
                      int64_t n_obs, double beta, const double* LB, int drift_id, int P) {
     if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_set_problem");
     if (!h->have_matrices) return magi_fail(h, MAGI_E_STATE, "matrices must be set before the problem");
     if (!mu || !N_ds || !LB || (n_obs > 0 && (!obs_idx || !y))) return magi_fail(h, MAGI_E_BADARG, "null pointer");
     DevProblem& pb = h->pb;
@@ -459,6 +541,7 @@ int magi_set_problem(magi_handle* h, const double* mu, const double* N_ds, const
 static int logpost_grad_impl(magi_handle* h, bool fused, int n_chains, const double* X, const double* sig_pre, const double* th_pre,
                              double beta_temp, double* logp, double* gX, double* gsig, double* gth, double* terms) {
     if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_logpost_grad");
     if (!X || !sig_pre || !th_pre) return magi_fail(h, MAGI_E_BADARG, "null state pointer");
     (void)hipSetDevice(h->device);
     int rc = magi_ensure_chains(h, n_chains);
@@ -533,8 +616,9 @@ int magi_sampler_init(magi_handle* h, const magi_sampler_cfg* cfg, int n_chains,
     if (cfg->mode == MAGI_MODE_HMC && cfg->hmc_leapfrogs < 1) return magi_fail(h, MAGI_E_BADARG, "hmc_leapfrogs must be >= 1");
     if (!(cfg->step_size > 0.0)) return magi_fail(h, MAGI_E_BADARG, "step_size must be positive");
     (void)hipSetDevice(h->device);
-    int rc = magi_ensure_chains(h, n_chains);
-    if (rc) return rc;
+    int rc;
+    if (h->group_n && (rc = group_refresh(h, n_chains))) return rc;
+    if ((rc = magi_ensure_chains(h, n_chains))) return rc;
     const DevProblem& pb = h->pb;
     SamplerCfgDev& c = h->cfg;
     c.total = cfg->num_results + cfg->num_burnin_steps;
@@ -842,6 +926,7 @@ static double ckpt_tag(const magi_handle* h, long long chain_id) {
 
 int magi_sampler_get_checkpoint(magi_handle* h, double* scalars) {
     if (!h || !scalars) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_sampler_get_checkpoint");
     if (!h->sampler_ready) return magi_fail(h, MAGI_E_STATE, "sampler not initialised");
     (void)hipSetDevice(h->device);
     std::vector<ChainCtl> ctl(h->n_chains);
@@ -860,6 +945,7 @@ int magi_sampler_get_checkpoint(magi_handle* h, double* scalars) {
 
 int magi_sampler_set_checkpoint(magi_handle* h, const double* scalars) {
     if (!h || !scalars) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_sampler_set_checkpoint");
     if (!h->sampler_ready) return magi_fail(h, MAGI_E_STATE, "call magi_sampler_init with the checkpointed states first");
     (void)hipSetDevice(h->device);
     static_assert(CKPT_COUNT <= MAGI_CKPT_SCALARS, "checkpoint layout");
@@ -899,6 +985,7 @@ int magi_fit_hparams(magi_handle* h, const double* I, int N, int D, const double
                      const double* sd_phi2, const double* sigma_sq_loc, double nu, int num_iters, double learning_rate, double jitter,
                      double* phi1, double* phi2, double* sigma_sq, double* loss_trace) {
     if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_fit_hparams");
     if (!I || !X_filled || !mu || !mu_phi2 || !sd_phi2 || !sigma_sq_loc || !phi1 || !phi2 || !sigma_sq)
         return magi_fail(h, MAGI_E_BADARG, "null pointer");
     if (N < 2 || D < 1 || num_iters < 0 || !(nu > 1.0)) return magi_fail(h, MAGI_E_BADARG, "bad N, D, num_iters or nu");
@@ -965,6 +1052,11 @@ int magi_gradient_bytes(magi_handle* h, int n_chains, double* phase_bytes) {
 
 int magi_stream_kernel_name(magi_handle* h, int n_chains, char* buf, int cap) {
     if (!h || !buf || cap < 2) return MAGI_E_BADARG;
+    if (h->group_n) {                  // (the group twins of k_stream<1> / k_stream<2>)
+        if (n_chains <= 0 || n_chains % h->group_n) return magi_fail(h, MAGI_E_BADARG, "n_chains is not a positive multiple of the group's members");
+        std::snprintf(buf, (size_t)cap, "%s", magi_stream_kernel(h, n_chains) == StreamKernel::Valu2 ? "k_stream_group<2>" : "k_stream_group<1>");
+        return MAGI_OK;
+    }
     if (!h->have_matrices || !h->have_problem) return magi_fail(h, MAGI_E_STATE, "set matrices and problem first");
     static const char* const names[] = {"k_stream<1>", "k_stream<2>", "k_stream_mc", "k_stream_sep<CW=8>", "k_stream_sep<CW=16>"};   // (StreamKernel order)
     std::snprintf(buf, (size_t)cap, "%s", names[(int)magi_stream_kernel(h, n_chains)]);
@@ -973,6 +1065,7 @@ int magi_stream_kernel_name(magi_handle* h, int n_chains, char* buf, int cap) {
 
 int magi_time_gradient(magi_handle* h, int n_chains, int reps, double* total_ms_per_eval, double* phase_ms) {
     if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_time_gradient");
     if (reps <= 0) return magi_fail(h, MAGI_E_BADARG, "reps must be positive");
     (void)hipSetDevice(h->device);
     int rc = magi_ensure_chains(h, n_chains);

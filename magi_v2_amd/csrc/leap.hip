@@ -16,43 +16,7 @@
 
 namespace {
 
-// Transposed butterfly: v[0..8) per lane -> every lane returns the 64-lane sum of v[lane >> 3].
-// Halving steps hand half of the values to the partner (v_permlane32/16_swap move both halves in one
-// instruction pair), so 8 row sums cost 7 exchanges + 3 plain steps instead of 8 x 6.
-__device__ __forceinline__ double swap_add32(double a, double b) {
-    unsigned alo = (unsigned)__double2loint(a), ahi = (unsigned)__double2hiint(a);
-    unsigned blo = (unsigned)__double2loint(b), bhi = (unsigned)__double2hiint(b);
-    auto lo = __builtin_amdgcn_permlane32_swap(alo, blo, false, false);
-    auto hi = __builtin_amdgcn_permlane32_swap(ahi, bhi, false, false);
-    return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
-}
-__device__ __forceinline__ double swap_add16(double a, double b) {
-    unsigned alo = (unsigned)__double2loint(a), ahi = (unsigned)__double2hiint(a);
-    unsigned blo = (unsigned)__double2loint(b), bhi = (unsigned)__double2hiint(b);
-    auto lo = __builtin_amdgcn_permlane16_swap(alo, blo, false, false);
-    auto hi = __builtin_amdgcn_permlane16_swap(ahi, bhi, false, false);
-    return __hiloint2double((int)hi[0], (int)lo[0]) + __hiloint2double((int)hi[1], (int)lo[1]);
-}
-__device__ __forceinline__ double tsum8(const double (&v)[8], int lane) {
-    // lanes 32..63 keep rows 4..7, lanes 0..31 rows 0..3
-    const double s0 = swap_add32(v[0], v[4]), s1 = swap_add32(v[1], v[5]), s2 = swap_add32(v[2], v[6]), s3 = swap_add32(v[3], v[7]);
-    // odd rows of 16 lanes keep the upper two of those
-    const double u0 = swap_add16(s0, s2), u1 = swap_add16(s1, s3);
-    // lanes with bit 3 set keep u1 (partner: row_mirror, which flips bit 3)
-    const bool hi8 = (lane & 8) != 0;
-    const double keep = hi8 ? u1 : u0, send = hi8 ? u0 : u1;
-    double w = keep + dpp_f64<0x140>(send);
-    w += dpp_f64<0x141>(w);   // row_half_mirror (stays inside the 8-lane group)
-    w += dpp_f64<0x4E>(w);
-    w += dpp_f64<0xB1>(w);
-    return w;
-}
-
-#ifndef MAGI_ST_WAVES
-#define MAGI_ST_WAVES 4
-#endif
-constexpr int ST_WAVES = MAGI_ST_WAVES;        // waves per block task
-constexpr int ST_RW = MAGI_TB / ST_WAVES;      // rows of the block per wave
+#include "leap_stream.h"
 
 // ---- streaming kernel: one TB x TB block of FH / FK / FE per workgroup ----------------------------------
 // grid (n_tasks + 1, ceil(n_chains / NC)), block 64 * ST_WAVES.  Wave w streams rows [w*RW, (w+1)*RW) of the block with
@@ -64,232 +28,8 @@ constexpr int ST_RW = MAGI_TB / ST_WAVES;      // rows of the block per wave
 template <int NC, int DRIFT>
 __global__ __launch_bounds__(64 * ST_WAVES) __attribute__((amdgpu_waves_per_eu(3)))
 void k_stream(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
-    using DR = DriftT<DRIFT>;
-    constexpr int D = DR::D, P = DR::P, TB = MAGI_TB;
-    WG_TRACE(0, 0);
-    // (the "all chains idle" flag is fetched here but tested after the other first loads are on the wire: an early return on it
-    //  would put one more dependent round trip in front of every workgroup of every slot)
-    const int all_done = ch.gctl->all_done;
-    kernarg_prefetch<sizeof(DevProblem) + sizeof(DevChains) + sizeof(SamplerCfgDev) + sizeof(int)>();
-    const int c0 = blockIdx.y * NC;
-    __shared__ double vcol[NC][TB], vrow[NC][TB], rowout[NC][TB], colacc[ST_WAVES][NC][TB];
-    __shared__ double th_s[NC][MAGI_MAX_P];
-    const int n_dec = (int)gridDim.x - pb.n_tasks;        // decision workgroups come FIRST in dispatch order: their one round of
-    if ((int)blockIdx.x < n_dec) {                         // loads is then on the wire before the stream saturates the memory system
-        // ---- the decisions of the previous slot, one workgroup per chain, next to this slot's stream (decide.h) ----
-        __shared__ double dsh[25 * 16], dshs[24];
-        __shared__ ChainCtl s_ctl;
-        __shared__ int s_g[2];
-        __shared__ double s_par[PAR_COUNT];
-        __shared__ double s_ops[OPS_COUNT * OPS_W];
-        __shared__ double s_cst[3 * MAGI_MAX_D];
-        const int chain = c0 + (int)blockIdx.x;
-        if (chain < ch.n_chains) decide_block<DRIFT>(pb, ch, cfg, chain, parity, all_done, dsh, dshs, &s_ctl, s_g, s_par, s_ops, s_cst);
-        return;
-    }
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int tix = (int)blockIdx.x - n_dec;
-    MAGI_STAMPS_DECL(stream, 8);
-    MAGI_STAMP(stream, 0);
-    // (the descriptor table is read-only for the lifetime of the matrices: fetched through the constant address space it is a
-    //  scalar load on its own counter, so waiting for it does not wait for the tile loads issued below and vice versa)
-    typedef const int __attribute__((address_space(4))) * const_int_ptr;
-    const_int_ptr tk = (const_int_ptr)(unsigned long long)(pb.tasks + 4 * (size_t)tix);
-    int4 task;
-    task.x = tk[0]; task.y = tk[1]; task.z = tk[2]; task.w = tk[3];
-    // the wave's rows in chunks of 8, two chunks in flight (a0 / a1): 16 KB per wave on the wire while one chunk is in the ALUs.
-    // tile loads need nothing but the block index: on the wire before the plan-dependent loads (except in the waves that derive theta')
-    const double2* A = reinterpret_cast<const double2*>(pb.tiles + (size_t)tix * TB * TB + (size_t)((threadIdx.x >> 6) * ST_RW) * TB) + (threadIdx.x & 63);
-    constexpr int NCK = ST_RW / 8;
-    // Odd slots walk the wave's row chunks backwards: what a slot read LAST is what the next one reads FIRST, so the tail of the
-    // block stream is still in the XCD's L2 (4 MB against 9 MB of blocks per XCD; tools/micro/readshape.hip: 5-15 % on the
-    // load-only twin).  Chunk ck of the walk is physical chunk pc(ck); results are summed per PHYSICAL chunk so that they do
-    // not depend on the direction.  (Only the one- and two-chain instantiations: four chains have no registers for it.)
-    static_assert(NC <= 2, "three or more chains per pass run k_stream_mc");
-    constexpr bool ALT = true;
-    const int pc0 = (ALT && (parity & 1)) ? NCK - 1 : 0, pcs = (ALT && (parity & 1)) ? -1 : 1;
-    double2 a0[8], a1[8];
-    if ((threadIdx.x >> 6) >= NC) {
-#pragma unroll
-        for (int r = 0; r < 8; ++r) a0[r] = A[(size_t)(pc0 * 8 + r) * (TB / 2)];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) a1[r] = A[(size_t)((pc0 + pcs) * 8 + r) * (TB / 2)];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    const int d = task.x, kind = task.y, bi = task.z, bj = task.w;
-    const int N = pb.N;
-
-    // What to evaluate for each chain, from the plan the point phase executed LAST (the decisions that complete it run
-    // concurrently and may not be read): a leaf -> assume the subtree continues: the speculative state in the other
-    // buffer, with theta' derived here exactly as the decisions derive it; a skip-type plan -> the buffer as is.
-    const bool isrow = t >= TB;
-    const int loc = (isrow ? t - TB : t) & (TB - 1);
-    const int gi = (isrow ? bi : bj) * TB + loc;
-    const bool wantf = isrow ? (kind != TK_FH) : (kind == TK_FK);
-    const double mud = MAGI_SEL_D(pb.mu, d);
-    double xin[NC][D];
-    bool act[NC];
-    // (small loads first, the tile stream behind them: their wait then does not cover the row loads)
-    // (blocks of FH multiply xc on both sides: they need no theta and do not wait for it -- their traffic fills the window
-    //  in which the other workgroups derive theta')
-    if (wave < NC && kind != TK_FH) {
-        const int c = wave, cc = min(c0 + c, ch.n_chains - 1);
-        const LeafPlan* lp = ch.plan + (size_t)(parity ^ 1) * ch.n_chains + cc;
-        const bool derive = lp->active && !lp->skip && lp->leaf;
-        double thp = 0.0;
-        if (derive) {
-            const double* vb = ch.vec + vec_off(pb, cc, 0);
-            const double* part = ch.part + (size_t)cc * PART_K * ch.n_wg;
-            // (every load of the derivation is issued before the first wait)
-            const int e = pb.ND + D + min(lane, P - 1);
-            const double qv = (vb + (size_t)(V_Q + lp->cur) * pb.dimp)[e], pv = (vb + (size_t)(V_P + lp->cur) * pb.dimp)[e];
-            double rows[P];
-            part_rows_sum<P>(part, ch.n_wg, PK_TP, lane, rows);
-            double tpp = 0.0;
-#pragma unroll
-            for (int k = 0; k < P; ++k) if (lane == k) tpp = rows[k];
-            if (lane < P) {
-                const double ex = m_exp(qv);
-                const double sg = ex / (1.0 + ex);                       // == par[PAR_SGT] of that state (compute_par_entry)
-                const double qnx = next_entry_pre(pv, qv, lp->hs, lp->eps, theta_entry_grad(pb.beta_inv, tpp, sg));
-                thp = m_log(1.0 + m_exp(qnx));                           // == par'[PAR_TH] (compute_par_entry)
-            }
-        } else if (lane < P) {
-            thp = ch.par[(size_t)cc * PAR_COUNT + PAR_TH + lane];
-        }
-        if (lane < P) th_s[c][lane] = thp;
-        MAGI_STAMP(stream, 1);
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        const int cc = min(c0 + c, ch.n_chains - 1);
-        const LeafPlan* lp = ch.plan + (size_t)(parity ^ 1) * ch.n_chains + cc;
-        act[c] = (c0 + c < ch.n_chains) && lp->active != 0;
-        const int buf = (lp->skip || !lp->leaf) ? lp->cur : (lp->cur ^ 1);
-        const double* q = ch.vec + vec_off(pb, cc, V_Q + buf);
-#pragma unroll
-        for (int dd = 0; dd < D; ++dd) xin[c][dd] = q[dd * N + min(gi, N - 1)];
-    }
-
-    if (all_done) return;
-    MAGI_STAMPS_ON(decide, if (tix == 0 && threadIdx.x == 0) {
-        unsigned long long* st = reinterpret_cast<unsigned long long*>(ch.par + (size_t)c0 * PAR_COUNT + 40 + 11);
-        st[1] = __builtin_amdgcn_s_memrealtime();      // [12] first stream workgroup's start
-        st[0] = 0ull;                                    // [11] latest stream workgroup end (atomicMax below)
-    })
-    if (wave < NC) {                 // (the waves that derived theta' issue their first chunks now)
-#pragma unroll
-        for (int r = 0; r < 8; ++r) a0[r] = A[(size_t)(pc0 * 8 + r) * (TB / 2)];
-#pragma unroll
-        for (int r = 0; r < 8; ++r) a1[r] = A[(size_t)((pc0 + pcs) * 8 + r) * (TB / 2)];
-    }
-    __builtin_amdgcn_sched_barrier(0);
-    double thv[NC][P];
-    MAGI_STAMP(stream, 2);
-    if (kind != TK_FH) {
-        __syncthreads();             // th_s
-        MAGI_STAMP(stream, 3);
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-#pragma unroll
-            for (int k = 0; k < P; ++k) thv[c][k] = th_s[c][k];
-    } else {
-#pragma unroll
-        for (int c = 0; c < NC; ++c)
-#pragma unroll
-            for (int k = 0; k < P; ++k) thv[c][k] = 0.0;
-    }
-
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        double xd = xin[c][0];
-#pragma unroll
-        for (int dd = 1; dd < D; ++dd) if (d == dd) xd = xin[c][dd];
-        double val = wantf ? DR::f1(d, xin[c], thv[c]) : xd - mud;
-        if (gi >= N) val = 0.0;
-        if (t < 2 * TB) (isrow ? vrow : vcol)[c][loc] = val;
-    }
-    __syncthreads();
-    MAGI_STAMP(stream, 4);
-
-    constexpr int NACC = ALT ? NCK : 1;            // column accumulators per physical chunk (direction-independent sums)
-    double2 vc[NC], cacc[NC][NACC];
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        vc[c] = *reinterpret_cast<const double2*>(&vcol[c][2 * lane]);
-#pragma unroll
-        for (int k = 0; k < NACC; ++k) { cacc[c][k].x = 0.0; cacc[c][k].y = 0.0; }
-    }
-#pragma unroll
-    for (int ck = 0; ck < NCK; ++ck) {
-        double2 (&a)[8] = (ck & 1) ? a1 : a0;
-        const int row0 = wave * ST_RW + (pc0 + pcs * ck) * 8;          // first row of this chunk inside the block
-#pragma unroll
-        for (int c = 0; c < NC; ++c) {
-            double p[8];
-            double2& acc = cacc[c][ALT ? ck : 0];
-#pragma unroll
-            for (int r = 0; r < 8; ++r) {
-                const double2 ar = a[r];
-                p[r] = fma(ar.y, vc[c].y, ar.x * vc[c].x);
-                const double xr = vrow[c][row0 + r];
-                acc.x = fma(ar.x, xr, acc.x);
-                acc.y = fma(ar.y, xr, acc.y);
-            }
-            const double s = tsum8(p, lane);
-            // all 8 lanes of a group hold the same bits (commutative butterflies): an unconditional store keeps the loop
-            // free of branches (with them LLVM sinks the column accumulators behind the loop and the tile stays live)
-            rowout[c][row0 + (lane >> 3)] = s;
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        if (ck + 2 < NCK) {
-#pragma unroll
-            for (int r = 0; r < 8; ++r) a[r] = A[(size_t)((pc0 + pcs * (ck + 2)) * 8 + r) * (TB / 2)];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    }
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        double2 tot = cacc[c][0];
-        if (ALT) {
-            // physical chunk order 0, 1, .., NCK - 1 whatever the walk was: walk index of physical chunk k is k (even slots) or NCK - 1 - k
-            const bool rev = (parity & 1) != 0;
-            tot = rev ? cacc[c][NCK - 1] : cacc[c][0];
-#pragma unroll
-            for (int k = 1; k < NACC; ++k) {
-                const double2 nx = rev ? cacc[c][NCK - 1 - k] : cacc[c][k];
-                tot.x += nx.x; tot.y += nx.y;
-            }
-        }
-        *reinterpret_cast<double2*>(&colacc[wave][c][2 * lane]) = tot;
-    }
-    MAGI_STAMP(stream, 5);
-    __syncthreads();
-    MAGI_STAMP(stream, 6);
-
-    // partials: threads [0, TB) the row-type output (block row bi, slot bj), threads [TB, 2 TB) the
-    // column-type output (block row bj, slot bi; the diagonal blocks of FH / FK are complete by rows)
-    const int rvec = kind == TK_FH ? TV_HX : kind == TK_FK ? TV_KF : TV_EX;
-    const int cvec = kind == TK_FH ? TV_HX : kind == TK_FK ? TV_KF : TV_ETF;
-    const bool colout = (kind == TK_FE) || (bi != bj);
-    const size_t cstride = (size_t)4 * D * pb.nb * pb.Np;
-#pragma unroll
-    for (int c = 0; c < NC; ++c) {
-        if (!act[c] || t >= 2 * TB) continue;
-        double* tp = ch.tpart + (size_t)(c0 + c) * cstride;
-        if (!isrow) {
-            tp[((size_t)(rvec * D + d) * pb.nb + bj) * pb.Np + bi * TB + loc] = rowout[c][loc];
-        } else if (colout) {
-            double sum = colacc[0][c][loc];
-#pragma unroll
-            for (int w = 1; w < ST_WAVES; ++w) sum += colacc[w][c][loc];
-            tp[((size_t)(cvec * D + d) * pb.nb + bi) * pb.Np + bj * TB + loc] = sum;
-        }
-    }
-    MAGI_STAMP(stream, 7);
-    MAGI_STAMPS_FLUSH(stream, tix == MAGI_STAMP_WG && blockIdx.y == 0 && threadIdx.x == 64 * MAGI_STAMP_WAVE, ch.par, 8);
-    MAGI_STAMPS_ON(decide, __syncthreads(); if (threadIdx.x == 0)
-        atomicMax(reinterpret_cast<unsigned long long*>(ch.par + (size_t)c0 * PAR_COUNT + 40 + 11), (unsigned long long)__builtin_amdgcn_s_memrealtime());)
+    constexpr int KARGS = sizeof(DevProblem) + sizeof(DevChains) + sizeof(SamplerCfgDev) + sizeof(int);
+#include "leap_stream_body.h"
 }
 
 // ---- multi-chain streaming kernel on the matrix cores -----------------------------------------------------------------------
@@ -916,30 +656,10 @@ __global__ __launch_bounds__(256) void k_mirror(DevProblem pb, DevChains ch) {
 }
 
 // ---- point kernel: the elementwise half of slot `parity` (leap_point.h), N / 16 workgroups per chain -------------------------
-template <int DRIFT> struct PointRes {
-    static constexpr int SEPN = DriftT<DRIFT>::SEP ? PT_POINTS * SepLayout<DRIFT>::PS_TOTAL : 0;
-    static constexpr int N = SEPN > PT_POINTS * PT_DSLOT * 4 ? SEPN : PT_POINTS * PT_DSLOT * 4;
-};
 template <int DRIFT>
 __global__ __launch_bounds__(PT_THREADS) void k_point(DevProblem pb, DevChains ch, int parity) {
-    __shared__ double res[PointRes<DRIFT>::N];
-    __shared__ double redk[64 * PART_K];
-    __shared__ double s_mu[MAGI_MAX_D];
-    __shared__ double s_x[PT_POINTS * PT_DSLOT];
-    WG_TRACE(1, 0);
-    // (flag and plan are fetched together and combined arithmetically: `a || b` would fetch b only after a has arrived --
-    //  one more dependent round trip at the head of a 5 us kernel)
-    const int all_done = ch.gctl->all_done;
-    const LeafPlan lp = ch.plan[(size_t)parity * ch.n_chains + blockIdx.y];
-    kernarg_prefetch<sizeof(DevProblem) + sizeof(DevChains) + sizeof(int)>();
-    if (all_done != 0) return;
-    if (lp.vop != 0) { boundary_block<DRIFT>(pb, ch, lp, blockIdx.y, blockIdx.x, redk, s_mu, s_x, parity ^ 1); return; }     // a subtree / transition end (decide.h)
-    const int gate = (lp.active ^ 1) | lp.skip;
-    if (gate != 0) return;
-    if constexpr (DriftT<DRIFT>::SEP) {
-        if (ch.sep) { point_block_sep<DRIFT>(pb, ch, lp, blockIdx.y, blockIdx.x, res, redk, s_mu, s_x, parity ^ 1); return; }
-    }
-    point_block<DRIFT>(pb, ch, lp, blockIdx.y, blockIdx.x, res, redk, s_mu, parity ^ 1);
+    constexpr int KARGS = sizeof(DevProblem) + sizeof(DevChains) + sizeof(int);
+#include "leap_point_body.h"
 }
 
 // load-only twin of k_stream's tile stream (bench.py's ceiling leg): every workgroup reads its 128 KB block with the same
@@ -985,21 +705,11 @@ __global__ __launch_bounds__(MAGI_TAIL_THREADS) void k_leap_finalize(DevProblem 
     }
 }
 
-// Launches kernel k (`what` heads the error message); while magi_sampler_profile has set the handle's event pair, as an extended
-// launch that records the kernel's own begin / end in them.
-template <typename... P, typename... A>
-int launch(magi_handle* h, const char* what, void (*k)(P...), dim3 grid, dim3 block, hipStream_t s, A... args) {
-    if (h->prof_e0) hipExtLaunchKernelGGL(k, grid, block, 0, s, h->prof_e0, h->prof_e1, 0, args...);
-    else hipLaunchKernelGGL(k, grid, block, 0, s, args...);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string(what) + hipGetErrorString(e));
-    return MAGI_OK;
-}
 
 template <int NC, int DRIFT>
 int launch_stream_valu(magi_handle* h, int n_chains, int parity, bool with_decisions, hipStream_t s) {
     const dim3 grid(h->pb.n_tasks + (with_decisions ? NC : 0), (n_chains + NC - 1) / NC);      // + one decision workgroup per chain
-    return launch(h, "stream launch: ", k_stream<NC, DRIFT>, grid, dim3(64 * ST_WAVES), s, h->pb, h->ch, h->cfg, parity);
+    return magi_launch(h, "stream launch: ", k_stream<NC, DRIFT>, grid, dim3(64 * ST_WAVES), s, h->pb, h->ch, h->cfg, parity);
 }
 
 // (k_stream_sep exists for separable drifts only, k_stream_mc for the others: magi_stream_kernel never picks the missing one)
@@ -1010,10 +720,10 @@ int launch_stream_mc(magi_handle* h, int n_chains, int parity, bool with_decisio
     const char* what = "stream (matrix-core) launch: ";
     if constexpr (DriftT<DRIFT>::SEP) {          // grid.z = basis planes
         if (h->stream_kernel == StreamKernel::Sep8)
-            return launch(h, what, k_stream_sep<DRIFT, 8>, dim3(pb.n_stasks + dec, groups, SepLayout<DRIFT>::gz(8)), dim3(256), s, pb, h->ch, h->cfg, parity);
-        return launch(h, what, k_stream_sep<DRIFT, 16>, dim3(pb.n_stasks + dec, groups, SepLayout<DRIFT>::gz(16)), dim3(256), s, pb, h->ch, h->cfg, parity);
+            return magi_launch(h, what, k_stream_sep<DRIFT, 8>, dim3(pb.n_stasks + dec, groups, SepLayout<DRIFT>::gz(8)), dim3(256), s, pb, h->ch, h->cfg, parity);
+        return magi_launch(h, what, k_stream_sep<DRIFT, 16>, dim3(pb.n_stasks + dec, groups, SepLayout<DRIFT>::gz(16)), dim3(256), s, pb, h->ch, h->cfg, parity);
     } else {
-        return launch(h, what, k_stream_mc<DRIFT>, dim3(pb.n_tasks + dec, groups), dim3(256), s, pb, h->ch, h->cfg, parity);
+        return magi_launch(h, what, k_stream_mc<DRIFT>, dim3(pb.n_tasks + dec, groups), dim3(256), s, pb, h->ch, h->cfg, parity);
     }
 }
 
@@ -1033,7 +743,10 @@ int magi_leap_wgs(const DevProblem& pb) { return (pb.N + PT_POINTS - 1) / PT_POI
 // (288 workgroups) 14.6 / 16.0 and 14.9 / 16.2; N = 512, 8 chains (576) 20.0 / 17.0; N = 1024, 3 chains 30.7 / 23.5.
 // stream_family = valu forces the VALU kernel for every batch (A/B).  k_stream_sep's chain columns per operand line: xop_width.
 // A function of (options, problem, n_chains) alone: magi_stream_kernel_name and magi_gradient_bytes ask it about other batch sizes.
+// A problem group (magi_group_create) streams chain pairs when every member has an even number of chains and single chains otherwise, so
+// that a pair never spans two problems; magi_sampler_init has checked that each member's own rule picks a VALU kernel for its share.
 StreamKernel magi_stream_kernel(const magi_handle* h, int n_chains) {
+    if (h->group_n > 0) return (n_chains / h->group_n) % 2 == 0 ? StreamKernel::Valu2 : StreamKernel::Valu1;
     const int n = h->opt.family_chains > 0 ? std::max(n_chains, h->opt.family_chains) : n_chains;
     const bool matrix_cores = h->opt.stream_family == 1 ||
                               (h->opt.stream_family != 2 && n >= 3 && (long)h->pb.n_tasks * ((n + 1) / 2) > 320);
@@ -1111,13 +824,14 @@ void magi_sep_traffic(const DevProblem& pb, int n_chains, double* stores, double
 int magi_launch_mirror(magi_handle* h, int n_chains, hipStream_t s) {
     if (!h->ch.sep) return MAGI_OK;
     const dim3 g((h->pb.N + 255) / 256, n_chains), b(256);
-#define MAGI_CALL(DR) return launch(h, "mirror launch: ", k_mirror<DR>, g, b, s, h->pb, h->ch)
+#define MAGI_CALL(DR) return magi_launch(h, "mirror launch: ", k_mirror<DR>, g, b, s, h->pb, h->ch)
     MAGI_DRIFT_DISPATCH(h->pb.drift, MAGI_CALL);
 #undef MAGI_CALL
     return MAGI_OK;
 }
 
 int magi_launch_stream(magi_handle* h, int n_chains, int parity, bool with_decisions, hipStream_t s) {
+    if (h->group_n) return magi_launch_stream_group(h, n_chains, parity, with_decisions, s);      // (leap_group.hip)
     switch (h->stream_kernel) {        // (the order of the cases is the order of the kernels in the code object)
     case StreamKernel::Mc:
     case StreamKernel::Sep8:
@@ -1141,24 +855,25 @@ int magi_launch_stream(magi_handle* h, int n_chains, int parity, bool with_decis
 }
 
 int magi_launch_point(magi_handle* h, int n_chains, int parity, hipStream_t s) {
+    if (h->group_n) return magi_launch_point_group(h, n_chains, parity, s);
     const dim3 g(magi_leap_wgs(h->pb), n_chains), b(PT_THREADS);
-#define MAGI_CALL(DR) return launch(h, "point launch: ", k_point<DR>, g, b, s, h->pb, h->ch, parity)
+#define MAGI_CALL(DR) return magi_launch(h, "point launch: ", k_point<DR>, g, b, s, h->pb, h->ch, parity)
     MAGI_DRIFT_DISPATCH(h->pb.drift, MAGI_CALL);
 #undef MAGI_CALL
     return MAGI_OK;
 }
 
 int magi_launch_read_tiles(magi_handle* h, int rev, hipStream_t s) {
-    return launch(h, "read_tiles launch: ", k_read_tiles, dim3(h->pb.n_tasks), dim3(256), s, reinterpret_cast<const double2*>(h->pb.tiles), h->d_fin, rev);
+    return magi_launch(h, "read_tiles launch: ", k_read_tiles, dim3(h->pb.n_tasks), dim3(256), s, reinterpret_cast<const double2*>(h->pb.tiles), h->d_fin, rev);
 }
 
 int magi_launch_plan_eval(magi_handle* h, int n_chains, hipStream_t s, int parity) {
-    return launch(h, "plan launch: ", k_plan_eval, dim3((n_chains + 63) / 64), dim3(64), s, h->ch, parity);
+    return magi_launch(h, "plan launch: ", k_plan_eval, dim3((n_chains + 63) / 64), dim3(64), s, h->ch, parity);
 }
 
 int magi_launch_leap_finalize(magi_handle* h, int n_chains, double* d_out, hipStream_t s, int parity) {
     const dim3 g(n_chains), b(MAGI_TAIL_THREADS);
-#define MAGI_CALL(DR) return launch(h, "leap_finalize launch: ", k_leap_finalize<DR>, g, b, s, h->pb, h->ch, d_out, parity)
+#define MAGI_CALL(DR) return magi_launch(h, "leap_finalize launch: ", k_leap_finalize<DR>, g, b, s, h->pb, h->ch, d_out, parity)
     MAGI_DRIFT_DISPATCH(h->pb.drift, MAGI_CALL);
 #undef MAGI_CALL
     return MAGI_OK;

@@ -499,3 +499,9 @@ __device__ __forceinline__ void boundary_block(const DevProblem& pb, const DevCh
         if (q == 0) *(&ch.part[((size_t)cc * PART_K + k) * ch.n_wg + blk]) = s;
     }
 }
+
+// LDS of the point kernel's result staging (k_point, k_point_group)
+template <int DRIFT> struct PointRes {
+    static constexpr int SEPN = DriftT<DRIFT>::SEP ? PT_POINTS * SepLayout<DRIFT>::PS_TOTAL : 0;
+    static constexpr int N = SEPN > PT_POINTS * PT_DSLOT * 4 ? SEPN : PT_POINTS * PT_DSLOT * 4;
+};

@@ -216,7 +216,7 @@ __global__ __launch_bounds__(MAGI_TAIL_THREADS) void k_finalize(DevProblem pb, D
 }
 
 // transformed parameters of the states in V_Q (API path; the sampler's tail does this itself)
-__global__ void k_prepare(DevProblem pb, DevChains ch) {
+__device__ __forceinline__ void prepare_body(const DevProblem& pb, const DevChains& ch) {
     const int c = blockIdx.x, j = threadIdx.x;
     if (j < pb.D + pb.P)
         compute_par_entry(pb, j, ch.vec[vec_off(pb, c, V_Q) + pb.ND + j], ch.par + (size_t)c * PAR_COUNT);
@@ -228,6 +228,11 @@ __global__ void k_prepare(DevProblem pb, DevChains ch) {
         ch.xop[xop_off(pb, ch.n_chains, 1, c, d, i)] = q[e];
     }
 }
+
+__global__ void k_prepare(DevProblem pb, DevChains ch) { prepare_body(pb, ch); }
+
+// (problem groups: chain blockIdx.x belongs to member blockIdx.x / per)
+__global__ void k_prepare_group(const DevProblem* table, DevChains ch, int per) { prepare_body(group_member(table, (int)blockIdx.x / per), ch); }
 
 template <int PHASE, int NC>
 int launch_phase_nc(magi_handle* h, int n_chains, hipStream_t s) {
@@ -275,7 +280,8 @@ int magi_launch_gradient(magi_handle* h, int n_chains, hipStream_t s) {
 }
 
 int magi_launch_prepare(magi_handle* h, int n_chains, hipStream_t s) {
-    hipLaunchKernelGGL(k_prepare, dim3(n_chains), dim3(64), 0, s, h->pb, h->ch);
+    if (h->group_n) hipLaunchKernelGGL(k_prepare_group, dim3(n_chains), dim3(64), 0, s, (const DevProblem*)h->d_members, h->ch, h->group_per);
+    else hipLaunchKernelGGL(k_prepare, dim3(n_chains), dim3(64), 0, s, h->pb, h->ch);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("prepare launch: ") + hipGetErrorString(e));
     return magi_launch_mirror(h, n_chains, s);          // (separable drifts: the streaming kernel's operand mirror)

@@ -73,6 +73,14 @@ struct DevProblem {
     int bandf;     // -1 dense; else half-width 3b of the fused operators (products of band-b matrices)
 };
 
+// Member m of a problem group's device table (magi_group_create; leap.hip: k_stream_group).  The index is wave-uniform and the table
+// read-only while the sampler runs: read through the constant address space, the fields are scalar loads issued where a kernel first uses
+// them -- as the kernel-argument copy of a single problem is read -- and nothing is copied per lane.
+__device__ __forceinline__ const DevProblem& group_member(const DevProblem* table, int m) {
+    typedef const DevProblem __attribute__((address_space(4))) * const_pb_ptr;
+    return *(const DevProblem*)(const_pb_ptr)(unsigned long long)(table + m);
+}
+
 // Per-chain vector slots (each dimp doubles) -------------------------------------------------
 enum VecSlot {
     V_Q = 0,     // position buffer 0: X comp-major [D][N], sigma_pre[D], theta_pre[P]
@@ -923,6 +931,11 @@ struct magi_handle {
     hipEvent_t ev_pw[4] = {nullptr, nullptr, nullptr, nullptr};      // begin / end of the two factorisations of a dense build
     double potrf_wall_ms = 0.0, potrf_wall_flops = 0.0;              // of the last dense build (whole factorisations, not serialised)
     size_t apply_pin_cap = 0;
+    // problem group (magi_group_create): group_n > 0 members whose chains this handle samples; it has no matrices of its own
+    int group_n = 0;
+    std::vector<magi_handle*> members;
+    DevProblem* d_members = nullptr;     // [group_n] device table: the members' problems as of the last magi_sampler_init
+    int group_per = 0;                   // chains per member (n_chains / group_n)
 };
 
 // work-space slot `k` with room for n doubles (grow-only; freed by magi_destroy); nullptr + error on failure
@@ -941,6 +954,17 @@ int magi_fail(magi_handle* h, int code, const std::string& msg);
                                  ":" + std::to_string(__LINE__) + ")");                           \
     } while (0)
 
+// Launches kernel k (`what` heads the error message); while magi_sampler_profile has set the handle's event pair, as an extended
+// launch that records the kernel's own begin / end in them.
+template <typename... P, typename... A>
+int magi_launch(magi_handle* h, const char* what, void (*k)(P...), dim3 grid, dim3 block, hipStream_t s, A... args) {
+    if (h->prof_e0) hipExtLaunchKernelGGL(k, grid, block, 0, s, h->prof_e0, h->prof_e1, 0, args...);
+    else hipLaunchKernelGGL(k, grid, block, 0, s, args...);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string(what) + hipGetErrorString(e));
+    return MAGI_OK;
+}
+
 // launchers implemented in logpost.hip / sampler.hip ---------------------------------------------
 int magi_launch_gradient(magi_handle* h, int n_chains, hipStream_t s);        // phases 1-3
 int magi_launch_phase(magi_handle* h, int phase, int n_chains, hipStream_t s);
@@ -949,6 +973,8 @@ int magi_launch_stream(magi_handle* h, int n_chains, int parity, bool with_decis
 int magi_launch_point(magi_handle* h, int n_chains, int parity, hipStream_t s);                            // k_point: leapfrog epilogue per grid point
 int magi_launch_leap_finalize(magi_handle* h, int n_chains, double* d_out, hipStream_t s, int parity = 0);
 int magi_leap_wgs(const DevProblem& pb);
+int magi_launch_stream_group(magi_handle* h, int n_chains, int parity, bool with_decisions, hipStream_t s);   // leap_group.hip: the group twins
+int magi_launch_point_group(magi_handle* h, int n_chains, int parity, hipStream_t s);                            // of the two above (magi_group_create)
 StreamKernel magi_stream_kernel(const magi_handle* h, int n_chains);    // leap.hip: the streaming kernel that serves a batch of n_chains
 int magi_build_profile_get(const magi_handle* h, double* flops, double* ms, long* calls);           // build.hip
 int magi_fit_hparams_device(magi_handle* h, const double* I, int N, int D, const double* X, const double* mu, const double* mu_phi2,

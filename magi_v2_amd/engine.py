@@ -39,6 +39,7 @@ class SamplerCfg(C.Structure):
 
 _SYMBOLS = {
     "magi_create": (C.c_void_p, [C.c_int]),
+    "magi_group_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(C.c_void_p)]),
     "magi_destroy": (None, [C.c_void_p]),
     "magi_last_error": (C.c_char_p, [C.c_void_p]),
     "magi_version": (C.c_char_p, []),
@@ -142,6 +143,7 @@ class MagiEngine:
         self._h = self._lib.magi_create(int(device_id))
         if not self._h:
             raise MagiHipError(-2, self._lib.magi_last_error(None).decode())
+        self.device = int(device_id)
         self.N = self.D = self.P = None
         self.n_chains = 0
         self._cfg = None
@@ -425,3 +427,46 @@ class MagiEngine:
         b = np.zeros(8)
         self._check(self._lib.magi_gradient_bytes(self._h, int(n_chains), _ptr(b)))
         return b
+
+    @staticmethod
+    def group(engines):
+        """A MagiGroup over ``engines`` (see there)."""
+        return MagiGroup(engines)
+
+
+class MagiGroup(MagiEngine):
+    """One sampler over the chains of several problems of one shape on one GPU (include/magi_hip.h: magi_group_create): one captured
+    graph, one [stream, point] kernel pair per leapfrog slot for all of them, one host thread.
+
+    ``members``: MagiEngines of one loaded library and one device, each with its matrices and its problem set.  The chains are
+    problem-major, C per member: ``sampler_init`` takes G * C states and chain ids (ids may repeat across members), and the chains of member
+    m reproduce ``members[m].sampler_init(cfg, <its C states>, seed, <its C ids>)`` bit for bit.  The sampler_* methods work as on an
+    engine; the calls that need matrices of their own raise.  The group keeps its members alive; a member changed after ``sampler_init``
+    takes effect at the next ``sampler_init``."""
+
+    def __init__(self, engines):
+        engines = list(engines)
+        if not engines:
+            raise ValueError("a group needs at least one member")
+        lib, dev = engines[0]._lib, engines[0].device
+        for k, e in enumerate(engines):
+            if isinstance(e, MagiGroup) or not getattr(e, "_h", None):
+                raise ValueError(f"group member {k} is a group or a closed engine")
+            if e._lib is not lib:
+                raise ValueError(f"group member {k} runs another library than member 0 (its drift differs): group engines of one library only")
+            if e.device != dev:
+                raise ValueError(f"group member {k} is on device {e.device}, member 0 on {dev}")
+        self._lib = lib
+        self.user_drift = engines[0].user_drift
+        self.device = dev
+        self.members = engines
+        self._h = None
+        arr = (C.c_void_p * len(engines))(*[e._h for e in engines])
+        out = C.c_void_p()
+        rc = lib.magi_group_create(arr, len(engines), C.byref(out))
+        if rc != 0:
+            raise MagiHipError(rc, lib.magi_last_error(None).decode())
+        self._h = out.value
+        self.N, self.D, self.P = engines[0].N, engines[0].D, engines[0].P
+        self.n_chains = 0
+        self._cfg = None

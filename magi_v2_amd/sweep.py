@@ -44,11 +44,14 @@ def alpha_sweep_datasets(npz_path: str, discretization: int = 1) -> List[Tuple[s
 
 
 class SweepRunner:
-    """The datasets one rank owns: a MagiEngine (handle) per dataset on the rank's GPU, matrices built there."""
+    """The datasets one rank owns: a MagiEngine (handle) per dataset on the rank's GPU, matrices built there.  With two or more of them
+    (and ``grouped``, the default) they are sampled as one problem group (engine.MagiGroup: one captured graph, one kernel pair per
+    leapfrog slot for all their chains, one host thread); ``grouped=False``: one handle per dataset, each driven from its own host thread.
+    Either way a unit's samples are the same bits."""
 
     def __init__(self, device: int, datasets: Sequence[Tuple[str, dict]], chains_per_dataset: int, rank: int, world: int,
-                 bandsize=80, drift: str = "seir4"):
-        from .engine import MagiEngine
+                 bandsize=80, drift: str = "seir4", grouped: bool = True):
+        from .engine import MagiEngine, MagiGroup
         self.chains = chains_per_dataset
         self.units = shard_units(len(datasets), chains_per_dataset, rank, world)          # [(dataset index, [global unit ids])]
         self.engines, self.pbs, self.names = [], [], []
@@ -59,21 +62,32 @@ class SweepRunner:
             eng.build_matrices(pb["I"], pb["hp"]["phi1s"], pb["hp"]["phi2s"], 2.01, bandsize=bandsize, want_host=False)
             eng.set_problem(pb["mu"], pb["N_ds"], pb["idx"], pb["y"], pb["beta"], pb["LB"], drift)
             self.engines.append(eng); self.pbs.append(pb); self.names.append(name)
+        # (a group runs the VALU streaming kernels only: with more chains per dataset than those serve, the handles run on their own)
+        valu = all(e.stream_kernel_name(chains_per_dataset).startswith("k_stream<") for e in self.engines)
+        self.group = MagiGroup(self.engines) if grouped and len(self.engines) >= 2 and valu else None
 
     @property
     def unit_ids(self) -> List[int]:
         return [u for _, ids in self.units for u in ids]
 
     def init(self, seed: int, **cfg_kw):
+        rep = lambda v: np.repeat(np.asarray(v)[None], self.chains, axis=0)
+        if self.group is not None:
+            cfg = self.group.default_cfg(**cfg_kw)
+            cat = lambda key: np.concatenate([rep(pb[key]) for pb in self.pbs])
+            self.group.sampler_init(cfg, cat("Xhat"), cat("sig_pre0"), cat("th_pre0"), seed=seed, chain_ids=self.unit_ids)
+            return
         for eng, pb, (_, ids) in zip(self.engines, self.pbs, self.units):
             cfg = eng.default_cfg(**cfg_kw)
-            rep = lambda v: np.repeat(np.asarray(v)[None], self.chains, axis=0)
             eng.sampler_init(cfg, rep(pb["Xhat"]), rep(pb["sig_pre0"]), rep(pb["th_pre0"]), seed=seed, chain_ids=ids)
         self._captured = False
 
     def run(self, n_steps: int) -> int:
         """n_steps transitions of every chain of every owned dataset; returns the leapfrogs taken.  The handles are independent: each is
-        driven from its own host thread (ctypes releases the GIL), so a rank that owns two small datasets keeps both on the GPU at once."""
+        driven from its own host thread (ctypes releases the GIL), so a rank that owns two small datasets keeps both on the GPU at once.
+        A group advances all of them in one sampler."""
+        if self.group is not None:
+            return int(self.group.sampler_run(n_steps)[0])
         lf = [0] * len(self.engines)
         err: Dict[int, BaseException] = {}
 
@@ -102,7 +116,7 @@ class SweepRunner:
     def samples(self) -> Tuple[np.ndarray, List[int]]:
         """[units of this rank, results, N*D + D + P] (X flattened, sigma_pre, theta_pre) and their global unit ids."""
         blocks = []
-        for eng in self.engines:
+        for eng in ([self.group] if self.group is not None else self.engines):     # (a group's chains are in unit order: problem-major)
             Xs, sp, tp = eng.sampler_samples()
             blocks.append(np.concatenate([Xs.reshape(Xs.shape[0], Xs.shape[1], -1), sp, tp], axis=2))
         tail = blocks[0].shape[1:] if blocks else (0, 0)
@@ -114,6 +128,9 @@ class SweepRunner:
         return gather_samples(flat, ids, dst=dst)
 
     def close(self):
+        if self.group is not None:
+            self.group.close()
+            self.group = None
         for eng in self.engines:
             eng.close()
         self.engines = []
