@@ -248,6 +248,25 @@ int magi_sample(magi_handle* h, const magi_sampler_cfg* cfg, int n_chains,
 int magi_theta_init(magi_handle* h, int drift_id, int P, const double* Xhat, const double* mu, int num_iters, double learning_rate,
                     double* theta, double* loss_trace);
 
+/* ---- self-test ------------------------------------------------------------------------------- */
+
+/* Drift probe: evaluate THIS library's drift code by itself at n points, through the members the production kernels call (new
+ * unit csrc/selftest.hip; nothing is re-derived inside it).  magi_v2_amd/selftest.py holds the result against the expressions the code
+ * was generated from (a traced f_vec: the sympy evaluators of the same trace) before a freshly built library is first used.
+ * x[n][D], th[P] (transformed parameters, as the drift sees them), g[n][D] ->
+ * f[n][D], c[n][D] (c_k = sum_d g_d df_d/dx_k), t[n][P] (t_p = sum_d g_d df_d/dtheta_p).
+ *   path 0: DriftT<>::f / jt (what k_point and the theta initialiser inline)
+ *   path 1: the runtime-switch entries drift_f / drift_jt_g / drift_tt_g_acc (what the three-phase kernels call; for a traced drift
+ *           the generated user_drift_f / user_drift_jt)
+ *   path 2: the separable members (DriftT<>::coefs(theta), ::basis(x); what k_stream_sep and its point phase consume):
+ *           f_d = sum_k coefs[d][k] * basis[d][k] only, c and t are not written (g, c, t may be NULL);
+ *           MAGI_E_BADARG if DriftT<>::SEP is false
+ *   path 3: DriftT<>::f1(d, ..) per component (what the streaming kernels k_stream / k_stream_mc inline); f only, as path 2
+ * Needs a handle only for its device and stream: no matrices, no problem; a group handle is fine.  1 <= n <= 2^20. */
+int magi_drift_probe(magi_handle* h, int drift_id, int P, int path, int n,
+                     const double* x, const double* th, const double* g,
+                     double* f, double* c, double* t);
+
 /* ---- multi-GPU ---------------------------------------------------------------------------------
  * There is deliberately NO magi_gather in this ABI (SURVEY 8b had listed one).  The path shards by independent (dataset, chain) units with
  * no exchange while sampling (one handle per GPU, one process per GPU); its only collective is ONE gather of the post-burn-in samples at

@@ -75,6 +75,7 @@ _SYMBOLS = {
     "magi_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "magi_debug_par": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "magi_build_profile": (C.c_int, [C.c_void_p, _dp, _dp, _lp]),
+    "magi_drift_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
 }
 
 _libs = {}
@@ -130,16 +131,24 @@ class SamplerDiag:
 class MagiEngine:
     """One handle = one GPU.  Not thread-safe; different engines may be used from different threads."""
 
-    def __init__(self, device_id: int = 0, drift=None):
+    def __init__(self, device_id: int = 0, drift=None, _library: Optional[str] = None):
         """``drift``: a magi_v2_amd.drift.Drift traced from a user f_vec -> the engine runs the library that
-        magi_v2_amd.jit compiles for it; None / a built-in -> the base library."""
+        magi_v2_amd.jit compiles for it; None / a built-in -> the base library.  A drift-specialised library passes its self-test
+        (magi_v2_amd.selftest: verdict cached beside the file) before its first handle exists; a library that fails raises
+        MagiSelfTestError and is not used.  (``_library``: the self-test's own handles, on the file under test.)"""
         self.user_drift = None
-        if drift is not None and not getattr(drift, "is_builtin", True):
-            from . import jit
-            self._lib = load_library(jit.library_for(drift))
-            self.user_drift = drift
+        user = drift is not None and not getattr(drift, "is_builtin", True)
+        if _library is not None:
+            self._lib = load_library(_library)
+        elif user:
+            from . import jit, selftest
+            path = jit.library_for(drift)
+            selftest.ensure(path, drift, int(device_id))
+            self._lib = load_library(path)
         else:
             self._lib = load_library()
+        if user:
+            self.user_drift = drift
         self._h = self._lib.magi_create(int(device_id))
         if not self._h:
             raise MagiHipError(-2, self._lib.magi_last_error(None).decode())
@@ -175,6 +184,31 @@ class MagiEngine:
         if name == "stream_family" and isinstance(value, str):
             value = self._FAMILIES[value]
         self._check(self._lib.magi_set_option(self._h, name.encode(), int(value)))
+
+    def drift_probe(self, drift, X, th, g=None, path=0):
+        """This library's drift code by itself at the points X[n, D] (magi_drift_probe): (f[n, D], c[n, D], t[n, P]) with c_k = sum_d g_d
+        df_d/dx_k and t_p = sum_d g_d df_d/dtheta_p through path 0 (DriftT::f / jt) or 1 (the runtime-switch entries); (f, None, None)
+        through path 2 (the separable members; MagiHipError when the drift has none) or 3 (DriftT::f1).  ``th``: the parameters as the
+        drift sees them.  ``drift``: built-in name, or the Drift this engine was created for."""
+        if isinstance(drift, str):
+            (D, P), drift_id = DRIFT_SHAPES[drift], DRIFT_IDS[drift]
+        else:
+            D, P, drift_id = drift.D, drift.P, drift.device_id
+        X = _f64(X)
+        n = X.shape[0]
+        X, th = _f64(X, (n, D)), _f64(th, (P,))
+        deriv = int(path) in (0, 1)
+        g = _f64(np.zeros((n, D)) if g is None else g, (n, D)) if deriv else None
+        f = np.empty((n, D))
+        c, t = (np.empty((n, D)), np.empty((n, P))) if deriv else (None, None)
+        self._check(self._lib.magi_drift_probe(self._h, drift_id, P, int(path), n, _ptr(X), _ptr(th), _ptr(g), _ptr(f), _ptr(c), _ptr(t)))
+        return f, c, t
+
+    def selftest(self, drift=None, force=False):
+        """Self-test of the library this engine runs (magi_v2_amd.selftest.ensure: cached verdict, or a run on handles of its own);
+        returns the Report, raises MagiSelfTestError.  The base library is tested for ``drift`` (a built-in name) or, None, all three."""
+        from . import selftest
+        return selftest.ensure(self._lib._name, self.user_drift if self.user_drift is not None else drift, self.device, force=force)
 
     def stream_kernel_name(self, n_chains=1):
         buf = C.create_string_buffer(64)

@@ -1,16 +1,21 @@
 """Dev: kernel resource usage of csrc/leap.hip (hipcc -Rpass-analysis=kernel-resource-usage) + where in the ISA the scratch accesses sit.
-    python tools/resource_usage.py > profiles/r03_kernel_resource_usage.txt"""
-import re, subprocess, sys, os
+    python tools/resource_usage.py > profiles/r03_kernel_resource_usage.txt
+    python tools/resource_usage.py selftest.hip          (another unit of csrc/: the table alone)"""
+import re, subprocess, sys, os, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-os.chdir("/tmp")
+WORK = tempfile.mkdtemp(prefix="magi_ru_")          # (hipcc --save-temps writes into the working directory)
+os.chdir(WORK)
 sys.path.insert(0, ROOT)
 from magi_v2_amd import build
-src = os.path.join(build.CSRC, "leap.hip")
-r = subprocess.run(build.compile_command(src, ["-Rpass-analysis=kernel-resource-usage"]) + ["-c", src, "-o", "/tmp/leap_ru.o", "--save-temps"],
+unit = sys.argv[1] if len(sys.argv) > 1 else "leap.hip"
+src = os.path.join(build.CSRC, unit)
+r = subprocess.run(build.compile_command(src, ["-Rpass-analysis=kernel-resource-usage"]) + ["-c", src, "-o", os.path.join(WORK, unit[:-4] + "_ru.o"), "--save-temps"],
                    capture_output=True, text=True)
+if r.returncode != 0:
+    sys.exit(r.stderr[-4000:])
 txt = r.stderr
 blocks = re.split(r"remark: [^\n]*Function Name: ", txt)[1:]
-print("# hipcc -O3 --offload-arch=gfx950 -ffp-contract=on -Rpass-analysis=kernel-resource-usage magi_v2_amd/csrc/leap.hip  (ROCm 7.2)")
+print("# hipcc -O3 --offload-arch=gfx950 -ffp-contract=on -Rpass-analysis=kernel-resource-usage magi_v2_amd/csrc/%s  (ROCm 7.2)" % unit)
 print("# kernel | VGPRs | VGPR spills | SGPR spills | scratch B/lane | occupancy waves/SIMD | LDS B/block")
 KEYS = ["    VGPRs", "VGPRs Spill", "SGPRs Spill", r"ScratchSize \[bytes/lane\]", r"Occupancy \[waves/SIMD\]", r"LDS Size \[bytes/block\]"]
 for b in blocks:
@@ -22,7 +27,9 @@ for b in blocks:
         m = re.search(k + r": (\d+)", b)
         vals.append(m.group(1) if m else "?")
     print("%-28s | %4s | %3s | %3s | %4s | %2s | %6s" % tuple([dem] + vals))
-s = open("/tmp/leap-hip-amdgcn-amd-amdhsa-gfx950.s").read()
+if unit != "leap.hip":
+    sys.exit(0)
+s = open(os.path.join(WORK, "leap-hip-amdgcn-amd-amdhsa-gfx950.s")).read()
 def body(sym):
     i = s.index("\n" + sym + ":"); j = s.index(".Lfunc_end", i); return s[i:j].split("\n")
 print()
