@@ -50,6 +50,10 @@ enum { MAGI_MODE_NUTS = 0, MAGI_MODE_HMC = 1 };
  * D, P when this library was built that way (it then accepts ONLY drift = MAGI_DRIFT_USER), else 0. */
 int magi_user_drift_info(int* D, int* P);
 
+/* 1 when this library was built for a traced f_vec that uses its first argument t, else 0 (the base library, a library built for a
+ * drift that ignores t).  Such a library evaluates the drift of grid point i at the time t[i] given to magi_set_times. */
+int magi_user_drift_time_dependent(void);
+
 /* ---- lifetime --------------------------------------------------------------------------- */
 
 /* Binds device `device_id`, creates the stream.  NULL on failure (see magi_last_error(NULL)). */
@@ -124,6 +128,15 @@ int magi_dense_apply(magi_handle* h, int which, int transpose, int nv, const dou
 int magi_set_problem(magi_handle* h, const double* mu, const double* N_ds,
                      const int64_t* obs_idx, const double* y, int64_t n_obs,
                      double beta, const double* LB, int drift_id, int P);
+
+/* The times of the grid points, t[n] with n = the N of the handle's matrices (build or set them first: MAGI_E_STATE without;
+ * MAGI_E_BADARG for another n or a non-finite entry) -- the reference's self.I, which it passes to f_vec as t (magi_v2.py:155, 206,
+ * 335).  Read by a library whose drift depends on time (magi_user_drift_time_dependent) in magi_theta_init, magi_logpost_grad*, the
+ * sampler and as a member of a group; any other library stores and ignores them.  In a time-dependent library magi_set_problem
+ * without times for the current N fails with MAGI_E_STATE: nothing is ever evaluated at t = 0 silently.  The call invalidates what
+ * magi_set_problem invalidates (the sampler state, the captured graph); matrices of another N forget the times.  The times are
+ * independent of the grid the matrices were built on.  A group handle has none of its own: MAGI_E_STATE. */
+int magi_set_times(magi_handle* h, const double* t, int n);
 
 /* unnormalized_log_prob (magi_v2.py:308-348) and its gradient (TF autodiff in the reference,
  * induced by magi_v2.py:360-364) for n_chains independent states.
@@ -266,6 +279,10 @@ int magi_theta_init(magi_handle* h, int drift_id, int P, const double* Xhat, con
 int magi_drift_probe(magi_handle* h, int drift_id, int P, int path, int n,
                      const double* x, const double* th, const double* g,
                      double* f, double* c, double* t);
+/* magi_drift_probe with a time per point, tt[n] (NULL: every point at time 0, which is what magi_drift_probe does). */
+int magi_drift_probe_at(magi_handle* h, int drift_id, int P, int path, int n,
+                        const double* x, const double* th, const double* g,
+                        double* f, double* c, double* t, const double* tt);
 
 /* ---- multi-GPU ---------------------------------------------------------------------------------
  * There is deliberately NO magi_gather in this ABI (SURVEY 8b had listed one).  The path shards by independent (dataset, chain) units with

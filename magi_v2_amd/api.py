@@ -7,7 +7,8 @@ CPU implementation of that path in this package: without the library or a GPU th
 What differs from the reference, deliberately:
   * ``f_vec`` is a built-in drift name or a numpy-compatible callable (TensorFlow is not a dependency).  A
     callable that equals a compiled-in drift uses the hand-written kernels; any other one is traced with
-    sympy and the kernels are compiled for it (drift.py, jit.py; D <= 8, P <= 8).
+    sympy and the kernels are compiled for it (drift.py, jit.py; D <= 8, P <= 8).  It may use ``t``: the time of grid
+    point ``i`` is ``self.I[i]``, as in the reference.
   * hyper-parameters are fitted on the GPU (``magi_fit_hparams``: the reference's GP marginal
     likelihood + priors + Adam, magi_v2.py:538-691, restated -- TFP itself is not available, so this
     step is parity-unpinned); ``hparams=`` / ``hparam_iters=0`` bypass it.
@@ -278,11 +279,13 @@ class MAGI_v2:
         elif self._dev_valid and not self._host_overrides():
             # the general branch stays on the GPU: drift values, theta-Jacobian, (K^-1 + K^-T) r and the Adam update of every step in one
             # captured graph, the host waits once (csrc/thetainit.hip); 10 000 steps at N = 161: a fraction of a second
+            if self.drift.time_dependent:
+                self.engine.set_times(self.I)
             return self.engine.theta_init(self.drift, self.Xhat_init, self.mu_ds, iters)
         else:
             def grad_fn(th):
                 fv = f_np(self.I, self.Xhat_init, th).reshape(D, n)              # the reshape quirk
-                _, T = jac_np(self.Xhat_init, th)                                # [n, D, P]
+                _, T = jac_np(self.Xhat_init, th, self.I)                        # [n, D, P]
                 Tq = np.stack([T[:, :, p].reshape(D, n) for p in range(P)], axis=-1)   # same reshape as the drift
                 r = fv - bvec
                 g = self._dense_apply("K_inv", r) + self._dense_apply("K_inv", r, transpose=True)      # (K^-1 + K^-T) r on the GPU
@@ -306,7 +309,7 @@ class MAGI_v2:
         f = self.drift.f_np(I, X_full, thetas)
         h2 = 2.0 * (I[1, 0] - I[0, 0])
         r = f[1:-1] - (X_full[2:] - X_full[:-2]) / h2                            # [n-2, D]
-        J, T = self.drift.jac_np(X_full[1:-1], thetas)                           # [n-2, D, D], [n-2, D, P]
+        J, T = self.drift.jac_np(X_full[1:-1], thetas, I[1:-1])                  # [n-2, D, D], [n-2, D, P]
         gX = np.zeros_like(X_full)
         gX[1:-1] += 2.0 * np.einsum("nd,ndk->nk", r, J)
         gX[2:] -= 2.0 * r / h2
@@ -375,6 +378,8 @@ class MAGI_v2:
         self._sync_matrices()
         if family_chains is not None:
             eng.set_option("family_chains", int(family_chains))
+        if self.drift.time_dependent:          # (after the matrices, which fix N; an updated grid -- update_kernel_matrices -- is followed here)
+            eng.set_times(self.I)
         eng.set_problem(self.mu_ds, self.N_ds.astype(np.float64), np.asarray(self.not_nan_idxs),
                         np.asarray(self.y_tau_ds_observed), float(self.beta), sigma_sqs_LB, self.drift)
         sig_pre0, th_pre0 = host.softplus_inverse_inits(np.asarray(self.sigma_sqs_init, dtype=np.float64),

@@ -1620,6 +1620,7 @@ int magi_ensure_dense(magi_handle* h, int N, int D) {
     if (h->dDense[0] && h->dense_N == N && h->dense_D == D) return MAGI_OK;
     const size_t nn = (size_t)N * N;
     for (int k = 0; k < 3; ++k) { if (h->dDense[k]) (void)hipFree(h->dDense[k]); h->dDense[k] = nullptr; }
+    if (h->dense_N != N) h->times_N = 0;          // (the times of the grid points belong to a grid of the old size: magi_set_times)
     h->dense_N = h->dense_D = 0;
     for (int k = 0; k < 3; ++k) {
         hipError_t e = hipMalloc(&h->dDense[k], nn * D * sizeof(double));

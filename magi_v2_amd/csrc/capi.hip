@@ -34,6 +34,8 @@ void free_dev(void* p) { if (p) (void)hipFree(p); }
 
 void free_matrices(magi_handle* h) {
     free_dev(h->dCsym); free_dev(h->dM); free_dev(h->dMt); free_dev(h->dKsym); free_dev(h->dYobs);
+    free_dev(h->dTimes);
+    h->dTimes = nullptr; h->times_N = 0; h->times_cap = 0; h->pb.tgrid = nullptr;
     free_dev(h->dTiles); free_dev(h->dTasks);
     for (int k = 0; k < 3; ++k) { free_dev(h->dDense[k]); h->dDense[k] = nullptr; }
     h->dense_N = h->dense_D = 0;
@@ -272,6 +274,14 @@ int magi_user_drift_info(int* D, int* P) {
 #endif
 }
 
+int magi_user_drift_time_dependent(void) {
+#ifdef MAGI_USER_DRIFT_HEADER
+    return DriftT<MAGI_DRIFT_USER>::TDEP ? 1 : 0;
+#else
+    return 0;
+#endif
+}
+
 const char* magi_last_error(const magi_handle* h) { return h ? h->err.c_str() : g_magi_last_error.c_str(); }
 
 magi_handle* magi_create(int device_id) {
@@ -345,6 +355,7 @@ int magi_group_create(magi_handle* const* members, int n_members, magi_handle** 
     g->pb = members[0]->pb;                        // the shape; the data of every member is read from the device table
     g->pb.Csym = g->pb.M = g->pb.Mt = g->pb.Ksym = g->pb.yobs = g->pb.tiles = nullptr;
     g->pb.tasks = g->pb.stasks = nullptr;
+    g->pb.tgrid = nullptr;
     hipError_t e = hipMalloc(&g->d_members, sizeof(DevProblem) * n_members);
     if (e != hipSuccess) {
         magi_destroy(g);
@@ -508,6 +519,9 @@ int magi_set_problem(magi_handle* h, const double* mu, const double* N_ds, const
 #endif
     if (pb.D != needD || P != needP)
         return magi_fail(h, MAGI_E_BADARG, "drift expects D=" + std::to_string(needD) + ", P=" + std::to_string(needP));
+    if (magi_user_drift_time_dependent() && h->times_N != pb.N)
+        return magi_fail(h, MAGI_E_STATE, "this drift depends on time: call magi_set_times with the " + std::to_string(pb.N) +
+                                          " times of the grid points before magi_set_problem");
     (void)hipSetDevice(h->device);
     const int N = pb.N, D = pb.D;
     std::vector<double> yobs((size_t)N * D, std::nan(""));
@@ -535,6 +549,36 @@ int magi_set_problem(magi_handle* h, const double* mu, const double* N_ds, const
     h->have_problem = true;
     free_chains(h);          // dimp may have changed
     drop_graph(h);
+    return MAGI_OK;
+}
+
+int magi_set_times(magi_handle* h, const double* t, int n) {
+    if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_set_times");
+    if (!t) return magi_fail(h, MAGI_E_BADARG, "null pointer");
+    // the handle's N: of the resident dense stacks (magi_build_dense, before they are packed) or of the packed matrices
+    const int N = (h->dDense[0] && h->dense_N > 0) ? h->dense_N : (h->have_matrices ? h->pb.N : 0);
+    if (N <= 0) return magi_fail(h, MAGI_E_STATE, "matrices must be built or set before the times (they fix N)");
+    if (n != N) return magi_fail(h, MAGI_E_BADARG, "magi_set_times: n = " + std::to_string(n) + " times for a grid of N = " + std::to_string(N) + " points");
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(t[i])) return magi_fail(h, MAGI_E_BADARG, "magi_set_times: t[" + std::to_string(i) + "] is not finite");
+    (void)hipSetDevice(h->device);
+    const size_t np_ = ((size_t)n + MAGI_TB - 1) / MAGI_TB * MAGI_TB;        // = pb.Np: padded with the last time, no load needs a bounds test
+    if (h->stream) MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // (nothing in flight reads the old times)
+    h->sampler_ready = false;
+    drop_graph(h);                                                           // (the problem, pointer included, is a kernel argument of the captured graph)
+    h->times_N = 0;
+    if (np_ > h->times_cap) {
+        free_dev(h->dTimes);
+        h->dTimes = nullptr; h->times_cap = 0; h->pb.tgrid = nullptr;
+        MAGI_HIP_CHECK(h, hipMalloc(&h->dTimes, np_ * sizeof(double)));
+        h->times_cap = np_;
+    }
+    std::vector<double> pad(np_, t[n - 1]);
+    std::copy(t, t + n, pad.begin());
+    MAGI_HIP_CHECK(h, hipMemcpy(h->dTimes, pad.data(), np_ * sizeof(double), hipMemcpyHostToDevice));
+    h->pb.tgrid = h->dTimes;
+    h->times_N = n;
     return MAGI_OK;
 }
 

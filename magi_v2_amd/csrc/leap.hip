@@ -167,6 +167,17 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
     const unsigned vrow = ((unsigned)(bi * TB + 32 * wave + lj) * (unsigned)cw + (unsigned)li) * 8u; // + (16 cidx + 4 q) cw 8
     const unsigned cw8 = (unsigned)cw * 8u;
     double xcol[4][2][D], xrow[2][4][D];
+    // (a time-dependent drift: the times of the two slices hang on the task alone and go out in the same round; the lane that holds x of
+    //  a point loads t of that point)
+    double tcol[4][2], trow[2][4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int hh = 0; hh < 2; ++hh) tcol[k][hh] = colf ? point_time<DR>(pb, bj * TB + 2 * (t >> 4) + 32 * k + hh) : 0.0;
+#pragma unroll
+    for (int cidx = 0; cidx < 2; ++cidx)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) trow[cidx][q] = (coltype && rowf) ? point_time<DR>(pb, bi * TB + 32 * wave + 16 * cidx + 4 * q + lj) : 0.0;
     if (valid) {
         if (colf) {
 #pragma unroll
@@ -241,7 +252,7 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
         for (int k = 0; k < 4; ++k) {
             const int i0 = bj * TB + 2 * ((t >> 4) + 16 * k);
             double v0, v1;
-            if (colf) { v0 = DR::f1(d, xcol[k][0], thv); v1 = DR::f1(d, xcol[k][1], thv); }
+            if (colf) { v0 = drift_f1_at<DR>(d, xcol[k][0], thv, tcol[k][0]); v1 = drift_f1_at<DR>(d, xcol[k][1], thv, tcol[k][1]); }
             else { v0 = xcol[k][0][0] - mud; v1 = xcol[k][1][0] - mud; }
             vv[k].x = (valid && i0 < pb.N) ? v0 : 0.0;
             vv[k].y = (valid && i0 + 1 < pb.N) ? v1 : 0.0;
@@ -264,7 +275,7 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
         for (int q = 0; q < 4; ++q) {
             const int i = bi * TB + 32 * wave + 16 * cidx + 4 * q + lj;
             double w0 = 0.0;
-            if (valid && coltype) w0 = rowf ? DR::f1(d, xrow[cidx][q], thv) : xrow[cidx][q][0] - mud;
+            if (valid && coltype) w0 = rowf ? drift_f1_at<DR>(d, xrow[cidx][q], thv, trow[cidx][q]) : xrow[cidx][q][0] - mud;
             wf[cidx][q] = (i < pb.N) ? w0 : 0.0;
         }
     __syncthreads();                 // operand image complete
@@ -638,7 +649,7 @@ __global__ __launch_bounds__(256) void k_mirror(DevProblem pb, DevChains ch) {
         double x[D], ph[D][NBM];
 #pragma unroll
         for (int dd = 0; dd < D; ++dd) x[dd] = q[dd * pb.N + i];
-        DR::basis(x, ph);
+        drift_basis_at<DR>(x, point_time<DR>(pb, i), ph);
         const int cw = xop_width(ch.n_chains), groups = (ch.n_chains + 15) >> 4, cl = c & 15;
         const int planes = 1 + (NBM * cw + 15) / 16;
 #pragma unroll

@@ -20,7 +20,7 @@ template <int DRIFT>
 struct GridPoint {     // component d of grid index i of one chain (one lane)
     using DR = DriftT<DRIFT>;
     static constexpr int D = DR::D, P = DR::P;
-    struct Ops { double y, phe, rhoe, cpk[4], crk[4], x[D], th[P], sig2, qprev, gold; };
+    struct Ops { double y, phe, rhoe, cpk[4], crk[4], x[D], th[P], sig2, qprev, gold, tm; };
 
     // the lane's own operands: independent of the products, so their latency overlaps the partial sums
     static __device__ __forceinline__ Ops load(const DevProblem& pb, const DevChains& ch, const LeafPlan& lp, int cc, int i, int d) {
@@ -31,6 +31,7 @@ struct GridPoint {     // component d of grid index i of one chain (one lane)
         const double* q = vb + (size_t)(V_Q + lp.cur) * dimp;
         const int e = d * N + i;
         o.y = pb.yobs[e];
+        o.tm = point_time<DR>(pb, i);
         o.phe = 0.0; o.rhoe = 0.0; o.qprev = 0.0; o.gold = 0.0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) { o.cpk[k] = 0.0; o.crk[k] = 0.0; }
@@ -67,10 +68,10 @@ struct GridPoint {     // component d of grid index i of one chain (one lane)
         double f[D], g2[D], jt[D], tp[P];
 #pragma unroll
         for (int k = 0; k < P; ++k) tp[k] = 0.0;
-        DR::f(o.x, o.th, f);
+        drift_f_at<DR>(o.x, o.th, o.tm, f);
 #pragma unroll
         for (int dd = 0; dd < D; ++dd) g2[dd] = 2.0 * (res[dd * 4 + TV_KF] - res[dd * 4 + TV_EX]);
-        DR::jt(o.x, o.th, g2, jt, tp);
+        drift_jt_at<DR>(o.x, o.th, o.tm, g2, jt, tp);
         // select this lane's component
         double xd = o.x[0], fd = f[0], jtd = jt[0];
 #pragma unroll
@@ -265,7 +266,7 @@ __device__ __forceinline__ void point_block_sep(const DevProblem& pb, const DevC
             double f[D], g2[D], jt[D], tp[P];
 #pragma unroll
             for (int k = 0; k < P; ++k) tp[k] = 0.0;
-            DR::f(ops.x, ops.th, f);
+            drift_f_at<DR>(ops.x, ops.th, ops.tm, f);
             double hx = 0.0, ex = 0.0, etf = 0.0, kf = 0.0;
 #pragma unroll
             for (int dd = 0; dd < D; ++dd) {
@@ -281,7 +282,7 @@ __device__ __forceinline__ void point_block_sep(const DevProblem& pb, const DevC
                 g2[dd] = 2.0 * (kfd - exd);
                 if (d == dd) { hx = r[SL::slot_hx(dd)]; ex = exd; etf = etd; kf = kfd; }
             }
-            DR::jt(ops.x, ops.th, g2, jt, tp);
+            drift_jt_at<DR>(ops.x, ops.th, ops.tm, g2, jt, tp);
             double xd = ops.x[0], fdv = f[0], jtd = jt[0];
 #pragma unroll
             for (int dd = 1; dd < D; ++dd) if (d == dd) { xd = ops.x[dd]; fdv = f[dd]; jtd = jt[dd]; }
@@ -329,7 +330,7 @@ __device__ __forceinline__ void point_block_sep(const DevProblem& pb, const DevC
                 double xq[D], ph[D][NBM];
 #pragma unroll
                 for (int dd = 0; dd < D; ++dd) xq[dd] = s_x[fpt * PT_DSLOT + dd];
-                DR::basis(xq, ph);
+                drift_basis_at<DR>(xq, ops.tm, ph);          // (the next state of the SAME grid point)
                 const int cw = xop_width(ch.n_chains), groups = (ch.n_chains + 15) >> 4, cl = cc & 15;
                 const int planes = 1 + (NBM * cw + 15) / 16;
                 double* m0 = ch.vop + vop_off(D, planes, pb.Np, groups, mirror_buf, cc >> 4, fd, 0, 0);      // plane 0 of this component
@@ -470,7 +471,7 @@ __device__ __forceinline__ void boundary_block(const DevProblem& pb, const DevCh
                     double xq[D], ph[D][NBM];
 #pragma unroll
                     for (int dd = 0; dd < D; ++dd) xq[dd] = s_x[fpt * PT_DSLOT + dd];
-                    DR::basis(xq, ph);
+                    drift_basis_at<DR>(xq, point_time<DR>(pb, fi), ph);
                     const int cw = xop_width(ch.n_chains), groups = (ch.n_chains + 15) >> 4, cl = cc & 15;
                     const int planes = 1 + (NBM * cw + 15) / 16;
                     double* m0 = ch.vop + vop_off(D, planes, pb.Np, groups, mirror_buf, cc >> 4, fd, 0, 0);

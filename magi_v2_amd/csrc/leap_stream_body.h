@@ -66,6 +66,7 @@
     const int gi = (isrow ? bi : bj) * TB + loc;
     const bool wantf = isrow ? (kind != TK_FH) : (kind == TK_FK);
     const double mud = MAGI_SEL_D(pb.mu, d);
+    const double tm = point_time<DR>(pb, gi);          // (a time-dependent drift: needs the task alone, on the wire in front of everything the plan decides)
     double xin[NC][D];
     bool act[NC];
     // (small loads first, the tile stream behind them: their wait then does not cover the row loads)
@@ -144,7 +145,7 @@
         double xd = xin[c][0];
 #pragma unroll
         for (int dd = 1; dd < D; ++dd) if (d == dd) xd = xin[c][dd];
-        double val = wantf ? DR::f1(d, xin[c], thv[c]) : xd - mud;
+        double val = wantf ? drift_f1_at<DR>(d, xin[c], thv[c], tm) : xd - mud;
         if (gi >= N) val = 0.0;
         if (t < 2 * TB) (isrow ? vrow : vcol)[c][loc] = val;
     }

@@ -41,13 +41,13 @@ __device__ inline void row_epilogue(const DevProblem& pb, double* vb, const doub
     for (int p = 0; p < MAGI_MAX_P; ++p) th[p] = (p < pb.P) ? par[PAR_TH + p] : 0.0;
     if (PHASE == 1) {
         vb[(size_t)V_CX * dimp + e] = v0;
-        vb[(size_t)V_R * dimp + e] = drift_f(pb.drift, d, xg, th) - v1;
+        vb[(size_t)V_R * dimp + e] = drift_f(pb.drift, d, xg, th, point_time_rt(pb, row)) - v1;
     } else {
         double g2[MAGI_MAX_D];
 #pragma unroll
         for (int dd = 0; dd < MAGI_MAX_D; ++dd)
             g2[dd] = (dd < pb.D) ? 2.0 * vb[(size_t)V_KR * dimp + dd * N + row] : 0.0;
-        const double jt = drift_jt_g(pb.drift, d, xg, th, g2);
+        const double jt = drift_jt_g(pb.drift, d, xg, th, g2, point_time_rt(pb, row));
         const double d12 = 2.0 * vb[(size_t)V_CX * dimp + e] - v0 + jt;
         const double y = pb.yobs[e];
         double d4 = 0.0;

@@ -71,6 +71,8 @@ struct DevProblem {
     int Np;        // nb * TB
     int wb;        // block half-band: blocks with |bi - bj| <= wb exist (nb when dense)
     int bandf;     // -1 dense; else half-width 3b of the fused operators (products of band-b matrices)
+    const double* tgrid;   // [Np] times of the grid points (magi_set_times), padded with the last one; read by the kernels of a library whose
+                           // drift uses t (DriftT<>::TDEP, point_time below) and by no other; nullptr until they are set
 };
 
 // Member m of a problem group's device table (magi_group_create; leap.hip: k_stream_group).  The index is wave-uniform and the table
@@ -392,10 +394,12 @@ template <int DRIFT> struct DriftT;
         }                                                        \
     } while (0)
 #endif
-__device__ __forceinline__ double drift_f(int drift, int d, const double* x, const double* th) {
+// (tm: the time of the grid point, point_time_rt below; the compiled-in drifts do not use it)
+__device__ __forceinline__ double drift_f(int drift, int d, const double* x, const double* th, double tm) {
+    (void)tm;
     switch (drift) {
 #ifdef MAGI_USER_DRIFT_HEADER
-    case MAGI_DRIFT_USER: return user_drift_f(d, x, th);
+    case MAGI_DRIFT_USER: return user_drift_f(d, x, th, tm);
 #endif
     case MAGI_DRIFT_SEIR3: {   // vignette.ipynb cell 3
         double E = x[0], I = x[1], R = x[2], S = 1.0 - ((E + I) + R);
@@ -421,14 +425,15 @@ __device__ __forceinline__ double drift_f(int drift, int d, const double* x, con
 }
 
 // sum_d' g[d'] * d f_d' / d x_d   (column d of the Jacobian contracted with g)
-__device__ __forceinline__ double drift_jt_g(int drift, int d, const double* x, const double* th, const double* g) {
+__device__ __forceinline__ double drift_jt_g(int drift, int d, const double* x, const double* th, const double* g, double tm) {
+    (void)tm;
     switch (drift) {
 #ifdef MAGI_USER_DRIFT_HEADER
     case MAGI_DRIFT_USER: {
         double c[MAGI_MAX_D];
 #pragma unroll
         for (int k = 0; k < MAGI_MAX_D; ++k) c[k] = 0.0;
-        user_drift_jt(x, th, g, c, nullptr);
+        user_drift_jt(x, th, tm, g, c, nullptr);
         return MAGI_SEL_D(c, d);
     }
 #endif
@@ -460,7 +465,8 @@ __device__ __forceinline__ double drift_jt_g(int drift, int d, const double* x, 
 
 // out[p] += sum_d g[d] * d f_d / d theta_p
 __device__ __forceinline__ void drift_tt_g_acc(int drift, const double (&x)[MAGI_MAX_D], const double (&th)[MAGI_MAX_P],
-                                               const double (&g)[MAGI_MAX_D], double (&out)[MAGI_MAX_P]) {
+                                               const double (&g)[MAGI_MAX_D], double (&out)[MAGI_MAX_P], double tm) {
+    (void)tm;
     // every case fills the same five scalars so the accumulation below keeps static indices
     double o0 = 0.0, o1 = 0.0, o2 = 0.0, o3 = 0.0, o4 = 0.0;
 #ifdef MAGI_USER_DRIFT_HEADER
@@ -468,7 +474,7 @@ __device__ __forceinline__ void drift_tt_g_acc(int drift, const double (&x)[MAGI
         double t[MAGI_MAX_P];
 #pragma unroll
         for (int k = 0; k < MAGI_MAX_P; ++k) t[k] = 0.0;
-        user_drift_jt(x, th, g, nullptr, t);
+        user_drift_jt(x, th, tm, g, nullptr, t);
 #pragma unroll
         for (int k = 0; k < MAGI_MAX_P; ++k) out[k] += t[k];
         return;
@@ -511,6 +517,7 @@ __device__ __forceinline__ void drift_tt_g_acc(int drift, const double (&x)[MAGI
 // basis / coefs fill [D][NBMAX] with zeros in unused entries.
 template <> struct DriftT<MAGI_DRIFT_SEIR3> {
     static constexpr int D = 3, P = 3;
+    static constexpr bool TDEP = false;
     static constexpr bool SEP = true;
     static constexpr int NBMAX = 2;
     __host__ __device__ static constexpr int nbasis(int d) { return d == 2 ? 1 : 2; }
@@ -552,6 +559,7 @@ template <> struct DriftT<MAGI_DRIFT_SEIR3> {
 
 template <> struct DriftT<MAGI_DRIFT_SEIR4> {
     static constexpr int D = 4, P = 3;
+    static constexpr bool TDEP = false;
     static constexpr bool SEP = true;
     static constexpr int NBMAX = 2;
     __host__ __device__ static constexpr int nbasis(int d) { return (d == 0 || d == 3) ? 1 : 2; }
@@ -597,6 +605,7 @@ template <> struct DriftT<MAGI_DRIFT_SEIR4> {
 
 template <> struct DriftT<MAGI_DRIFT_SIRW> {
     static constexpr int D = 4, P = 5;
+    static constexpr bool TDEP = false;
     static constexpr bool SEP = true;
     static constexpr int NBMAX = 3;
     __host__ __device__ static constexpr int nbasis(int d) { return d < 2 ? 2 : 3; }
@@ -641,6 +650,48 @@ template <> struct DriftT<MAGI_DRIFT_SIRW> {
         t[4] += (g[0] - g[3]) * W;
     }
 };
+
+// ------------------------------------------------------------------------------------------
+// Time-dependent drifts (a traced f_vec that uses t: DriftT<>::TDEP).  The time of grid point i is pb.tgrid[i] (i < Np: the padding
+// holds the last time, no load needs a bounds test).  Every drift evaluation of every kernel goes through the five functions below; with
+// TDEP false the time is the constant 0.0 that nothing reads -- no load, no instruction -- and the members are called with the
+// signatures they have always had.
+// ------------------------------------------------------------------------------------------
+template <class DR>
+__device__ __forceinline__ double point_time(const DevProblem& pb, int i) {
+    if constexpr (DR::TDEP) return pb.tgrid[i];
+    else return 0.0;
+}
+// for the kernels that take the drift id as a run-time value (logpost.hip, finalize_gradient)
+__device__ __forceinline__ double point_time_rt(const DevProblem& pb, int i) {
+#ifdef MAGI_USER_DRIFT_HEADER
+    return point_time<DriftT<MAGI_DRIFT_USER>>(pb, i);
+#else
+    (void)pb; (void)i;
+    return 0.0;
+#endif
+}
+template <class DR>
+__device__ __forceinline__ void drift_f_at(const double (&x)[DR::D], const double (&th)[DR::P], double tm, double (&o)[DR::D]) {
+    if constexpr (DR::TDEP) DR::f(x, th, tm, o);
+    else DR::f(x, th, o);
+}
+template <class DR>
+__device__ __forceinline__ double drift_f1_at(int d, const double (&x)[DR::D], const double (&th)[DR::P], double tm) {
+    if constexpr (DR::TDEP) return DR::f1(d, x, th, tm);
+    else return DR::f1(d, x, th);
+}
+template <class DR>
+__device__ __forceinline__ void drift_jt_at(const double (&x)[DR::D], const double (&th)[DR::P], double tm, const double (&g)[DR::D], double (&c)[DR::D],
+                                            double (&t)[DR::P]) {
+    if constexpr (DR::TDEP) DR::jt(x, th, tm, g, c, t);
+    else DR::jt(x, th, g, c, t);
+}
+template <class DR>
+__device__ __forceinline__ void drift_basis_at(const double (&x)[DR::D], double tm, double (&ph)[DR::D][DR::NBMAX]) {
+    if constexpr (DR::TDEP) DR::basis(x, tm, ph);
+    else DR::basis(x, ph);
+}
 
 // ------------------------------------------------------------------------------------------
 // Storage of the separable streaming path (k_stream_sep, leap.hip).
@@ -795,7 +846,7 @@ __device__ inline FinalizeOut finalize_gradient(const DevProblem& pb, double* vb
                 if (!isnan(y)) { const double df = xv - y; ss[d] = fma(df, df, ss[d]); }
             } else { x[d] = 0.0; g2[d] = 0.0; }
         }
-        drift_tt_g_acc(pb.drift, x, th, g2, tp);
+        drift_tt_g_acc(pb.drift, x, th, g2, tp, point_time_rt(pb, i));
     }
     double red[K];
     red[0] = t1s;
@@ -883,6 +934,9 @@ struct magi_handle {
     bool have_problem = false;
     DevProblem pb{};
     double *dCsym = nullptr, *dM = nullptr, *dMt = nullptr, *dKsym = nullptr, *dYobs = nullptr;
+    double* dTimes = nullptr;        // pb.tgrid: the times of the grid points (magi_set_times), [times_cap >= pb.Np]
+    int times_N = 0;                 // the N they were set for (0: not set; forgotten when the matrices change to another N)
+    size_t times_cap = 0;
     size_t mat_elems = 0;
     // dense C^-1, m, K^-1 ([D][N][N], unmasked) as built or uploaded: authoritative until the caller uploads others; packed
     // (band mask, symmetrised / transposed copies, single-phase operator blocks) by magi_pack_matrices

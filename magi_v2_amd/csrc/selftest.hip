@@ -14,11 +14,13 @@ namespace {
 template <int DRIFT, int PATH>
 __global__ __launch_bounds__(256) void k_drift_probe(int drift, int n, const double* __restrict__ xs /* [n][D] */, const double* __restrict__ ths /* [P] */,
                                                      const double* __restrict__ gs /* [n][D] */, double* __restrict__ fo /* [n][D] */,
-                                                     double* __restrict__ co /* [n][D] */, double* __restrict__ to /* [n][P] */) {
+                                                     double* __restrict__ co /* [n][D] */, double* __restrict__ to /* [n][P] */,
+                                                     const double* __restrict__ ts /* [n] time per point, or null: 0 */) {
     using DR = DriftT<DRIFT>;
     constexpr int D = DR::D, P = DR::P;
     const int i = blockIdx.x * 256 + threadIdx.x;
     if (i >= n) return;
+    const double tm = ts ? ts[i] : 0.0;
     if constexpr (PATH == 1) {
         double x[MAGI_MAX_D], g[MAGI_MAX_D], th[MAGI_MAX_P], t[MAGI_MAX_P];
 #pragma unroll
@@ -27,10 +29,10 @@ __global__ __launch_bounds__(256) void k_drift_probe(int drift, int n, const dou
         for (int p = 0; p < MAGI_MAX_P; ++p) { th[p] = (p < P) ? ths[p] : 0.0; t[p] = 0.0; }
 #pragma unroll
         for (int d = 0; d < D; ++d) {
-            fo[(size_t)i * D + d] = drift_f(drift, d, x, th);
-            co[(size_t)i * D + d] = drift_jt_g(drift, d, x, th, g);
+            fo[(size_t)i * D + d] = drift_f(drift, d, x, th, tm);
+            co[(size_t)i * D + d] = drift_jt_g(drift, d, x, th, g, tm);
         }
-        drift_tt_g_acc(drift, x, th, g, t);
+        drift_tt_g_acc(drift, x, th, g, t, tm);
 #pragma unroll
         for (int p = 0; p < P; ++p) to[(size_t)i * P + p] = t[p];
     } else {
@@ -45,8 +47,8 @@ __global__ __launch_bounds__(256) void k_drift_probe(int drift, int n, const dou
             for (int k = 0; k < D; ++k) g[k] = gs[(size_t)i * D + k];
 #pragma unroll
             for (int p = 0; p < P; ++p) t[p] = 0.0;
-            DR::f(x, th, f);
-            DR::jt(x, th, g, c, t);
+            drift_f_at<DR>(x, th, tm, f);
+            drift_jt_at<DR>(x, th, tm, g, c, t);
 #pragma unroll
             for (int k = 0; k < D; ++k) { fo[(size_t)i * D + k] = f[k]; co[(size_t)i * D + k] = c[k]; }
 #pragma unroll
@@ -54,7 +56,7 @@ __global__ __launch_bounds__(256) void k_drift_probe(int drift, int n, const dou
         } else if constexpr (PATH == 2) {
             if constexpr (DR::SEP) {
                 double ph[D][DR::NBMAX], cf[D][DR::NBMAX];
-                DR::basis(x, ph);
+                drift_basis_at<DR>(x, tm, ph);
                 DR::coefs(th, cf);
 #pragma unroll
                 for (int d = 0; d < D; ++d) {
@@ -66,36 +68,38 @@ __global__ __launch_bounds__(256) void k_drift_probe(int drift, int n, const dou
             }
         } else {
 #pragma unroll
-            for (int d = 0; d < D; ++d) fo[(size_t)i * D + d] = DR::f1(d, x, th);
+            for (int d = 0; d < D; ++d) fo[(size_t)i * D + d] = drift_f1_at<DR>(d, x, th, tm);
         }
     }
 }
 
 template <int DRIFT>
-int probe(magi_handle* h, int drift, int P, int path, int n, const double* x, const double* th, const double* g, double* f, double* c, double* t) {
+int probe(magi_handle* h, int drift, int P, int path, int n, const double* x, const double* th, const double* g, double* f, double* c, double* t, const double* tt) {
     using DR = DriftT<DRIFT>;
     constexpr int D = DR::D;
     if (P != DR::P) return magi_fail(h, MAGI_E_BADARG, "drift expects P=" + std::to_string(DR::P));
     if (path == 2 && !DR::SEP) return magi_fail(h, MAGI_E_BADARG, "path 2: this drift has no separable form");
     const bool deriv = path < 2;
     if (deriv && (!g || !c || !t)) return magi_fail(h, MAGI_E_BADARG, "null pointer");
-    // one device buffer: x | g | f | c (n D each), t (n P), th (P)
-    const size_t nd = (size_t)n * D, np_ = (size_t)n * P, total = 4 * nd + np_ + P;
+    // one device buffer: x | g | f | c (n D each), t (n P), th (P), times (n)
+    const size_t nd = (size_t)n * D, np_ = (size_t)n * P, total = 4 * nd + np_ + P + (size_t)n;
     double* buf = nullptr;
     MAGI_HIP_CHECK(h, hipMalloc((void**)&buf, total * sizeof(double)));
     double *dx = buf, *dg = buf + nd, *df = buf + 2 * nd, *dc = buf + 3 * nd, *dt = buf + 4 * nd, *dth = dt + np_;
+    const double* dtt = tt ? dth + P : nullptr;
     int rc = MAGI_OK;
     hipError_t e = hipMemcpyAsync(dx, x, nd * sizeof(double), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dth, th, P * sizeof(double), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess && tt) e = hipMemcpyAsync(dth + P, tt, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess && deriv) e = hipMemcpyAsync(dg, g, nd * sizeof(double), hipMemcpyHostToDevice, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(df, 0, (2 * nd + np_) * sizeof(double), h->stream);
     if (e == hipSuccess) {
         const dim3 grid((n + 255) / 256), block(256);
         switch (path) {
-        case 0: rc = magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 0>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt); break;
-        case 1: rc = magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 1>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt); break;
-        case 2: rc = magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 2>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt); break;
-        default: rc = magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 3>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt); break;
+        case 0: rc = magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 0>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt, dtt); break;
+        case 1: rc = magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 1>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt, dtt); break;
+        case 2: rc = magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 2>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt, dtt); break;
+        default: rc = magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 3>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt, dtt); break;
         }
     }
     if (rc == MAGI_OK && e == hipSuccess) e = hipMemcpyAsync(f, df, nd * sizeof(double), hipMemcpyDeviceToHost, h->stream);
@@ -113,6 +117,11 @@ int probe(magi_handle* h, int drift, int P, int path, int n, const double* x, co
 
 int magi_drift_probe(magi_handle* h, int drift_id, int P, int path, int n, const double* x, const double* th, const double* g,
                      double* f, double* c, double* t) {
+    return magi_drift_probe_at(h, drift_id, P, path, n, x, th, g, f, c, t, nullptr);
+}
+
+int magi_drift_probe_at(magi_handle* h, int drift_id, int P, int path, int n, const double* x, const double* th, const double* g,
+                        double* f, double* c, double* t, const double* tt) {
     if (!h) return MAGI_E_BADARG;
     if (!x || !th || !f) return magi_fail(h, MAGI_E_BADARG, "null pointer");
     if (path < 0 || path > 3) return magi_fail(h, MAGI_E_BADARG, "path: 0 f / jt, 1 runtime-switch entries, 2 separable members, 3 f1");
@@ -124,7 +133,7 @@ int magi_drift_probe(magi_handle* h, int drift_id, int P, int path, int n, const
 #endif
     (void)hipSetDevice(h->device);
     int rc = MAGI_OK;
-#define MAGI_CALL(DR) rc = probe<DR>(h, drift_id, P, path, n, x, th, g, f, c, t)
+#define MAGI_CALL(DR) rc = probe<DR>(h, drift_id, P, path, n, x, th, g, f, c, t, tt)
     MAGI_DRIFT_DISPATCH(drift_id, MAGI_CALL);
 #undef MAGI_CALL
     return rc;

@@ -17,7 +17,8 @@ enum { TI_TH = 0, TI_M = 8, TI_V = 16, TI_B1T = 24, TI_B2T = 25, TI_STEP = 26, T
 
 template <int DRIFT>
 __global__ __launch_bounds__(256) void k_ti_eval(int N, const double* __restrict__ Xh /* [N][D] */, const double* __restrict__ st,
-                                                 const double* __restrict__ bvec /* [D N] */, double* __restrict__ r, double* __restrict__ Tq /* [P][D N] */) {
+                                                 const double* __restrict__ bvec /* [D N] */, double* __restrict__ r, double* __restrict__ Tq /* [P][D N] */,
+                                                 const double* __restrict__ tg /* [N] times of the grid points; read by a time-dependent drift only */) {
     using DR = DriftT<DRIFT>;
     constexpr int D = DR::D, P = DR::P;
     const int n = N * D, e = blockIdx.x * 256 + threadIdx.x;
@@ -28,8 +29,10 @@ __global__ __launch_bounds__(256) void k_ti_eval(int N, const double* __restrict
     for (int k = 0; k < D; ++k) { x[k] = Xh[(size_t)i * D + k]; g[k] = (k == d) ? 1.0 : 0.0; }
 #pragma unroll
     for (int p = 0; p < P; ++p) { th[p] = st[TI_TH + p]; t[p] = 0.0; }
-    const double f = DR::f1(d, x, th);
-    DR::jt(x, th, g, c, t);                          // g = e_d: t[p] = d f_d / d theta_p
+    double tm = 0.0;
+    if constexpr (DR::TDEP) tm = tg[i];
+    const double f = drift_f1_at<DR>(d, x, th, tm);
+    drift_jt_at<DR>(x, th, tm, g, c, t);                        // g = e_d: t[p] = d f_d / d theta_p
     r[e] = f - bvec[e];                              // (bvec is [D][N]: the SAME flat index -- the reshape of :155-156)
 #pragma unroll
     for (int p = 0; p < P; ++p) Tq[(size_t)p * n + e] = t[p];
@@ -73,7 +76,7 @@ __global__ __launch_bounds__(256) void k_ti_step(int n, int P, const double* __r
 template <int DRIFT>
 int launch_eval(magi_handle* h, int N, const double* Xh, const double* st, const double* bvec, double* r, double* Tq) {
     constexpr int D = DriftT<DRIFT>::D;
-    hipLaunchKernelGGL(k_ti_eval<DRIFT>, dim3((N * D + 255) / 256), dim3(256), 0, h->stream, N, Xh, st, bvec, r, Tq);
+    hipLaunchKernelGGL(k_ti_eval<DRIFT>, dim3((N * D + 255) / 256), dim3(256), 0, h->stream, N, Xh, st, bvec, r, Tq, (const double*)h->dTimes);
     return MAGI_OK;
 }
 
@@ -86,6 +89,8 @@ int magi_theta_init_device(magi_handle* h, int drift, int P, const double* Xhat,
     MAGI_DRIFT_DISPATCH(drift, MAGI_CALL);
 #undef MAGI_CALL
     if (needD != D || needP != P) return magi_fail(h, MAGI_E_BADARG, "drift expects D=" + std::to_string(needD) + ", P=" + std::to_string(needP));
+    if (magi_user_drift_time_dependent() && h->times_N != N)
+        return magi_fail(h, MAGI_E_STATE, "this drift depends on time: call magi_set_times with the " + std::to_string(N) + " times of the grid before magi_theta_init");
     // work space: Xh | xc | bvec | r | g1 | g2 (n each), Tq (P n), state (TI_COUNT), loss trace (iters)
     const size_t need = (size_t)6 * n + (size_t)P * n + TI_COUNT + (size_t)std::max(iters, 1);
     double* ws = magi_workspace(h, magi_handle::WS_TI, need);

@@ -1,5 +1,6 @@
-"""Two classic MAGI benchmark systems written the way a user of the reference writes ``f_vec`` (numpy in place of
-tf.*): used by the tests of the generic-drift path and pre-built by ``__graft_entry__.build()``."""
+"""Classic MAGI benchmark systems written the way a user of the reference writes ``f_vec`` (numpy in place of
+tf.*): used by the tests of the generic-drift path and pre-built by ``__graft_entry__.build()``.  ``EXAMPLES`` ignore their first
+argument; ``TIME_EXAMPLES`` are forced systems that use it."""
 import numpy as np
 
 
@@ -38,15 +39,43 @@ EXAMPLES = {"fhn": (fitzhugh_nagumo, 2, 3), "lotka_volterra": (lotka_volterra, 2
             "competition7": (competition_7, 2, 7)}
 
 
-def rk4(f_vec, x0, thetas, T, n, substeps=20):
-    """Reference trajectory on a uniform grid of n points over [0, T] (test data only)."""
+def seir_seasonal(t, X, thetas):
+    """SEIR with seasonal transmission (E, I, R; S = 1 - E - I - R implicit): beta(t) = beta (1 + a cos(pi t));  theta = (beta, gamma, sigma, a)."""
+    E, I, R = X[:, 0:1], X[:, 1:2], X[:, 2:3]
+    S = 1.0 - E - I - R
+    beta, gamma, sigma, a = (thetas[k] for k in range(4))
+    return np.concatenate([beta * (1.0 + a * np.cos(np.pi * t)) * S * I - sigma * E, sigma * E - gamma * I, gamma * I], axis=1)
+
+
+def fhn_forced(t, X, thetas):
+    """Periodically driven FitzHugh-Nagumo: V' = c (V - V^3/3 + R) + A cos(0.8 t),  R' = -(V - a + b R) / c;  theta = (a, b, c, A)."""
+    V, R = X[:, 0:1], X[:, 1:2]
+    a, b, c, A = (thetas[k] for k in range(4))
+    return np.concatenate([c * (V - V ** 3 / 3.0 + R) + A * np.cos(0.8 * t), -(V - a + b * R) / c], axis=1)
+
+
+def mm_infusion(t, X, thetas):
+    """Two compartments with a decaying infusion and saturable elimination:
+    x' = th0 e^{-0.3 t} - th1 x / (th2 + x) - th3 (x - y),  y' = th3 (x - y)."""
+    x, y = X[:, 0:1], X[:, 1:2]
+    return np.concatenate([thetas[0] * np.exp(-0.3 * t) - thetas[1] * x / (thetas[2] + x) - thetas[3] * (x - y), thetas[3] * (x - y)], axis=1)
+
+
+TIME_EXAMPLES = {"seir_seasonal": (seir_seasonal, 3, 4), "fhn_forced": (fhn_forced, 2, 4), "mm_infusion": (mm_infusion, 2, 4)}
+
+
+def rk4(f_vec, x0, thetas, T, n, substeps=20, grid=None):
+    """Reference trajectory on a uniform grid of n points over [0, T], or on ``grid`` (increasing times, its first the start): test data
+    only.  The drift is given the current time."""
     x = np.asarray(x0, dtype=np.float64)
     out = [x.copy()]
-    h = T / (n - 1) / substeps
-    f = lambda v: f_vec(None, v[None], thetas)[0]
-    for _ in range(n - 1):
-        for _ in range(substeps):
-            k1 = f(x); k2 = f(x + 0.5 * h * k1); k3 = f(x + 0.5 * h * k2); k4 = f(x + h * k3)
+    ts = np.linspace(0.0, T, n) if grid is None else np.asarray(grid, dtype=np.float64).reshape(-1)
+    f = lambda s, v: f_vec(np.array([[s]]), v[None], thetas)[0]
+    for i in range(len(ts) - 1):
+        h = T / (n - 1) / substeps if grid is None else (ts[i + 1] - ts[i]) / substeps
+        for j in range(substeps):
+            s = ts[i] + j * h
+            k1 = f(s, x); k2 = f(s + 0.5 * h, x + 0.5 * h * k1); k3 = f(s + 0.5 * h, x + 0.5 * h * k2); k4 = f(s + h, x + h * k3)
             x = x + h / 6.0 * (k1 + 2 * k2 + 2 * k3 + k4)
         out.append(x.copy())
-    return np.linspace(0.0, T, n), np.array(out)
+    return ts, np.array(out)

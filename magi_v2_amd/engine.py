@@ -44,6 +44,7 @@ _SYMBOLS = {
     "magi_last_error": (C.c_char_p, [C.c_void_p]),
     "magi_version": (C.c_char_p, []),
     "magi_user_drift_info": (C.c_int, [_ip, _ip]),
+    "magi_user_drift_time_dependent": (C.c_int, []),
     "magi_build_matrices": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp, C.c_double, C.c_int, _dp, _dp, _dp]),
     "magi_matern_blocks": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_double, C.c_double, C.c_double, _dp, _dp, _dp]),
     "magi_fit_hparams": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, C.c_double, C.c_int, C.c_double,
@@ -55,6 +56,7 @@ _SYMBOLS = {
     "magi_get_dense": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp]),
     "magi_dense_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp]),
     "magi_set_problem": (C.c_int, [C.c_void_p, _dp, _dp, _lp, _dp, C.c_int64, C.c_double, _dp, C.c_int, C.c_int]),
+    "magi_set_times": (C.c_int, [C.c_void_p, _dp, C.c_int]),
     "magi_logpost_grad": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "magi_logpost_grad_fused": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "magi_sampler_cfg_default": (None, [C.POINTER(SamplerCfg)]),
@@ -76,6 +78,7 @@ _SYMBOLS = {
     "magi_debug_par": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "magi_build_profile": (C.c_int, [C.c_void_p, _dp, _dp, _lp]),
     "magi_drift_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "magi_drift_probe_at": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
 }
 
 _libs = {}
@@ -149,6 +152,10 @@ class MagiEngine:
             self._lib = load_library()
         if user:
             self.user_drift = drift
+            if bool(self._lib.magi_user_drift_time_dependent()) != bool(getattr(drift, "time_dependent", False)):
+                raise ValueError(f"library {self._lib._name} was built for a drift that "
+                                 f"{'uses' if self._lib.magi_user_drift_time_dependent() else 'does not use'} t; drift '{drift.name}' "
+                                 f"{'does' if drift.time_dependent else 'does not'}")
         self._h = self._lib.magi_create(int(device_id))
         if not self._h:
             raise MagiHipError(-2, self._lib.magi_last_error(None).decode())
@@ -185,11 +192,12 @@ class MagiEngine:
             value = self._FAMILIES[value]
         self._check(self._lib.magi_set_option(self._h, name.encode(), int(value)))
 
-    def drift_probe(self, drift, X, th, g=None, path=0):
+    def drift_probe(self, drift, X, th, g=None, path=0, t=None):
         """This library's drift code by itself at the points X[n, D] (magi_drift_probe): (f[n, D], c[n, D], t[n, P]) with c_k = sum_d g_d
         df_d/dx_k and t_p = sum_d g_d df_d/dtheta_p through path 0 (DriftT::f / jt) or 1 (the runtime-switch entries); (f, None, None)
         through path 2 (the separable members; MagiHipError when the drift has none) or 3 (DriftT::f1).  ``th``: the parameters as the
-        drift sees them.  ``drift``: built-in name, or the Drift this engine was created for."""
+        drift sees them.  ``drift``: built-in name, or the Drift this engine was created for.  ``t``: the time of every point, [n]
+        (magi_drift_probe_at); None: all at time 0."""
         if isinstance(drift, str):
             (D, P), drift_id = DRIFT_SHAPES[drift], DRIFT_IDS[drift]
         else:
@@ -200,9 +208,13 @@ class MagiEngine:
         deriv = int(path) in (0, 1)
         g = _f64(np.zeros((n, D)) if g is None else g, (n, D)) if deriv else None
         f = np.empty((n, D))
-        c, t = (np.empty((n, D)), np.empty((n, P))) if deriv else (None, None)
-        self._check(self._lib.magi_drift_probe(self._h, drift_id, P, int(path), n, _ptr(X), _ptr(th), _ptr(g), _ptr(f), _ptr(c), _ptr(t)))
-        return f, c, t
+        c, tt = (np.empty((n, D)), np.empty((n, P))) if deriv else (None, None)
+        if t is None:
+            self._check(self._lib.magi_drift_probe(self._h, drift_id, P, int(path), n, _ptr(X), _ptr(th), _ptr(g), _ptr(f), _ptr(c), _ptr(tt)))
+        else:
+            times = _f64(np.asarray(t, dtype=np.float64).reshape(-1), (n,))
+            self._check(self._lib.magi_drift_probe_at(self._h, drift_id, P, int(path), n, _ptr(X), _ptr(th), _ptr(g), _ptr(f), _ptr(c), _ptr(tt), _ptr(times)))
+        return f, c, tt
 
     def selftest(self, drift=None, force=False):
         """Self-test of the library this engine runs (magi_v2_amd.selftest.ensure: cached verdict, or a run on handles of its own);
@@ -305,6 +317,12 @@ class MagiEngine:
         self.N, self.D = N, D
 
     # -- problem --------------------------------------------------------------------------------
+    def set_times(self, I):
+        """The times of the grid points ([N] or [N, 1]; magi_set_times), after the matrices: what a drift that uses ``t`` is evaluated at --
+        the reference passes its grid ``self.I``.  Required before ``set_problem`` / ``theta_init`` for such a drift, harmless otherwise."""
+        I = _f64(np.asarray(I, dtype=np.float64).reshape(-1))
+        self._check(self._lib.magi_set_times(self._h, _ptr(I), I.shape[0]))
+
     def set_problem(self, mu, N_ds, obs_idx, y, beta, LB, drift):
         """``drift``: built-in name, or the Drift this engine was created for."""
         D = self.D

@@ -169,11 +169,13 @@ def _normalised_error(got: np.ndarray, want: np.ndarray) -> float:
 
 
 def _check_drift(eng, drift, pr) -> List[Check]:
-    """magi_drift_probe against the host evaluators of the trace the header was printed from."""
+    """magi_drift_probe against the host evaluators of the trace the header was printed from; a drift that uses t is probed at N_PROBE
+    random times inside the synthetic grid's range (magi_drift_probe_at), any other exactly as before."""
     from .engine import MagiHipError
     X, th, g = pr["probe_X"], pr["probe_th"], pr["probe_g"]
-    f_want = np.asarray(drift.f_np(None, X, th), dtype=np.float64)
-    J, T = drift.jac_np(X, th)
+    tt = probe_times(pr) if getattr(drift, "time_dependent", False) else None
+    f_want = np.asarray(drift.f_np(tt, X, th), dtype=np.float64)
+    J, T = drift.jac_np(X, th, tt)
     c_want = np.einsum("nd,ndk->nk", g, J)
     t_want = np.einsum("nd,ndp->np", g, T)
     out = []
@@ -183,7 +185,7 @@ def _check_drift(eng, drift, pr) -> List[Check]:
         by, detail = {}, ""
         try:
             for label, path, wants in parts:
-                got = eng.drift_probe(drift, X, th, g, path)
+                got = eng.drift_probe(drift, X, th, g, path, t=tt)
                 for what, a, b in zip(("f", "c", "t"), got, wants):
                     if b is not None:
                         by[f"{label}.{what}"] = _normalised_error(a, b)
@@ -198,6 +200,12 @@ def _check_drift(eng, drift, pr) -> List[Check]:
     if _separable(drift):          # (a library that disagrees answers MAGI_E_BADARG: the check fails)
         one("drift.sep", [("path2", 2, (f_want, None, None))])
     return out
+
+
+def probe_times(pr) -> np.ndarray:
+    """The times a time-dependent drift is probed at: N_PROBE draws from the range of the synthetic grid, a generator of their own (the
+    synthetic problem of every other library stays what it was)."""
+    return np.random.default_rng(162).uniform(pr["I"][0], pr["I"][-1], N_PROBE)
 
 
 def _separable(drift) -> bool:
@@ -224,6 +232,8 @@ def _engine(lib_path, device, drift, pr, family="auto"):
     try:
         eng.set_option("stream_family", family)
         eng.build_matrices(pr["I"], pr["phi1s"], pr["phi2s"], float(pr["nu"]), bandsize=None, want_host=False)
+        if getattr(drift, "time_dependent", False):        # the synthetic grid is the times the drift is evaluated at
+            eng.set_times(pr["I"])
         eng.set_problem(pr["mu"], pr["N_ds"], pr["obs_idx"], pr["y"], float(pr["beta"]), pr["LB"], drift)
     except Exception:
         eng.close()

@@ -42,6 +42,7 @@ def drive(gpu: bool):
     assert lib.magi_version().startswith(b"magi_hip")
     d, p = C.c_int32(0), C.c_int32(0)
     assert lib.magi_user_drift_info(C.byref(d), C.byref(p)) == 0 and lib.magi_user_drift_info(None, None) == 0
+    assert lib.magi_user_drift_time_dependent() == 0
     # every int-returning entry point refuses a NULL handle (MAGI_E_BADARG) without touching anything
     n_null = 0
     for name, (res, args) in E._SYMBOLS.items():
@@ -72,7 +73,13 @@ def drive(gpu: bool):
     g = load_g4("seir4_N81")
     pr = problem_from_g4(g, 20)
     eng = engine_for(pr, 20)
-    for bad in (lambda: eng.set_option("no_such_option", 1), lambda: eng.set_option("potrf_panels", 99), lambda: eng.sampler_run(1),
+    eng.set_times(g["I"])                      # (stored and ignored by a library whose drift does not use t)
+    x1, th1 = np.full((1, 4), 0.2), np.ones(3)
+    eng.drift_probe("seir4", x1, th1, np.ones((1, 4)), 0, t=[0.5])
+    for bad in (lambda: eng.set_times(g["I"][:-1]), lambda: eng.set_times(np.full(pr.N, np.nan)),
+                lambda: eng._check(eng._lib.magi_set_times(eng._h, None, pr.N)),
+                lambda: eng._check(eng._lib.magi_drift_probe_at(eng._h, 1, 3, 0, 1, None, None, None, None, None, None, None)),
+                lambda: eng.set_option("no_such_option", 1), lambda: eng.set_option("potrf_panels", 99), lambda: eng.sampler_run(1),
                 lambda: eng._check(eng._lib.magi_sampler_profile(eng._h, 1, None, None, None)),
                 lambda: eng._check(eng._lib.magi_dense_apply(eng._h, 7, 0, 1, None, None))):
         try:
