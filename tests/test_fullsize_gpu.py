@@ -18,7 +18,9 @@ from N = 4096 on, `MAGI_GEMM_REMAP_MIN=1` forces it on every launch):
          host truth with the order forced and 2 / 8 panels per block column), test_config5_build_outputs_against_matern_columns
          (N = 8192, the order as it runs in production, truth = oracle Matern columns);
   <7> single-phase operators E = Ks M, H = M^T E + Cs: the fused vs three-phase log posterior at N = 1024 .. 8192
-      (test_full_size_logpost_consistency_and_gradient) and bit-identity of the fused log posterior under the forced order."""
+      (test_full_size_logpost_consistency_and_gradient) and bit-identity of the fused log posterior under the forced order -- both on Matern
+      matrices, whose far blocks have no effect; against the oracle on matrices where every block counts, plain and forced order:
+      tests/test_structureless_gpu.py."""
 import os
 
 import numpy as np
