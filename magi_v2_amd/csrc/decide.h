@@ -310,7 +310,7 @@ __device__ __forceinline__ void decide_block(const DevProblem& pb, const DevChai
             c.sub_weight = wsum_leaf;
             const bool cont_tree = hmc || (not_divergent && (c.cont != 0));
             c.cont = (no_u && cont_tree) ? 1 : 0;
-            c.nd = (c.nd && not_divergent) ? 1 : 0;
+            c.nd = ((hmc || c.nd) && not_divergent) ? 1 : 0;          // (HMC tests the END state only: an inner leaf's energy error is no divergence)
             if (cont_tree) c.e_sum_sub += shs[19];
             c.sub_lf += 1;
             c.it = it + 1;

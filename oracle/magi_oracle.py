@@ -726,8 +726,25 @@ class NutsResult:
 
 
 def nuts_one_step(q, cur_target, cur_grad, step_size, temp, fn_L, step, chain, key,
-                  max_tree_depth=10, max_energy_diff=1000.0) -> NutsResult:
+                  max_tree_depth=10, max_energy_diff=1000.0, events=None) -> NutsResult:
     """One NUTS transition, TFP-style (iterative doubling, multinomial, generalised U-turn).
+
+    ``events``: a ``collections.Counter`` (or None) that receives a census of the branches this transition takes.  Recording only:
+    no arithmetic and no control flow depends on it.  Keys (tuples):
+      ("check", k) / ("check_fail", k)   sub-tree U-turn checks of level k (span 2^k leaves) evaluated / answering "U-turn"; a check
+                                         behind a failed lower level of the same leaf is not evaluated (``and`` short-circuits), hence
+                                         not counted
+      ("u_end", k, last)                 a subtree ended by a U-turn check alone (the leaf did not diverge); k the lowest failing level,
+                                         last = the leaf was the subtree's last
+      ("div", it, depth)                 a divergent leaf: its index in the subtree, the subtree's depth
+      ("nan",)                           a NaN energy
+      ("wasted_accept", depth, acc)      a rejected subtree of that depth one of whose leaves had been accepted as its proposal (its
+                                         first leaf always is); acc = the transition had already accepted a proposal, which must survive
+      ("merge_not_chosen", depth)        a valid subtree that lost the merge draw
+      ("traj_u", depth)                  a trajectory-level U-turn after the merge of the subtree of that depth
+      ("max_depth", depth)               the transition ended by the depth cap
+      ("div_accepted",)                  a transition with has_divergence and is_accepted both set
+      ("depth", d)                       a transition of final depth d
 
     ``fn_L(q) -> (L, grad L)`` is the UNtempered log posterior; the target of this step is
     ``temp * L``.  ``cur_target/cur_grad`` are the cached (possibly one-step-stale, see
@@ -758,6 +775,7 @@ def nuts_one_step(q, cur_target, cur_grad, step_size, temp, fn_L, step, chain, k
         cumsum = np.zeros(dim)
         e_sum, lf, cont, nd = 0.0, 0, True, not_div
         it = 0
+        sub_took_leaf = False
         while it < nsteps and cont:
             # leapfrog (identity mass)
             p_half = p + 0.5 * eps * grd
@@ -768,6 +786,7 @@ def nuts_one_step(q, cur_target, cur_grad, step_size, temp, fn_L, step, chain, k
             cumsum = cumsum + p
             lf += 1
             no_u = True
+            k_fail = 0                     # (census only: the lowest failing check level of this leaf)
             if it % 2 == 0:
                 slot = bin(it).count("1")
                 mem_p[slot], mem_rho[slot] = p, cumsum
@@ -776,11 +795,19 @@ def nuts_one_step(q, cur_target, cur_grad, step_size, temp, fn_L, step, chain, k
                 while (it + 1) % (1 << k) == 0 and (1 << k) <= nsteps:
                     left = it + 1 - (1 << k)
                     slot = bin(left).count("1")
+                    was = no_u
                     no_u = no_u and _has_not_u_turn(cumsum - mem_rho[slot], mem_p[slot], p)
+                    if events is not None and was:
+                        events[("check", k)] += 1
+                        if not no_u:
+                            events[("check_fail", k)] += 1
+                            k_fail = k
                     k += 1
             energy = tgt - 0.5 * np.dot(p, p)
             if np.isnan(energy):
                 energy = -np.inf
+                if events is not None:
+                    events[("nan",)] += 1
             ediff = energy - init_energy
             not_divergent = bool(-ediff < max_energy_diff)
             wsum = _logaddexp(sub["weight"], ediff)
@@ -789,9 +816,15 @@ def nuts_one_step(q, cur_target, cur_grad, step_size, temp, fn_L, step, chain, k
             leaf_ctr += 1
             if u <= thresh:
                 sub.update(q=x, L=Lx, gL=gLx, target=tgt, grad=grd, energy=energy)
+                sub_took_leaf = True
             sub["weight"] = wsum
             cont_tree = not_divergent and cont
             cont = no_u and cont_tree
+            if events is not None:
+                if not not_divergent:
+                    events[("div", it, depth)] += 1
+                elif not no_u and cont_tree:
+                    events[("u_end", k_fail, it == nsteps - 1)] += 1
             nd = nd and not_divergent
             if cont_tree:
                 e_sum += math.exp(min(ediff, 0.0))
@@ -802,6 +835,11 @@ def nuts_one_step(q, cur_target, cur_grad, step_size, temp, fn_L, step, chain, k
         thresh = tree_weight - cand["weight"]
         u = math.log1p(-rng_uniform(depth, step, chain, STREAM_MERGE, key))
         choose = bool(u <= thresh) and cont
+        if events is not None:
+            if sub_took_leaf and not cont:
+                events[("wasted_accept", depth, is_accepted)] += 1
+            if cont and not choose:
+                events[("merge_not_chosen", depth)] += 1
         if choose:
             cand.update(q=sub["q"], L=sub["L"], gL=sub["gL"], target=sub["target"],
                         grad=sub["grad"], energy=sub["energy"])
@@ -813,11 +851,19 @@ def nuts_one_step(q, cur_target, cur_grad, step_size, temp, fn_L, step, chain, k
         energy_diff_sum += e_sum
         leapfrog_count += lf
         continue_tree = cont and no_u_traj
+        if events is not None and cont and not no_u_traj:
+            events[("traj_u", depth)] += 1
         not_div = nd
         depth += 1
 
     with np.errstate(divide="ignore", invalid="ignore"):
         lar = float(np.log(np.float64(energy_diff_sum) / np.float64(leapfrog_count)))
+    if events is not None:
+        events[("depth", depth)] += 1
+        if continue_tree:
+            events[("max_depth", depth)] += 1
+        if is_accepted and not not_div:
+            events[("div_accepted",)] += 1
     return NutsResult(q=cand["q"], L=cand["L"], gL=cand["gL"], log_accept_ratio=lar,
                       leapfrogs=leapfrog_count, depth=depth, is_accepted=is_accepted,
                       reach_max_depth=continue_tree, has_divergence=not not_div,
@@ -904,12 +950,14 @@ def unpack(q, N, D, P):
     return X, q[N * D: N * D + D], q[N * D + D: N * D + D + P]
 
 
-def make_fn_L(pr: Problem):
+def make_fn_L(pr: Problem, logpost_grad_fn: Optional[Callable] = None):
+    """``fn(q) -> (L, grad L)`` on the packed state; ``logpost_grad_fn`` defaults to this module's ``logpost_grad``."""
     N, D, P = pr.N, pr.D, pr.P
+    lg = logpost_grad if logpost_grad_fn is None else logpost_grad_fn
 
     def fn(q):
         X, s, t = unpack(q, N, D, P)
-        L, gX, gs, gt = logpost_grad(np.ascontiguousarray(X), s, t, 1.0, pr)
+        L, gX, gs, gt = lg(np.ascontiguousarray(X), s, t, 1.0, pr)
         return L, pack(gX, gs, gt)
     return fn
 
@@ -917,20 +965,26 @@ def make_fn_L(pr: Problem):
 def sample_chain(pr: Problem, Xhat_init, sigma_sqs_init, thetas_init, num_results, num_burnin_steps,
                  seed: int, chain: int = 0, step_size: float = 0.1, target_accept_prob: float = 0.75,
                  max_tree_depth: int = 10, min_temp: float = 0.1, stale_cache: bool = True,
-                 anneal: bool = True, trace: Optional[list] = None, hmc_leapfrogs: Optional[int] = None):
+                 anneal: bool = True, trace: Optional[list] = None, hmc_leapfrogs: Optional[int] = None,
+                 max_energy_diff: float = 1000.0, num_adaptation_steps: Optional[int] = None, logpost_grad: Optional[Callable] = None,
+                 events=None):
     """The reference's ``predict`` sampling loop (magi_v2.py:357-396) around ``LogAnnealedNUTS``
     (magi_v2.py:852-879): at chain step k the target is ``beta_temp(k) * L`` with
     ``beta_temp(k) = max(1/ln(k+2), min_temp)``; NUTS is wrapped in dual averaging for the first
-    ``int(0.8*num_burnin_steps)`` steps.
+    ``int(0.8*num_burnin_steps)`` steps (``num_adaptation_steps=None``; an explicit count otherwise).
+
+    ``max_energy_diff`` goes to ``nuts_one_step`` / ``hmc_one_step``; ``logpost_grad`` (signature of this module's ``logpost_grad``)
+    replaces it inside ``make_fn_L``, so that another restatement of the log posterior -- the C port, oracle/logpost_c.py -- can drive
+    a chain; ``events``: the branch census of ``nuts_one_step``, summed over the chain's transitions.
 
     ``stale_cache=True`` keeps TFP's behaviour of reusing the previous step's cached
     target/gradient, which were computed at the previous temperature."""
     N, D, P = pr.N, pr.D, pr.P
     X0, s0, t0 = initial_state(Xhat_init, sigma_sqs_init, thetas_init, pr.LB)
     q = pack(X0, s0, t0)
-    fn_L = make_fn_L(pr)
+    fn_L = make_fn_L(pr, logpost_grad)
     L, gL = fn_L(q)
-    num_adapt = int(0.8 * num_burnin_steps)
+    num_adapt = int(0.8 * num_burnin_steps) if num_adaptation_steps is None else int(num_adaptation_steps)
     da = dual_averaging_init(step_size)
     total = num_burnin_steps + num_results
     out_q = np.zeros((num_results, q.shape[0]))
@@ -942,9 +996,10 @@ def sample_chain(pr: Problem, Xhat_init, sigma_sqs_init, thetas_init, num_result
         tc = temp_prev if stale_cache else temp
         if hmc_leapfrogs is None:
             res = nuts_one_step(q, tc * L, tc * gL, da.step_size, temp, fn_L, k, chain, seed,
-                                max_tree_depth=max_tree_depth)
+                                max_tree_depth=max_tree_depth, max_energy_diff=max_energy_diff, events=events)
         else:
-            res = hmc_one_step(q, tc * L, tc * gL, da.step_size, temp, fn_L, k, chain, seed, hmc_leapfrogs)
+            res = hmc_one_step(q, tc * L, tc * gL, da.step_size, temp, fn_L, k, chain, seed, hmc_leapfrogs,
+                               max_energy_diff=max_energy_diff)
         ss_used = da.step_size
         if res.is_accepted:            # a new state was accepted somewhere in the tree
             q, L, gL = res.q, res.L, res.gL

@@ -8,7 +8,7 @@ import numpy as np
 import pytest
 
 from oracle import magi_oracle as orc
-from tests.util import engine_for, load_g4, problem_from_g4
+from tests.util import ENERGY_TOL, engine_for, load_g4, problem_from_g4
 
 pytestmark = pytest.mark.gpu
 
@@ -49,6 +49,8 @@ def test_chain_matches_oracle_draw_for_draw(tag, band, stale):
     np.testing.assert_array_equal(diag.leapfrogs_taken[0], leap)
     np.testing.assert_array_equal(diag.has_divergence[0], [int(r.has_divergence) for _, r, _ in trace])
     np.testing.assert_array_equal(diag.is_accepted[0], [int(r.is_accepted) for _, r, _ in trace])
+    np.testing.assert_array_equal(diag.reach_max_depth[0], [int(r.reach_max_depth) for _, r, _ in trace])
+    np.testing.assert_allclose(diag.energy[0], [r.energy for _, r, _ in trace], rtol=ENERGY_TOL[0], atol=ENERGY_TOL[1])   # (tests/util.py: how it is derived)
     assert lf == leap.sum()
     ss = np.array([s for _, _, s in trace])
     np.testing.assert_allclose(diag.step_size[0], ss, rtol=1e-9)
@@ -356,6 +358,9 @@ def test_deep_trees_match_oracle_draw_for_draw_in_every_kernel_family(tag, chain
         np.testing.assert_array_equal(d.tree_depth[i], [r.depth for _, r, _ in trace])
         np.testing.assert_array_equal(d.leapfrogs_taken[i], [r.leapfrogs for _, r, _ in trace])
         np.testing.assert_array_equal(d.is_accepted[i], [int(r.is_accepted) for _, r, _ in trace])
+        np.testing.assert_array_equal(d.has_divergence[i], [int(r.has_divergence) for _, r, _ in trace])
+        np.testing.assert_array_equal(d.reach_max_depth[i], [int(r.reach_max_depth) for _, r, _ in trace])
+        np.testing.assert_allclose(d.energy[i], [r.energy for _, r, _ in trace], rtol=ENERGY_TOL[0], atol=ENERGY_TOL[1])
         np.testing.assert_allclose(d.target_log_prob[i], [r.target_log_prob for _, r, _ in trace], rtol=1e-8)
         np.testing.assert_allclose(Xs[i], oX, rtol=0, atol=1e-8 * np.abs(oX).max())
         np.testing.assert_allclose(tp[i], otp, rtol=1e-7, atol=1e-9)

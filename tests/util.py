@@ -143,3 +143,172 @@ def structureless_states(pr, X, n, seed):
     sp = STRUCTURELESS_SIG_PRE + 0.3 * rng.standard_normal((n, pr.D))
     tp = np.log(np.expm1(structureless_theta(pr.drift)))[None] + 0.05 * rng.standard_normal((n, pr.P))
     return Xb, sp, tp
+
+
+# ---- the NUTS state machine, branch by branch -------------------------------------------------------------------------------------
+# One table of sampler configurations for tests/test_sampler_branches_cpu.py (which PROVES, with the oracle's census, that every case
+# takes the branches it is listed for, that a device deciding them wrongly would show, and that no decision of a case sits on a rounding
+# knife-edge) and tests/test_sampler_branches_gpu.py (which runs every case on the device, draw for draw against the oracle).
+#
+# Every case: theta_0 = 1 and the fixture's initial state, stale cache off, chain ids BRANCH_CHAINS (the census and the claims are chain
+# 20's; chain 21 is the last chain of every batch and is compared too).  `cfg`: the device's magi_sampler_cfg fields.
+#
+# Per case, measured on the CPU (numpy oracle; chain 20): depths of the transitions | census entries that justify the claims | largest
+# numpy-vs-C-port discrepancy over chains 20 and 21 as a fraction of the GPU tolerance of the worst field (bound: 1e-2) and of `energy`
+# in absolute terms.  Integer diagnostics are identical between the two CPU runs in every case.
+#
+#   case                depths (chain 20)             census entries behind the claims                                  worst fraction       |d energy|
+#   u_last              3 1 3 5 7 7 6                 u_end(5, last) 1; max_depth(7) 1; wasted_accept(5, acc) 1           2.7e-3 log_accept    4.4e-11
+#   u_early_l2          1 1 3 4 7 6 5                 u_end(2, early) 1; max_depth(7) 1                                   1.4e-4 log_accept    5.2e-12
+#   u_early_l4          1 1 2 3 6 7 6                 u_end(4, early) 1; wasted_accept(5, acc) 1                          3.6e-4 target        2.3e-11
+#   u_early_l3 (b = 5)  1 1 1 3 4 4 6                 u_end(3, early) 1, u_end(3, last) 1; wasted_accept(3 / 5, acc)      3.2e-6 log_accept    1.4e-12
+#   u_early_l5_depth8   5 3 5 7 8 8 8                 u_end(3, early) 1, u_end(5, early) 1, u_end(7, last) 1;             5.3e-3 step_size     7.7e-10
+#                                                     check(7) 2 of which 1 fails; cap 12; wasted_accept(4 / 7, acc) 3
+#   depth9              7 2 7 9 7 7 7                 511 leapfrogs; check(7) 4+, check(8) 1+, none fails                 5.5e-3 step_size     3.2e-9
+#   depth10_fixed_step  10 8 8 8                      1023 leapfrogs; check(7), check(8), check(9) 1; cap 12              3.6e-3 log_accept    5.4e-10
+#   div_mid             1 1 1 3 1 1 1                 div(leaf 2, depth 2) 1; div_accepted 1; wasted_accept(2, acc) 1     7.2e-4 step_size     2.0e-12
+#   div_mid_seir3 (b20) 1 1 1 3 1 1 1                 div(leaf 1, depth 2) 1; div_accepted 1; wasted_accept(2, acc) 1     6.3e-3 step_size     2.4e-11
+#   max_depth_1         1 1 1 1 1 1 1                 max_depth(1) 5, every transition one leaf                           1.8e-3 step_size     4.6e-11
+#   min_temp            2 1 2 4 5 6 5 6 6             9 transitions, 1/ln(k+2) < 0.5 from k = 6; u_end(3, early) 2,       7.1e-4 target        1.9e-11
+#                                                     u_end(4, early) 1; wasted_accept(4 / 5, acc) 3
+#   anneal_off          4 1 6 6 6 6 6                 beta_temp = 1                                                       7.1e-3 log_accept    1.6e-9
+#   target_accept       1 1 1 5 5 5 5                 step_size leaves the 0.75 run's at transition 1                     3.1e-3 step_size     3.9e-9
+#   adapt_0 / 2 / all   1.. / 4 1 6.. / 2 1 1 4 5 6 6 5   step_size: at-boundary then frozen / before, at, frozen / before    0 / 2.6e-4 / 7.0e-4  <= 3.3e-11
+#   hmc_div             (L = 8)                       a step with u <= ediff rejected because -ediff >= 0.2               3.6e-3 step_size     1.3e-10
+#   u_early_member2     1 1 3 4 7 6 4                 u_end(2, early) 1; max_depth(7) 1 (second member of the group)      5.5e-5 target        1.7e-11
+#
+# Checkpoint levels 10 and 11 stay unreached (a level-10 check needs a transition of >= 2047 leapfrogs), as do NaN energies.
+#
+BRANCH_CHAINS = (20, 21)
+
+# tolerances of the device-vs-oracle comparison, (rtol, atol); X: atol = 1e-8 max|X|.  Those of
+# test_deep_trees_match_oracle_draw_for_draw_in_every_kernel_family / test_chain_matches_oracle_draw_for_draw (tests/test_sampler_gpu.py).
+BRANCH_TOL = {"step_size": (1e-9, 0.0), "log_accept_ratio": (1e-7, 1e-9), "target_log_prob": (1e-8, 0.0), "X": (0.0, 1e-8),
+              "sig_pre": (1e-7, 1e-9), "th_pre": (1e-7, 1e-9)}
+# `energy` has no earlier tolerance.  Largest |energy_numpy - energy_C| over the table (both chains): 3.9e-9 (target_accept, |energy| ~ 9.4e3);
+# ENERGY_CPU_DISCREPANCY bounds it (tests/test_sampler_branches_cpu.py asserts that per case); atol = 100 x that (a third summation order, and the leapfrog amplification the
+# other fields' tolerances already allow) next to rtol 1e-8.
+ENERGY_CPU_DISCREPANCY = 4e-9
+ENERGY_TOL = (1e-8, 100.0 * ENERGY_CPU_DISCREPANCY)
+
+
+class BranchCase:
+    def __init__(self, name, tag, band, seed, cfg, claims, burnin=4, results=3, variant=None, batches=(1, 2, 3)):
+        self.name, self.tag, self.band, self.seed, self.cfg, self.claims = name, tag, band, seed, dict(cfg), tuple(claims)
+        self.burnin, self.results, self.variant, self.batches = burnin, results, variant, tuple(batches)
+
+    def __repr__(self):
+        return self.name
+
+
+_DEEP = dict(step_size=2e-3, max_tree_depth=6)
+BRANCH_CASES = [
+    BranchCase("u_last", "sirw_N41", None, 808, dict(step_size=2e-3, max_tree_depth=7), ('u_last_high', 'max_depth_7', 'wasted_accept')),
+    BranchCase("u_early_l2", "sirw_N41", None, 808, dict(step_size=1e-2, max_tree_depth=7), ('u_early_12', 'max_depth_7'), batches=(1, 2, 3, 9)),
+    BranchCase("u_early_l4", "sirw_N41", None, 5, dict(step_size=1e-2, max_tree_depth=7), ('u_early_34', 'wasted_accept')),
+    BranchCase("u_early_l3", "sirw_N41", 5, 5, dict(step_size=3e-2, max_tree_depth=7), ('u_early_34', 'wasted_accept')),
+    BranchCase("u_early_l5_depth8", "sirw_N41", None, 808, dict(step_size=1.2e-4, max_tree_depth=12), ('u_early_34', 'u_early_high', 'u_last_high', 'fail_ge_7', 'depth_cap_12', 'wasted_accept')),
+    BranchCase("depth9", "seir4_N81", None, 17, dict(step_size=2e-4, max_tree_depth=10), ('depth_ge_9', 'checks_7_8')),
+    BranchCase("depth10_fixed_step", "seir4_N81", None, 7, dict(step_size=1.6e-5, max_tree_depth=12, num_adaptation_steps=0), ('depth_ge_9', 'depth_ge_10', 'checks_7_8', 'check_9', 'depth_cap_12'), burnin=2, results=2),
+    BranchCase("div_mid", "seir4_N81", None, 5, dict(step_size=3e-2, max_tree_depth=7, max_energy_diff=1.0), ('div_mid', 'div_accepted', 'wasted_accept'), batches=(1, 2, 3, 9)),
+    BranchCase("div_mid_seir3", "seir3_N161", 20, 7, dict(step_size=3.75e-3, max_tree_depth=7, max_energy_diff=0.1), ('div_mid', 'div_accepted', 'wasted_accept')),
+    BranchCase("max_depth_1", "seir3_N161", None, 7, dict(step_size=3e-3, max_tree_depth=1), ('max_depth_1',)),
+    BranchCase("min_temp", "sirw_N41", None, 808, dict(_DEEP, step_size=2.5e-3, min_temp=0.5), ('min_temp_binds', 'u_early_34', 'wasted_accept'), burnin=5, results=4),
+    BranchCase("anneal_off", "seir4_N81", None, 808, dict(_DEEP, anneal=0), ('anneal_off',)),
+    BranchCase("target_accept", "seir3_N161", None, 808, dict(_DEEP, step_size=3e-3, target_accept_prob=0.6), ('target_accept_0.6',)),
+    BranchCase("adapt_0", "seir3_N161", None, 808, dict(_DEEP, num_adaptation_steps=0), ('adapt_0',), burnin=5),
+    BranchCase("adapt_2", "seir4_N81", None, 808, dict(_DEEP, num_adaptation_steps=2), ('adapt_2',), burnin=5),
+    BranchCase("adapt_all", "sirw_N41", None, 7, dict(_DEEP, step_size=3e-3, num_adaptation_steps=20), ('adapt_all', 'wasted_accept'), burnin=5),
+    BranchCase("hmc_div", "seir4_N81", None, 7, dict(step_size=2.5e-4, mode=1, hmc_leapfrogs=8, max_energy_diff=0.2), ('hmc_div_reject',), burnin=5),
+    BranchCase("u_early_member2", "sirw_N41", None, 808, dict(step_size=1e-2, max_tree_depth=7), ('u_early_12', 'max_depth_7'), variant=(1.02, 1.05), batches=()),
+]
+
+
+def branch_case(name):
+    return next(c for c in BRANCH_CASES if c.name == name)
+
+
+def branch_problem(case):
+    """(fixture, orc.Problem with the reference's band mask, unmasked orc.Problem) of a case; `variant` = (y factor, K^-1 factor): another
+    problem of the same shape (a second member for a problem group)."""
+    import dataclasses
+    g = load_g4(case.tag)
+    prs = [problem_from_g4(g, case.band), problem_from_g4(g, None)]
+    if case.variant is not None:
+        ys, ks = case.variant
+        prs = [dataclasses.replace(p, y=p.y * ys, K_inv=p.K_inv * ks) for p in prs]
+    return g, prs[0], prs[1]
+
+
+def c_port_logpost_grad(X, sig_pre, th_pre, beta_temp, pr):
+    """oracle/logpost_c.py behind the signature of orc.logpost_grad: an independent summation order of the same function."""
+    from oracle import logpost_c
+    lp, _, gX, gs, gt = logpost_c.logpost_grad(X, sig_pre, th_pre, beta_temp, pr)
+    return lp, gX, gs, gt
+
+
+def branch_oracle_kwargs(case):
+    """The arguments of orc.sample_chain that restate the case's device cfg."""
+    kw = dict(stale_cache=False)
+    for k, v in case.cfg.items():
+        if k in ("step_size", "max_tree_depth", "max_energy_diff", "target_accept_prob", "min_temp", "num_adaptation_steps"):
+            kw[k] = v
+        elif k == "anneal":
+            kw[k] = bool(v)
+        elif k == "hmc_leapfrogs":
+            kw[k] = v
+        elif k != "mode":
+            raise KeyError(k)
+    assert ("hmc_leapfrogs" in case.cfg) == (case.cfg.get("mode", 0) == 1)
+    return kw
+
+
+_branch_runs = {}
+
+
+def branch_oracle_run(case, chain, port="numpy"):
+    """(sample_chain's output, trace, census) of one chain of a case, computed once per session and shared: treat it as read-only."""
+    import collections
+    key = (case.name, chain, port)
+    if key not in _branch_runs:
+        g, pr, _ = branch_problem(case)
+        trace, events = [], collections.Counter()
+        out = orc.sample_chain(pr, g["Xhat_init"], g["sigma_sqs_init"], np.ones(pr.P), case.results, case.burnin, seed=case.seed, chain=chain,
+                               trace=trace, events=events, logpost_grad=c_port_logpost_grad if port == "c" else None,
+                               **branch_oracle_kwargs(case))
+        _branch_runs[key] = (out, trace, events)
+    return _branch_runs[key]
+
+
+def _u_end(ev, levels, last):
+    return any(k[0] == "u_end" and k[1] in levels and k[2] == last for k in ev)
+
+
+HIGH = range(5, 13)
+# branch -> predicate(case, census of chain 20, its trace): is the branch taken?  Every key must be claimed by a case (asserted).
+BRANCHES = {
+    "u_early_12": lambda c, ev, tr: _u_end(ev, (1, 2), False),              # a subtree ended before its last leaf by a level-1/2 check
+    "u_early_34": lambda c, ev, tr: _u_end(ev, (3, 4), False),              # ... by a level-3/4 check (levels 1, 2 passing)
+    "u_early_high": lambda c, ev, tr: _u_end(ev, HIGH, False),              # ... by a level >= 5 check alone (levels 1-4 passing)
+    "u_last_high": lambda c, ev, tr: _u_end(ev, HIGH, True),                # a level >= 5 check fails at the subtree's last leaf
+    "depth_ge_9": lambda c, ev, tr: any(r.depth >= 9 for _, r, _ in tr),
+    "depth_ge_10": lambda c, ev, tr: any(r.depth >= 10 for _, r, _ in tr),
+    "checks_7_8": lambda c, ev, tr: ev[("check", 7)] > 0 and ev[("check", 8)] > 0,
+    "check_9": lambda c, ev, tr: ev[("check", 9)] > 0,                      # (levels 10, 11 need 2047 leapfrogs in one transition: unreached)
+    "fail_ge_7": lambda c, ev, tr: any(ev[("check_fail", k)] > 0 for k in range(7, 13)),
+    "div_mid": lambda c, ev, tr: c.cfg.get("max_energy_diff", 1000.0) < 1000 and any(k[0] == "div" and k[1] > 0 and k[2] >= 2 for k in ev),
+    "div_accepted": lambda c, ev, tr: ev[("div_accepted",)] > 0,
+    "max_depth_7": lambda c, ev, tr: c.cfg.get("max_tree_depth") == 7 and ev[("max_depth", 7)] > 0,
+    "max_depth_1": lambda c, ev, tr: c.cfg.get("max_tree_depth") == 1 and ev[("max_depth", 1)] > 0 and all(r.leapfrogs == 1 for _, r, _ in tr),
+    "depth_cap_12": lambda c, ev, tr: c.cfg.get("max_tree_depth") == 12,
+    "wasted_accept": lambda c, ev, tr: any(k[0] == "wasted_accept" and k[1] >= 1 and k[2] for k in ev),  # (>= 2 leaves, a proposal to keep)
+    "min_temp_binds": lambda c, ev, tr: c.cfg.get("min_temp") == 0.5 and len(tr) >= 8 and 1.0 / np.log(len(tr) - 1 + 2.0) < 0.5,
+    "anneal_off": lambda c, ev, tr: c.cfg.get("anneal") == 0,
+    "target_accept_0.6": lambda c, ev, tr: c.cfg.get("target_accept_prob") == 0.6,
+    "adapt_0": lambda c, ev, tr: c.cfg.get("num_adaptation_steps") == 0 and c.burnin >= 5,
+    "adapt_2": lambda c, ev, tr: c.cfg.get("num_adaptation_steps") == 2 and c.burnin >= 5,
+    "adapt_all": lambda c, ev, tr: c.cfg.get("num_adaptation_steps", -1) >= c.burnin + c.results and c.burnin >= 5,
+    "hmc_div_reject": lambda c, ev, tr: c.cfg.get("mode") == 1 and any(
+        r.has_divergence and not r.is_accepted and np.log1p(-orc.rng_uniform(0, k, BRANCH_CHAINS[0], orc.STREAM_MERGE, c.seed)) <= r.log_accept_ratio
+        for k, r, _ in tr),                                                 # (u <= ediff <=> u <= min(ediff, 0): only divergence rejects it)
+}
