@@ -71,7 +71,8 @@ const char* magi_version(void);
  * m = p_Kappa Kappa^-1, K = Kappa_pp - p_Kappa Kappa^-1 Kappa_p, C^-1, K^-1, band mask.
  * bandsize < 0 means dense.  The results stay resident on the device for the log-posterior
  * and sampler calls; C_inv / m / K_inv ([D][N][N] row-major host buffers) may each be NULL
- * when the caller does not want a host copy. */
+ * when the caller does not want a host copy.  I need not be sorted for the dense outputs (row / column i belongs to I[i]);
+ * `bandsize` and the banded packing assume a sorted grid. */
 int magi_build_matrices(magi_handle* h, const double* I, int N, int D,
                         const double* phi1, const double* phi2, double nu, int bandsize,
                         double* C_inv, double* m, double* K_inv);
@@ -83,13 +84,15 @@ int magi_build_matrices(magi_handle* h, const double* I, int N, int D,
  * 1000 sqrt(D) / sd_phi2 sqrt(D)).  X_filled[N][D] row-major (no NaN), mu[D] the GP means (magi_v2.py:559).
  * phi1 / phi2 / sigma_sq hold the starting values on entry (magi_v2.py:631-639) and the fitted values on return.
  * Every step is Matern assembly + Cholesky + inverse + trace terms on the GPU; loss_trace[num_iters] may be NULL.
- * jitter: TFP's GaussianProcess default 1e-6. */
+ * jitter: TFP's GaussianProcess default 1e-6.  I need not be sorted (row n of X_filled belongs to I[n]); priors and starting values are
+ * the caller's. */
 int magi_fit_hparams(magi_handle* h, const double* I, int N, int D, const double* X_filled, const double* mu,
                      const double* mu_phi2, const double* sd_phi2, const double* sigma_sq_loc, double nu,
                      int num_iters, double learning_rate, double jitter,
                      double* phi1, double* phi2, double* sigma_sq, double* loss_trace);
 
-/* The three Matern blocks alone (magi_v2.py:781-815) for one component; host outputs [N][N]. */
+/* The three Matern blocks alone (magi_v2.py:781-815) for one component; host outputs [N][N].  I need not be sorted: every entry
+ * is a function of (I[i], I[j]) alone, so a permuted grid gives the permuted blocks bit for bit. */
 int magi_matern_blocks(magi_handle* h, const double* I, int N, double phi1, double phi2, double nu,
                        double* Kappa, double* p_Kappa, double* Kappa_pp);
 

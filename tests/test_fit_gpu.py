@@ -59,6 +59,59 @@ def test_single_adam_step_equals_oracle(data):
     eng.close()
 
 
+_multi_block = {}
+
+
+def multi_block_fit_truth():
+    """The fit on more than one Cholesky block: N = 300 (three block rows, the last ragged), the first two components of the synthetic SEIR
+    rows.  Returns (I, X, perm, priors, initial values, {k: (oracle result, oracle loss trace)} for k = 1 and 8 Adam steps) -- priors,
+    initial values and truth all from the SORTED rows: orc.fit_kernel_hparams derives the Fourier phi2 priors from the row order, so it is
+    not shuffle-invariant as a whole; everything after the priors is (tests/test_shuffled_grid_cpu.py, condition (e)).
+    Computed once and shared: read-only."""
+    if not _multi_block:
+        from magi_v2_amd import host
+        from tests.util import shuffled_grid
+        N = 300
+        I, X_obs, _, _ = host.synthetic_seir(N, seed=0)
+        X = host.linear_interpolate(X_obs)[:, :2]
+        perm = shuffled_grid(N, 5)[1]
+        pri = [orc.fourier_phi2_prior(X[:, d]) for d in range(2)]
+        init = orc.hparams_initial(X)
+        want = {}
+        for k in (1, 8):
+            trace = []
+            want[k] = (orc.fit_kernel_hparams(I, X, num_iters=k, trace=trace), np.array(trace))
+        _multi_block["v"] = (I, X, perm, pri, init, want)
+    return _multi_block["v"]
+
+
+@pytest.mark.parametrize("order,host_loop", [("sorted", 0), ("shuffled", 0), ("shuffled", 1)], ids=["sorted", "shuffled", "shuffled-host-loop"])
+def test_multi_block_fit_equals_oracle_sorted_and_shuffled(order, host_loop):
+    """magi_fit_hparams against the oracle where potrf panels and trtri levels run (N = 300), on the sorted rows and on the same rows in
+    shuffled order: there every 128-block of S^-1 carries the likelihood (on the sorted grid the blocks beyond the first neighbour are
+    zero to rounding; tests/test_shuffled_grid_cpu.py, condition (f)).  One Adam step moves each variable by lr along the gradient's sign,
+    eight steps carry its magnitudes, and the loss trace pins the likelihood itself at eight hyper-parameter points.  Bars: those of
+    test_single_adam_step_equals_oracle.  Both loops: the device-resident graph and the host loop share the kernels, not the graph."""
+    from magi_v2_amd.engine import MagiEngine
+    I, X, perm, pri, init, want = multi_block_fit_truth()
+    p = perm if order == "shuffled" else np.arange(len(I))
+    eng = MagiEngine(0)
+    try:
+        eng.set_option("fit_host_loop", host_loop)
+        for iters in (1, 8):
+            got = eng.fit_hparams(I[p], X[p], X.mean(axis=0), [q[0] for q in pri], [q[1] for q in pri], init["sigma_sqs"],
+                                  init["phi1s"], init["phi2s"], init["sigma_sqs"], num_iters=iters, want_trace=True)
+            res, trace = want[iters]
+            dev = max(np.abs(got[k] / res[k] - 1.0).max() for k in ("phi1s", "phi2s", "sigma_sqs"))
+            print(f"MULTI-BLOCK-FIT {order} host_loop={host_loop} iters={iters}: parameters {dev:.2e} (bar 1e-6), "
+                  f"loss trace {np.abs(got['loss'] / trace - 1.0).max():.2e} (bar 1e-8)")
+            for k in ("phi1s", "phi2s", "sigma_sqs"):
+                np.testing.assert_allclose(got[k], res[k], rtol=1e-6)
+            np.testing.assert_allclose(got["loss"], trace, rtol=1e-8)
+    finally:
+        eng.close()
+
+
 def test_fit_increases_the_marginal_likelihood(data):
     from magi_v2_amd.engine import MagiEngine
     I, X, g = data

@@ -11,6 +11,9 @@ cannot run there in seconds:
 Which test pins which GEMM class of csrc/build.hip (k_gemm_f64<CLS>; the XCD-aware super-block tile order switches on by itself
 from N = 4096 on, `MAGI_GEMM_REMAP_MIN=1` forces it on every launch):
   <2> potrf panels, <3> potrf rank-k updates, <4> trtri, <5> T^T T, <6> W^T / m / K_d products
+      -- all of the below on SORTED grids, where the factors are numerically block-bidiagonal and their far blocks have no effect; on grids
+         where every block counts (the same grid in shuffled order), plain and forced order, 1 to 4 panels, look-ahead:
+         tests/test_shuffled_grid_gpu.py and test_full_size_inverse_properties[2048-shuffled*] (conditions: tests/test_shuffled_grid_cpu.py);
       -- plain tile order:  test_full_size_inverse_properties[1024 / 2048] (dense host truth: C^-1 Kappa = I, m Kappa = p_Kappa,
          K^-1 K_ref = I), tests/test_build_gpu.py (mpmath / reference golden at small N);
       -- super-block order: test_remapped_tile_order_is_bit_identical_n2048 (every output equal BIT FOR BIT to the plain-order
@@ -27,7 +30,7 @@ import numpy as np
 import pytest
 
 from magi_v2_amd import host
-from tests.util import GOLDEN
+from tests.util import GOLDEN, shuffled_grid
 
 pytestmark = pytest.mark.gpu
 
@@ -132,20 +135,27 @@ def test_config5_sampler_runs_at_n8192():
     eng.close()
 
 
-@pytest.mark.parametrize("N,remap,panels,lookahead", [(1024, None, None, None), (2048, None, None, None), (2048, 1, 2, None), (2048, 1, 8, None), (2048, None, None, 1024),
-                                                      (2048, 1, 4, 1024)],
-                         ids=["1024", "2048", "2048-remap-2panels", "2048-remap-8panels", "2048-lookahead", "2048-remap-4panels-lookahead"])
-def test_full_size_inverse_properties(N, remap, panels, lookahead):
+@pytest.mark.parametrize("N,remap,panels,lookahead,shuffle", [(1024, None, None, None, False), (2048, None, None, None, False), (2048, 1, 2, None, False),
+                                                              (2048, 1, 8, None, False), (2048, None, None, 1024, False), (2048, 1, 4, 1024, False),
+                                                              (2048, None, None, None, True), (2048, 1, 4, 1024, True)],
+                         ids=["1024", "2048", "2048-remap-2panels", "2048-remap-8panels", "2048-lookahead", "2048-remap-4panels-lookahead",
+                              "2048-shuffled", "2048-shuffled-remap-4panels-lookahead"])
+def test_full_size_inverse_properties(N, remap, panels, lookahead, shuffle):
     """C^-1 Kappa = I, m Kappa = p_Kappa and K^-1 K_ref = I on random columns at BASELINE sizes; K_ref = Kappa_pp +
     p_Kappa Kappa^-1 p_Kappa is formed on the host from the GPU's Matern blocks (pinned against mpmath at small N).
     K^-1 is the worst-conditioned product of the build: Schur complement, second Cholesky, second inverse.
     remap / panels: the XCD-aware super-block tile order forced on every GEMM launch (it switches on by itself only above
     N = 4096), 2 / 4 / 8 panels per potrf block column instead of 3, and the factorisation's look-ahead (rank-k updates forked to the
     CU-masked side stream, on by itself from N = 4096) -- the code paths of the N = 8192 build at a size where the dense host truth is
-    affordable."""
+    affordable.
+    shuffle: the same grid in shuffled order (tests/util.py: shuffled_grid) -- same condition numbers, same bars, and a Cholesky factor in
+    which every block counts (tests/test_shuffled_grid_cpu.py), where the sorted grid's far blocks have no effect on any of the residuals."""
     from magi_v2_amd.engine import MagiEngine
     EPS = np.finfo(float).eps
     I = np.arange(N) * 0.025
+    if shuffle:
+        I, perm = shuffled_grid(N, 2048)
+        I = I[perm]
     eng = MagiEngine(0)
     if remap is not None:
         eng.set_option("gemm_remap_min", remap)

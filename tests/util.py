@@ -145,6 +145,20 @@ def structureless_states(pr, X, n, seed):
     return Xb, sp, tp
 
 
+# ---- shuffled grids: Matern problems in which every 128 x 128 block of the FACTORS matters -----------------------------------------
+# On a sorted grid the Cholesky factor of Kappa and its inverse are numerically block-bidiagonal, so the blocked factorisation, the
+# triangular inverse and the fit's S^-1 are only ever seen through their diagonal blocks and first neighbours
+# (tests/test_shuffled_grid_cpu.py measures it).  The same grid in shuffled order is legal input: the Matern blocks are element-wise
+# functions of (I_i, I_j) -- |I_i - I_j| and the sign of I_i - I_j -- and no build or fit entry point asks for sorted times (only
+# `bandsize` and the banded packing assume them).  Kappa(I[perm]) = P Kappa P^T has the eigenvalues, hence the condition number, of the
+# sorted matrix, so every conditioning-limited bar of the sorted tests applies unchanged -- while its Cholesky factor fills in completely.
+
+
+def shuffled_grid(N, seed, dt=0.025):
+    """(I_sorted, perm): the uniform grid of spacing dt and numpy.random.default_rng(seed).permutation(N); the shuffled grid is I_sorted[perm]."""
+    return np.arange(N) * dt, np.random.default_rng(seed).permutation(N)
+
+
 # ---- the NUTS state machine, branch by branch -------------------------------------------------------------------------------------
 # One table of sampler configurations for tests/test_sampler_branches_cpu.py (which PROVES, with the oracle's census, that every case
 # takes the branches it is listed for, that a device deciding them wrongly would show, and that no decision of a case sits on a rounding
