@@ -1,6 +1,6 @@
 """Classic MAGI benchmark systems written the way a user of the reference writes ``f_vec`` (numpy in place of
 tf.*): used by the tests of the generic-drift path and pre-built by ``__graft_entry__.build()``.  ``EXAMPLES`` ignore their first
-argument; ``TIME_EXAMPLES`` are forced systems that use it."""
+argument; ``TIME_EXAMPLES`` are forced systems that use it; ``DOMAIN_EXAMPLES`` are defined on part of the state space only (a square root, a logarithm)."""
 import numpy as np
 
 
@@ -62,6 +62,26 @@ def mm_infusion(t, X, thetas):
 
 
 TIME_EXAMPLES = {"seir_seasonal": (seir_seasonal, 3, 4), "fhn_forced": (fhn_forced, 2, 4), "mm_infusion": (mm_infusion, 2, 4)}
+
+
+def sqrt_outflow(t, X, thetas):
+    """Torricelli outflow from one tank into a second, leaky one: x' = -a sqrt(x),  y' = b sqrt(x) - c y;  theta = (a, b, c).
+    Defined for x >= 0 only.  Separable: coefficients a, b, c on the basis sqrt(x), y."""
+    x, y = X[:, 0:1], X[:, 1:2]
+    a, b, c = thetas[0], thetas[1], thetas[2]
+    return np.concatenate([-a * np.sqrt(x), b * np.sqrt(x) - c * y], axis=1)
+
+
+def gompertz_predation(t, X, thetas):
+    """Gompertz growth under predation: x' = a x log(K / x) - b x y,  y' = c x - b y;  theta = (a, K, b, c).
+    Defined for x > 0 only.  Not separable: log(K / x) mixes the state with the parameter K."""
+    x, y = X[:, 0:1], X[:, 1:2]
+    a, K, b, c = thetas[0], thetas[1], thetas[2], thetas[3]
+    return np.concatenate([a * x * np.log(K / x) - b * x * y, c * x - b * y], axis=1)
+
+
+# drifts with a limited domain: a leapfrog step that leaves it gives a NaN energy (tests/test_nonfinite_*.py)
+DOMAIN_EXAMPLES = {"sqrt_outflow": (sqrt_outflow, 2, 3), "gompertz": (gompertz_predation, 2, 4)}
 
 
 def rk4(f_vec, x0, thetas, T, n, substeps=20, grid=None):

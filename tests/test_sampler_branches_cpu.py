@@ -14,8 +14,10 @@ a transition takes (the census); the table ``tests.util.BRANCH_CASES`` lists, pe
   oracle at 1e-10 in tests/test_oracle_golden.py): the integer diagnostics must be identical and every compared float within 1/100 of
   the device tolerance.  A case that fails this is replaced by another seed or step, never given a looser bound.
 
-Unreached, and why: NaN energy (it takes an overflow that the two sides cannot be made to reach at the same leaf); checkpoint levels 10 and 11
-(a level-10 check needs a subtree of 1024 leaves, i.e. a transition of >= 2047 leapfrogs -- twice the per-transition budget of a quick test;
+NaN energies are not reached by these cases (asserted below); an overflow-driven one cannot be made to happen at the same leaf on both sides,
+one from a drift with a limited domain can: tests/test_nonfinite_cpu.py / tests/test_nonfinite_gpu.py (``tests.util.DOMAIN_CASES``).
+Unreached, and why: checkpoint levels 10 and 11 (a level-10 check needs a subtree of 1024 leaves, i.e. a transition of >= 2047 leapfrogs --
+twice the per-transition budget of a quick test;
 level 9 and depth 10 are reached by ``depth10_fixed_step``, a depth cap of 12 is run by two cases)."""
 import collections
 import sys
@@ -102,7 +104,7 @@ def test_case_takes_the_branches_it_is_listed_for(case):
         assert U.BRANCHES[b](case, ev, trace), (case.name, b)
     for chain in U.BRANCH_CHAINS:
         _, tr, e = U.branch_oracle_run(case, chain)
-        assert e[("nan",)] == 0                                                    # out of scope (module docstring)
+        assert e[("nan",)] == 0                                                    # (NaN energies: tests/test_nonfinite_cpu.py)
         assert len(tr) <= 12 and max(r.leapfrogs for _, r, _ in tr) <= 1023
 
 

@@ -1,4 +1,5 @@
 """Shared helpers for the tests (oracle side only; product code never imports this)."""
+import contextlib
 import os
 
 import numpy as np
@@ -191,7 +192,8 @@ def shuffled_grid(N, seed, dt=0.025):
 #   hmc_div             (L = 8)                       a step with u <= ediff rejected because -ediff >= 0.2               3.6e-3 step_size     1.3e-10
 #   u_early_member2     1 1 3 4 7 6 4                 u_end(2, early) 1; max_depth(7) 1 (second member of the group)      5.5e-5 target        1.7e-11
 #
-# Checkpoint levels 10 and 11 stay unreached (a level-10 check needs a transition of >= 2047 leapfrogs), as do NaN energies.
+# Checkpoint levels 10 and 11 stay unreached (a level-10 check needs a transition of >= 2047 leapfrogs).  NaN energies are not taken by these
+# cases; DOMAIN_CASES below reach them.
 #
 BRANCH_CHAINS = (20, 21)
 
@@ -326,3 +328,234 @@ BRANCHES = {
         r.has_divergence and not r.is_accepted and np.log1p(-orc.rng_uniform(0, k, BRANCH_CHAINS[0], orc.STREAM_MERGE, c.seed)) <= r.log_accept_ratio
         for k, r, _ in tr),                                                 # (u <= ediff <=> u <= min(ediff, 0): only divergence rejects it)
 }
+
+
+# ---- leaves with non-finite energies ------------------------------------------------------------------------------------------------
+# A leapfrog step that leaves the domain of a square-root or logarithmic drift gives a NaN energy; TFP, the oracle and csrc/decide.h
+# count such a leaf as energy -inf: it diverges and ends its sub-tree and the transition.  The two drifts of
+# magi_v2_amd.drift_examples.DOMAIN_EXAMPLES reach it from theta_0 = 1 at ordinary step sizes.  Fixture and case table for
+# tests/test_nonfinite_cpu.py (the proof on the oracle alone: every case takes what it claims, no leaf of a compared chain is within
+# rounding of the domain's edge, no decision sits on a rounding knife-edge, a device without the NaN rule would fail) and
+# tests/test_nonfinite_gpu.py (the device draw for draw against the oracle).  Everything here is CPU-only: the matrices are
+# orc.build_all's, the oracle's Jacobians complex-step derivatives of the callable.
+
+# drift -> (generating theta, x(0), T); the component whose sign decides whether a point is inside the domain is component 0 in both
+DOMAIN_TRUTH = {"sqrt_outflow": (np.array([0.5, 1.0, 0.8]), [1.0, 0.2], 3.6), "gompertz": (np.array([1.0, 1.0, 0.5, 0.3]), [0.02, 0.1], 3.0)}
+DOMAIN_MARGIN = 1e-6               # every entry a sqrt / log sees is at least this far from 0, as a fraction of max|X|: 100 x the X tolerance
+
+_domain_rec = None                 # while a list: the oracle's drift appends (min of component 0, max|X|, min |component 0|) per evaluation, NaNs for a non-finite state
+
+
+def _domain_oracle_drift(f_vec):
+    def fn(X, th):
+        X, th = np.asarray(X, dtype=np.float64), np.asarray(th, dtype=np.float64)
+        if _domain_rec is not None:
+            fin = bool(np.isfinite(X).all())
+            _domain_rec.append((float(X[:, 0].min()) if fin else np.nan, float(np.abs(X).max()) if fin else np.nan,
+                                float(np.abs(X[:, 0]).min()) if fin else np.nan))
+        with np.errstate(all="ignore"):
+            n, D = X.shape
+            J, T = np.zeros((n, D, D)), np.zeros((n, D, len(th)))
+            for k in range(D):                                                 # complex step (tests/test_drift_cpu.py), independent of sympy
+                Xc = X.astype(complex); Xc[:, k] += 1e-30j
+                J[:, :, k] = np.imag(f_vec(None, Xc, th.astype(complex))) / 1e-30
+            for p in range(len(th)):
+                tc = th.astype(complex); tc[p] += 1e-30j
+                T[:, :, p] = np.imag(f_vec(None, X.astype(complex), tc)) / 1e-30
+            return np.asarray(f_vec(None, X, th), dtype=np.float64), J, T
+    return fn
+
+
+@contextlib.contextmanager
+def domain_drifts():
+    """The DOMAIN_EXAMPLES drifts registered with the oracle (``orc.DRIFTS``, which ``Problem.drift`` names) for the duration only: other
+    tests iterate over that table."""
+    from magi_v2_amd.drift_examples import DOMAIN_EXAMPLES
+    added = {name: (_domain_oracle_drift(f_vec), D, P) for name, (f_vec, D, P) in DOMAIN_EXAMPLES.items() if name not in orc.DRIFTS}
+    orc.DRIFTS.update(added)
+    try:
+        yield
+    finally:
+        for name in added:
+            del orc.DRIFTS[name]
+
+
+class DomainCase(BranchCase):
+    """A BranchCase on a DOMAIN_EXAMPLES drift: `tag` is the drift's name; N grid points; `shift` is added to x(0) of component 0: the same system, its data
+    and its initial state inside the domain's interior (the second member of a problem group)."""
+
+    def __init__(self, name, drift, band, seed, cfg, claims, N=41, shift=0.0, **kw):
+        super().__init__(name, drift, band, seed, cfg, claims, **kw)
+        self.N, self.shift = N, shift
+
+
+_domain_problems = {}
+
+
+def domain_problem(case):
+    """(fixture {"Xhat_init", "sigma_sqs_init"}, orc.Problem with the reference's band mask, unmasked orc.Problem): the recipe of
+    tests/test_user_drift_gpu.py::make_problem (rk4 truth, every other grid point observed, initial hyper-parameters with phi2 = 1.5) with
+    observation noise 0.01 and the oracle's own matrix build."""
+    from magi_v2_amd.drift_examples import DOMAIN_EXAMPLES, rk4
+    key = (case.tag, case.N, case.band, case.shift)
+    if key not in _domain_problems:
+        f_vec, D, P = DOMAIN_EXAMPLES[case.tag]
+        truth, x0, T = DOMAIN_TRUTH[case.tag]
+        I, X = rk4(f_vec, [x0[0] + case.shift] + list(x0[1:]), truth, T, case.N)
+        X_obs = X + np.random.default_rng(0).normal(0, 0.01, X.shape)
+        X_obs[1::2] = np.nan
+        Xi = orc.linear_interpolate(X_obs)
+        hp = orc.hparams_initial(Xi)
+        C_inv, m, K_inv = orc.build_all(I, hp["phi1s"], np.full(D, 1.5), 2.01, bandsize=None)
+        N_ds = (~np.isnan(X_obs)).sum(axis=0).astype(np.float64)
+        idx = np.where(~np.isnan(X_obs).flatten())[0]
+        Xhat = orc.cubic_smoother(I, Xi)
+        mk = lambda b: orc.Problem(I=I, mu=Xi.mean(axis=0), C_inv=band_part_copy(C_inv, b), m=band_part_copy(m, b), K_inv=band_part_copy(K_inv, b),
+                                   N_ds=N_ds, obs_idx=idx, y=X_obs.reshape(-1)[idx], beta=float(D * case.N / N_ds.sum()),
+                                   LB=orc.sigma_sqs_lower_bound(Xhat), drift=case.tag, P=P)
+        _domain_problems[key] = ({"Xhat_init": Xhat, "sigma_sqs_init": hp["sigma_sqs"]}, mk(case.band), mk(None))
+    return _domain_problems[key]
+
+
+class Census(dict):
+    """The counter orc.nuts_one_step fills, which also keeps the order of its increments: ``log`` = [(key, drift evaluations so far)]."""
+
+    def __init__(self, clock):
+        super().__init__()
+        self.log, self.clock = [], clock
+
+    def __missing__(self, key):
+        return 0
+
+    def __setitem__(self, key, value):
+        self.log.append((key, self.clock()))
+        super().__setitem__(key, value)
+
+
+class DomainRun:
+    """One oracle chain of a case: ``out`` (sample_chain's), ``trace``, ``events`` (the census), ``evals`` (one record per drift evaluation:
+    min of component 0, max|X|, min|component 0|; NaN for a non-finite state) and, from the census' log,
+    ``nan_leaves`` = [(transition, leaf index in its sub-tree, sub-tree depth)] and ``ordinary`` = the same for divergent leaves of finite energy
+    (NUTS only: fixed-L HMC has no census)."""
+
+    def __init__(self, out, trace, events, evals, hmc):
+        self.out, self.trace, self.events, self.evals = out, trace, events, evals
+        ends = 1 + np.cumsum([r.leapfrogs for _, r, _ in trace])               # (evaluation 0 is the initial state's)
+        self.first_eval = np.concatenate([[1], ends[:-1]])
+        self.nan_leaves, self.ordinary, self.wasted = [], [], []
+        where = lambda clock: int(np.searchsorted(ends, clock, side="left"))     # the transition whose leaf was evaluation number clock - 1
+        pending = False
+        for key, clock in events.log:
+            if key == ("nan",):
+                pending = True
+            elif key[0] == "div":
+                (self.nan_leaves if pending else self.ordinary).append((where(clock), key[1], key[2]))
+                pending = False
+            elif key[0] == "wasted_accept":
+                self.wasted.append((where(clock), key[1], key[2]))
+        assert hmc or len(self.nan_leaves) == events[("nan",)]
+
+    def nan_transitions(self):
+        return sorted({k for k, _, _ in self.nan_leaves})
+
+    def outside(self, k):
+        """Leaves of transition k (in evaluation order) whose state is outside the domain or non-finite."""
+        a = self.first_eval[k]
+        return [j for j in range(self.trace[k][1].leapfrogs) if not self.evals[a + j][0] > 0.0]
+
+
+_domain_runs = {}
+
+
+def domain_oracle_run(case, chain, logpost_grad=None, cache=True, **over):
+    """DomainRun of one chain of a case, computed once per session and shared (read-only).  ``logpost_grad`` / ``over``: another log
+    posterior / other sample_chain arguments (not cached)."""
+    global _domain_rec
+    key = (case.name, chain)
+    if not cache or logpost_grad is not None or over or key not in _domain_runs:
+        fx, pr, _ = domain_problem(case)
+        trace, evals = [], []
+        events = Census(lambda: len(evals))
+        _domain_rec = evals
+        try:
+            with domain_drifts():
+                out = orc.sample_chain(pr, fx["Xhat_init"], fx["sigma_sqs_init"], np.ones(pr.P), case.results, case.burnin, seed=case.seed, chain=chain,
+                                       trace=trace, events=events, logpost_grad=logpost_grad, **dict(branch_oracle_kwargs(case), **over))
+        finally:
+            _domain_rec = None
+        run = DomainRun(out, trace, events, evals, "hmc_leapfrogs" in case.cfg)
+        if logpost_grad is not None or over or not cache:
+            return run
+        _domain_runs[key] = run
+    return _domain_runs[key]
+
+
+def _nan_tr(run, k):
+    r = run.trace[k][1]
+    return r.has_divergence and r.log_accept_ratio == -np.inf
+
+
+# claim -> predicate(case, {chain: DomainRun}): does the case take it?  NUTS claims are read off the census of chain 20 unless they say otherwise.
+DOMAIN_BRANCHES = {
+    # the first leaf of a transition is NaN: one leapfrog, log_accept_ratio = -inf, not accepted, has_divergence
+    "nan_first_leaf": lambda c, runs: any(
+        (it, d) == (0, 0) and runs[20].trace[k][1].leapfrogs == 1 and _nan_tr(runs[20], k) and not runs[20].trace[k][1].is_accepted
+        for k, it, d in runs[20].nan_leaves),
+    # a NaN leaf at index >= 1 of a sub-tree of depth >= 2 in a transition that had accepted a proposal, which survives
+    "nan_mid_subtree": lambda c, runs: any(
+        it >= 1 and d >= 2 and runs[20].trace[k][1].is_accepted and runs[20].trace[k][1].has_divergence and (k, d, True) in runs[20].wasted
+        for k, it, d in runs[20].nan_leaves) and runs[20].events[("div_accepted",)] > 0,
+    "nan_last_leaf": lambda c, runs: any(d >= 1 and it == (1 << d) - 1 for k, it, d in runs[20].nan_leaves),
+    # >= 2 accepted transitions after the run's last NaN transition
+    "recovers": lambda c, runs: bool(runs[20].nan_leaves) and sum(
+        int(r.is_accepted) for k, r, _ in runs[20].trace if k > runs[20].nan_transitions()[-1]) >= 2,
+    # a transition index at which chain 20 takes a NaN leaf and chain 21 does not, and one the other way round
+    "one_of_the_batch": lambda c, runs: bool(set(runs[20].nan_transitions()) - set(runs[21].nan_transitions()))
+    and bool(set(runs[21].nan_transitions()) - set(runs[20].nan_transitions())),
+    # adaptation on: the step size falls after a -inf ratio
+    "adapts": lambda c, runs: "num_adaptation_steps" not in c.cfg and any(
+        k + 1 < min(int(0.8 * c.burnin), len(runs[20].trace)) and runs[20].trace[k][1].log_accept_ratio == -np.inf
+        and runs[20].trace[k + 1][2] < runs[20].trace[k][2] for k in runs[20].nan_transitions()),
+    # fixed-L HMC whose trajectory leaves the domain before its last leaf: rejected, has_divergence, log_accept_ratio = -inf
+    "hmc_nan": lambda c, runs: c.cfg.get("mode") == 1 and c.cfg.get("hmc_leapfrogs") == 8 and any(
+        run.outside(k) and run.outside(k)[0] < 7 and not r.is_accepted and r.has_divergence and r.log_accept_ratio == -np.inf
+        for run in (runs[20],) for k, r, _ in run.trace),
+    # an ordinary divergence, of finite energy
+    "ordinary_div": lambda c, runs: bool(runs[20].ordinary),
+    "two_operator_blocks": lambda c, runs: c.N == 161 and c.band == 20 and bool(runs[20].nan_leaves),
+    "interior": lambda c, runs: c.shift > 0 and all(not runs[ch].nan_leaves and all(e[0] >= 0.3 for e in runs[ch].evals) for ch in BRANCH_CHAINS),
+}
+
+# Every case: theta_0 = 1, 6 burn-in + 4 kept transitions, stale cache off, chains BRANCH_CHAINS.  Measured on the CPU (chain 20 | chain 21): NaN leaves as
+# (transition, leaf index in its sub-tree, sub-tree depth) | smallest |argument of sqrt / log| / max|X| over all evaluated states (bound DOMAIN_MARGIN)
+# | float64 vs long-double operator products, worst fraction of the device tolerance (bound 1e-2) | device vs oracle on an MI355X, the same fraction.
+#
+#   case                 NaN leaves, chain 20 | chain 21                              margin    CPU vs CPU            device vs oracle
+#   sqrt_deep            (1, 0, 0) (7, 13, 4) | (1, 0, 0)                             1.5e-4    9.0e-4 log_accept     1.4e-3 log_accept
+#   sqrt_last_leaf       (7, 3, 2) (9, 0, 2) | (2, 0, 3) (8, 0, 0) (9, 0, 0)          1.6e-4    2.4e-3 step_size      5.2e-3 step_size
+#   gompertz_first_leaf  (0, 0, 0) (1, 0, 0) (2, 0, 0) | the same                     2.7e-4    2.9e-6 log_accept     3.5e-6 log_accept
+#   sqrt_hmc             outside from leaf 1 or 2 of 8 in transitions 0, 1, 4, 9      1.2e-5    3.2e-6 target         1.8e-5 target
+#   gompertz_hmc         outside from leaf 0 or 2 of 8 in transitions 0, 1, 2         4.4e-5    6.0e-6 target         1.3e-5 target
+#   sqrt_n161 (b = 20)   (0, 0, 0) (1, 0, 0) (2, 0, 0) | the same                     2.7e-5    2.6e-4 log_accept     4.0e-4 log_accept
+#   sqrt_interior        none (every evaluated x >= 0.3; second member of the group)  2.1e-1    1.8e-3 target         9.5e-3 target (group)
+#
+# In every case and on every kernel the device has every integer diagnostic and every -inf of log_accept_ratio where the oracle has them.
+_D6 = dict(max_tree_depth=6)
+_HMC8 = dict(mode=1, hmc_leapfrogs=8)
+DOMAIN_CASES = [
+    DomainCase("sqrt_deep", "sqrt_outflow", None, 6, dict(_D6, step_size=1e-3),
+               ("nan_first_leaf", "nan_mid_subtree", "recovers", "adapts", "ordinary_div"), burnin=6, results=4, batches=(1, 2, 3, 9)),
+    DomainCase("sqrt_last_leaf", "sqrt_outflow", None, 808, dict(_D6, step_size=3e-3),
+               ("nan_mid_subtree", "nan_last_leaf", "one_of_the_batch", "ordinary_div"), burnin=6, results=4),
+    DomainCase("gompertz_first_leaf", "gompertz", None, 808, dict(_D6, step_size=3e-2),
+               ("nan_first_leaf", "recovers", "adapts", "ordinary_div"), burnin=6, results=4, batches=(1, 2, 3, 9)),
+    DomainCase("sqrt_hmc", "sqrt_outflow", None, 808, dict(_HMC8, step_size=3e-3), ("hmc_nan",), burnin=6, results=4, batches=(1, 3)),
+    DomainCase("gompertz_hmc", "gompertz", None, 808, dict(_HMC8, step_size=3e-3), ("hmc_nan",), burnin=6, results=4, batches=(1, 3)),
+    DomainCase("sqrt_n161", "sqrt_outflow", 20, 808, dict(_D6, step_size=3e-3),
+               ("nan_first_leaf", "recovers", "adapts", "ordinary_div", "two_operator_blocks"), N=161, burnin=6, results=4, batches=(1, 3)),
+    DomainCase("sqrt_interior", "sqrt_outflow", None, 6, dict(_D6, step_size=1e-3), ("interior",), shift=3.0, burnin=6, results=4, batches=()),
+]
+
+
+def domain_case(name):
+    return next(c for c in DOMAIN_CASES if c.name == name)
