@@ -1,6 +1,7 @@
 """Classic MAGI benchmark systems written the way a user of the reference writes ``f_vec`` (numpy in place of
 tf.*): used by the tests of the generic-drift path and pre-built by ``__graft_entry__.build()``.  ``EXAMPLES`` ignore their first
-argument; ``TIME_EXAMPLES`` are forced systems that use it; ``DOMAIN_EXAMPLES`` are defined on part of the state space only (a square root, a logarithm)."""
+argument; ``TIME_EXAMPLES`` are forced systems that use it; ``DOMAIN_EXAMPLES`` are defined on part of the state space only (a square root, a logarithm);
+``EDGE_EXAMPLES`` sit at the documented shape limits (D = 1, 7, 8; P = 8) and at the edges of what the tracer prints and separates."""
 import numpy as np
 
 
@@ -82,6 +83,70 @@ def gompertz_predation(t, X, thetas):
 
 # drifts with a limited domain: a leapfrog step that leaves it gives a NaN energy (tests/test_nonfinite_*.py)
 DOMAIN_EXAMPLES = {"sqrt_outflow": (sqrt_outflow, 2, 3), "gompertz": (gompertz_predation, 2, 4)}
+
+
+def logistic_1(t, X, thetas):
+    """Logistic growth, ONE component: x' = r x (1 - x / K);  theta = (r, K).  Separable: coefficients r, r / K on the basis x, x^2."""
+    x = X[:, 0:1]
+    return thetas[0] * x * (1.0 - x / thetas[1])
+
+
+def chain_8(t, X, thetas):
+    """Linear cascade of eight compartments with a constant source and a saturating last link, 8 parameters:
+    x0' = th0 - th1 x0,  xk' = thk x(k-1) - th(k+1) xk (k = 1..5),  x6' = th6 x5 - th7 x6 / (1 + x7^2),  x7' = th7 x6 / (1 + x7^2) - th1 x7.
+    Separable: two basis functions per component, the source's a constant."""
+    x = [X[:, k:k + 1] for k in range(8)]
+    th = [thetas[k] for k in range(8)]
+    link = th[7] * x[6] / (1.0 + x[7] ** 2)
+    return np.concatenate([th[0] - th[1] * x[0]] + [th[k] * x[k - 1] - th[k + 1] * x[k] for k in range(1, 6)]
+                          + [th[6] * x[5] - link, link - th[1] * x[7]], axis=1)
+
+
+def cascade_7(t, X, thetas):
+    """Seven-compartment cascade whose last link is Michaelis-Menten with its constant a parameter, 8 parameters:
+    x0' = th0 - th1 x0,  xk' = thk x(k-1) - th(k+1) xk (k = 1..4),  x5' = th5 x4 - th6 x5 / (th7 + x5),  x6' = th6 x5 / (th7 + x5) - th1 x6.
+    Not separable (th7 + x5 mixes the state with a parameter)."""
+    x = [X[:, k:k + 1] for k in range(7)]
+    th = [thetas[k] for k in range(8)]
+    mm = th[6] * x[5] / (th[7] + x[5])
+    return np.concatenate([th[0] - th[1] * x[0]] + [th[k] * x[k - 1] - th[k + 1] * x[k] for k in range(1, 5)]
+                          + [th[5] * x[4] - mm, mm - th[1] * x[6]], axis=1)
+
+
+def hill_powers(t, X, thetas):
+    """A Hill term with its exponent a parameter beside powers of every kind the printer knows:
+    x' = V y^n / (K^n + y^n) - d x^2.5 - 0.3 x^5 + pi / 10,  y' = d 2^x - V x^(1/3) y - 0.02 / y^6;  theta = (V, n, K, d).
+    Defined for x, y > 0.  Not separable."""
+    x, y = X[:, 0:1], X[:, 1:2]
+    V, n, K, d = thetas[0], thetas[1], thetas[2], thetas[3]
+    return np.concatenate([V * y ** n / (K ** n + y ** n) - d * x ** 2.5 - 0.3 * x ** 5 + np.pi / 10.0,
+                           d * 2 ** x - V * x ** (1.0 / 3.0) * y - 0.02 * y ** -6], axis=1)
+
+
+def mixed_3(t, X, thetas):
+    """Three components that between them hold every shape of separable term:
+    x' = a e^-x - b sin y + c tanh(x y) - e log(1 + x^2)                                  (four transcendental basis functions),
+    y' = p - y + 2 p q x - p q x y + z^2 / 3 - (x / 7)^2 + 0.1 / (1 + y^2)                 (a constant term, a parameter-free group, a merged pair),
+    z' = 0;  theta = (p, q, a, b, c, e)."""
+    x, y, z = X[:, 0:1], X[:, 1:2], X[:, 2:3]
+    p, q, a, b, c, e = (thetas[k] for k in range(6))
+    return np.concatenate([a * np.exp(-x) - b * np.sin(y) + c * np.tanh(x * y) - e * np.log(1.0 + x ** 2),
+                           p - y + 2.0 * p * q * x - p * q * x * y + np.square(z) / 3 - (x / 7) ** 2 + 0.1 * np.reciprocal(1.0 + y ** 2),
+                           0.0 * x], axis=1)
+
+
+def five_terms(t, X, thetas):
+    """A component with five separable terms (one more than the separable kernels carry): x' = a x + b y + c x y + d x^2 + e y^2,  y' = -a y."""
+    x, y = X[:, 0:1], X[:, 1:2]
+    a, b, c, d, e = (thetas[k] for k in range(5))
+    return np.concatenate([a * x + b * y + c * x * y + d * x ** 2 + e * y ** 2, -a * y], axis=1)
+
+
+# the documented shape limits (D = 1, 7, 8; P = 8) and the printer's and the separator's vocabulary (tests/test_drift_edges_*.py)
+EDGE_EXAMPLES = {"logistic1": (logistic_1, 1, 2), "chain8": (chain_8, 8, 8), "cascade7": (cascade_7, 7, 8), "hill_pow": (hill_powers, 2, 4),
+                 "mixed3": (mixed_3, 3, 6)}
+# traced on the CPU only: no library is built for it
+EDGE_TRACE_ONLY = {"five_term": (five_terms, 2, 5)}
 
 
 def rk4(f_vec, x0, thetas, T, n, substeps=20, grid=None):

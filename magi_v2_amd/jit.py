@@ -128,8 +128,9 @@ def library_for(drift, verbose: bool = False, extra=()) -> str:
                 reuse = {}
                 if not wide and not extra and not _build.needs_build():
                     for src in _build.sources():
-                        if os.path.basename(src) in _DRIFT_FREE:
-                            reuse[src] = os.path.join(_build.OBJDIR, os.path.basename(src) + ".o")
+                        obj = os.path.join(_build.OBJDIR, os.path.basename(src) + ".o")
+                        if os.path.basename(src) in _DRIFT_FREE and os.path.exists(obj):       # (a tree that received the library without its objects compiles them)
+                            reuse[src] = obj
                 tmp = os.path.join(work, "libmagi_hip_user.so")
                 try:                                      # (compile_checked keeps each unit's ISA and runs the EXEC-prologue check on it, build.py)
                     _build.build_library(_build.sources(), work, tmp, extra=drift_flags(drift, hdr, extra), reuse=reuse, verbose=verbose)

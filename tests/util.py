@@ -71,9 +71,13 @@ def synthetic_seir_problem(N, seed=0, dt=0.025, alpha=0.05, band=None, phi=None)
 # diagonal operator blocks and their neighbours only (tests/test_structureless_cpu.py measures it).  Users may upload any matrices
 # (magi_set_matrices; the reference lets them overwrite the attributes): the fixture below has i.i.d. entries instead.
 
-STRUCTURELESS_BOX = {"seir3": (0.05, 0.3), "seir4": (0.05, 0.3), "sirw": (0.05, 0.3), "seir_seasonal": (0.05, 0.3)}   # drift -> (low, high) of every component; others (0.1, 0.9)
+STRUCTURELESS_BOX = {"seir3": (0.05, 0.3), "seir4": (0.05, 0.3), "sirw": (0.05, 0.3), "seir_seasonal": (0.05, 0.3),
+                     "hill_pow": (0.5, 1.5)}                                                       # drift -> (low, high) of every component; others (0.1, 0.9)
 STRUCTURELESS_THETA = {"seir3": [6.0, 0.6, 1.8], "seir4": [6.0, 0.6, 1.8], "sirw": [2.0, 0.5, 0.3, 1.0, 0.2], "seir_seasonal": [6.0, 0.6, 1.8, 0.4],
-                       "ptrans": [0.07, 0.6, 0.05, 0.3, 0.017, 0.3]}                               # nominal parameters; others 0.5
+                       "ptrans": [0.07, 0.6, 0.05, 0.3, 0.017, 0.3],
+                       # magi_v2_amd.drift_examples.EDGE_EXAMPLES (tests/test_drift_edges_*.py): no two parameters of a drift alike
+                       "logistic1": [0.8, 1.3], "chain8": [0.6, 0.9, 0.5, 0.8, 0.4, 0.7, 0.55, 1.1], "cascade7": [0.6, 0.9, 0.5, 0.8, 0.4, 0.7, 0.95, 0.45],
+                       "hill_pow": [1.0, 2.0, 0.8, 0.5], "mixed3": [0.7, 0.9, 0.6, 0.8, 1.1, 0.5]}       # nominal parameters; others 0.5
 STRUCTURELESS_SIG_PRE = -3.0                                                                       # nominal sigma_pre of every component
 
 
