@@ -344,7 +344,6 @@ int magi_stream_kernel_name(magi_handle* h, int n_chains, char* buf, int cap);
  *   "potrf_lookahead_min" MAGI_POTRF_LOOKAHEAD_MIN  >= 0
  *   "no_graph"            MAGI_NO_GRAPH             flag
  *   "fit_host_loop"       MAGI_FIT_HOST_LOOP        flag
- *   "fit_per_component"   MAGI_FIT_PER_COMPONENT    flag
  *   "build_profile"       MAGI_BUILD_PROFILE        flag
  *   "build_serial"        MAGI_BUILD_SERIAL         flag
  *   "slot_budget_graphs"  (none: a test hook)       cap on the graph launches of one magi_sampler_run; 0 = the computed bound */

@@ -107,12 +107,13 @@ struct MaternArgs {
                                // fp64 arithmetic, so a small matrix wants one entry per thread rather than 16)
     const double* dyn;         // non-null: phi1, c, logA, diag_pp come from device memory (FitDyn below) -- the hyper-parameter
                                // fit replays one captured graph per Adam step, so its launch arguments cannot change
-    long bsK, bs_dyn;          // grid.z > 1 (the fit's batched step: all components in one launch): element strides of the outputs / dyn blocks
+    long bsK, bs_dyn;          // grid.z > 1 (the fit: all components in one launch): element strides of the outputs / dyn blocks
 };
 
 // 64 x 64 tile per 256-thread workgroup; the two 64-entry slices of the time grid staged in LDS
 // layout of the per-component device block of the hyper-parameter fit (doubles)
-enum FitDyn { FD_RAW = 0, FD_M = 3, FD_V = 6, FD_PV = 9 /* phi1, phi2, sigma^2 */, FD_C = 12, FD_LOGA, FD_DIAGPP, FD_SHIFT, FD_COUNT };
+enum FitDyn { FD_RAW = 0, FD_M = 3, FD_V = 6, FD_PV = 9 /* phi1, phi2, sigma^2 */, FD_C = 12, FD_LOGA, FD_DIAGPP, FD_SHIFT,
+              FD_MU_PHI2, FD_SD_PHI2, FD_SIG_LOC /* the component's priors, written once at set-up */, FD_COUNT };
 
 __global__ __launch_bounds__(256) void k_matern(MaternArgs a) {
     __shared__ double ts[64], tt[64];
@@ -770,7 +771,7 @@ __global__ void k_symmetrize(double* A, int N) {             // A = (A + A^T)/2,
 __global__ void k_fit_shift(const double* __restrict__ Kap, double* __restrict__ S, int N, double shift, const double* __restrict__ dyn) {
     const size_t e = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (e >= (size_t)N * N) return;
-    Kap += (size_t)blockIdx.y * N * N; S += (size_t)blockIdx.y * N * N;          // (grid.y = component of a batched step)
+    Kap += (size_t)blockIdx.y * N * N; S += (size_t)blockIdx.y * N * N;          // (grid.y = component)
     if (dyn) dyn += (size_t)blockIdx.y * FD_COUNT;
     if (dyn) shift = dyn[FD_SHIFT];
     const int i = (int)(e / N), j = (int)(e - (size_t)i * N);
@@ -836,20 +837,17 @@ __global__ __launch_bounds__(256) void k_fit_final(const double* __restrict__ pa
     if (threadIdx.x < 5) out[threadIdx.x] = v[threadIdx.x];
 }
 
-// The scalar tail of one Adam step of one component, on the device so that a fit never waits for the host:
+// The scalar tail of one Adam step, on the device so that a fit never waits for the host (grid.x = component):
 // log likelihood and gradient from the reduced sums, TruncatedNormal priors, softplus chain rule, Adam update (tf_keras
 // defaults), next hyper-parameters and the Matern constants derived from them.  (reference: magi_v2.py:611-691)
-struct FitStepArgs {
+struct FitStepArgs {           // per-component blocks, FD_COUNT / 4 / 8 / 2 / `iters` apart:
     double* dyn;               // [FD_COUNT]
     int* ist;                  // [0] step t (1-based)  [1] failed pivot index (-1: none, sticky)  [2] step of the failure
     const double* out;         // [6] sums of k_fit_final + log-diagonal sum
     const int* status;         // pivot word of this step's Cholesky
     double* trace;             // [iters]: D (loglik + log prior) of the parameters the step started from
-    int N, D;
-    double nu, lgam_nu, mu_phi2, sd_phi2, sig_loc, lr, jitter;
-    // batched step (grid.x = components; blocks of dyn / ist / out / status / trace are FD_COUNT / 4 / 8 / 2 / `iters` apart):
-    int batched, iters;
-    double mu_phi2_z[8], sd_phi2_z[8], sig_loc_z[8];
+    int N, D, iters;
+    double nu, lgam_nu, lr, jitter;
 };
 
 __device__ inline void fit_derive(double* dyn, double nu, double lgam_nu, double jitter) {
@@ -862,12 +860,9 @@ __device__ inline void fit_derive(double* dyn, double nu, double lgam_nu, double
 
 __global__ void k_fit_step(FitStepArgs a) {
     if (threadIdx.x != 0) return;
-    if (a.batched) {
-        const int z = blockIdx.x;
-        a.dyn += (size_t)z * FD_COUNT; a.ist += 4 * z; a.out += 8 * z; a.status += 2 * z; a.trace += (size_t)z * a.iters;
-        a.mu_phi2 = a.mu_phi2_z[z]; a.sd_phi2 = a.sd_phi2_z[z]; a.sig_loc = a.sig_loc_z[z];
-    } else if (blockIdx.x != 0) return;
-    double* dyn = a.dyn;
+    const int z = blockIdx.x;
+    a.ist += 4 * z; a.out += 8 * z; a.status += 2 * z; a.trace += (size_t)z * a.iters;
+    double* dyn = a.dyn + (size_t)z * FD_COUNT;
     const int t = a.ist[0];
     if (t == 0) {                                      // first launch: hyper-parameters from the raw variables
         for (int k = 0; k < 3; ++k) dyn[FD_PV + k] = log1p(exp(dyn[FD_RAW + k]));
@@ -883,15 +878,15 @@ __global__ void k_fit_step(FitStepArgs a) {
     const double logdet = 2.0 * o[5];
     const double ll = -0.5 * o[3] - 0.5 * logdet - 0.5 * a.N * log(2.0 * 3.141592653589793);
     const double g3[3] = {0.5 * o[0] / p1, 0.5 * o[1] / p2, 0.5 * (o[4] - o[2])};
-    const double sc[3] = {1000.0 * sD, a.sd_phi2 * sD, 1000.0 * sD};
-    const double z[3] = {(p1 - 1e-4) / sc[0], (p2 - a.mu_phi2) / sc[1], (s2 - a.sig_loc) / sc[2]};
-    const double lp = -0.5 * (z[0] * z[0] + z[1] * z[1] + z[2] * z[2]);
+    const double sc[3] = {1000.0 * sD, dyn[FD_SD_PHI2] * sD, 1000.0 * sD};
+    const double zs[3] = {(p1 - 1e-4) / sc[0], (p2 - dyn[FD_MU_PHI2]) / sc[1], (s2 - dyn[FD_SIG_LOC]) / sc[2]};
+    const double lp = -0.5 * (zs[0] * zs[0] + zs[1] * zs[1] + zs[2] * zs[2]);
     a.trace[t - 1] = D * (ll + lp);
     const double b1 = 0.9, b2 = 0.999, eps = 1e-7;
     const double al = a.lr * sqrt(1.0 - pow(b2, (double)t)) / (1.0 - pow(b1, (double)t));
     for (int k = 0; k < 3; ++k) {
         const double raw = dyn[FD_RAW + k];
-        const double g = -D * (g3[k] - z[k] / sc[k]) * (1.0 / (1.0 + exp(-raw)));
+        const double g = -D * (g3[k] - zs[k] / sc[k]) * (1.0 / (1.0 + exp(-raw)));
         const double m = b1 * dyn[FD_M + k] + (1.0 - b1) * g;
         const double v = b2 * dyn[FD_V + k] + (1.0 - b2) * g * g;
         const double nraw = raw - al * m / (sqrt(v) + eps);
@@ -916,20 +911,16 @@ struct Linalg {
     bool lookahead = false;     // potrf may fork the rank-k updates to the handle's CU-masked stream (dense build only; never inside a capture)
 };
 
-// optional per-class timing of the build (MAGI_BUILD_PROFILE=1): HIP events around every launch, so the
-// build is serialised and slower -- diagnostics only
-enum BuildClass { BC_MATERN = 0, BC_DIAG, BC_PANEL, BC_TRAIL, BC_TRTRI, BC_LAUUM, BC_PROD, BC_FUSED, BC_COUNT };
-struct BuildProfile { double flops[BC_COUNT]; double ms[BC_COUNT]; long calls[BC_COUNT]; bool on; hipEvent_t e0, e1; };
-BuildProfile g_prof{};
-
-void prof_begin(hipStream_t s) { if (g_prof.on) (void)hipEventRecord(g_prof.e0, s); }
-void prof_end(hipStream_t s, int cls, double flops) {
-    if (!g_prof.on) return;
-    (void)hipEventRecord(g_prof.e1, s);
-    (void)hipEventSynchronize(g_prof.e1);
+// the handle's build profile (magi_internal.h: BuildProfile): the launch between the two calls, timed on stream s
+void prof_begin(magi_handle* h, hipStream_t s) { if (h->prof.on) (void)hipEventRecord(h->prof.e0, s); }
+void prof_end(magi_handle* h, hipStream_t s, int cls, double flops) {
+    BuildProfile& p = h->prof;
+    if (!p.on) return;
+    (void)hipEventRecord(p.e1, s);
+    (void)hipEventSynchronize(p.e1);
     float ms = 0.f;
-    (void)hipEventElapsedTime(&ms, g_prof.e0, g_prof.e1);
-    g_prof.ms[cls] += ms; g_prof.flops[cls] += flops; g_prof.calls[cls] += 1;
+    (void)hipEventElapsedTime(&ms, p.e0, p.e1);
+    p.ms[cls] += ms; p.flops[cls] += flops; p.calls[cls] += 1;
 }
 
 // executed flops of a launch: tiles actually computed x 2 * 128 * 128 * (k range)
@@ -958,7 +949,7 @@ int launch_gemm(magi_handle* h, hipStream_t s, const GemmArgs& g_in, int batch =
     const int remap_min = (g.remap_min > 0 && h->opt.gemm_remap_min == MAGI_GEMM_REMAP_MIN_DEFAULT) ? g.remap_min : h->opt.gemm_remap_min;
     g.remap = (nsuper >= remap_min && (!g.lower_only || tY == tX)) ? 1 : 0;
     dim3 grid(g.remap ? ((nsuper + 7) / 8) * 8 * 64 : tY * tX, 1, batch);
-    prof_begin(s);
+    prof_begin(h, s);
     switch (cls) {
     case BC_PANEL: hipLaunchKernelGGL(k_gemm_f64<BC_PANEL>, grid, dim3(256), 0, s, g); break;
     case BC_TRAIL: hipLaunchKernelGGL(k_gemm_f64<BC_TRAIL>, grid, dim3(256), 0, s, g); break;
@@ -969,7 +960,7 @@ int launch_gemm(magi_handle* h, hipStream_t s, const GemmArgs& g_in, int batch =
     }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("gemm launch: ") + hipGetErrorString(e));
-    if (g_prof.on) prof_end(s, cls, gemm_flops(g, batch));
+    if (h->prof.on) prof_end(h, s, cls, gemm_flops(g, batch));
     return MAGI_OK;
 }
 
@@ -1031,10 +1022,10 @@ int potrf(Linalg& la, double* A, const char* what, bool defer_status = false, in
     for (int z = 0; z < la.batch; ++z)          // status words of this slot <- -1
         MAGI_HIP_CHECK(h, hipMemsetAsync(la.status + 2 * z + status_slot, 0xFF, sizeof(int), la.s));
     auto diag = [&](int j0, int n) {
-        prof_begin(sc);
+        prof_begin(h, sc);
         hipLaunchKernelGGL(k_diag_chol_inv, dim3(la.batch), dim3(256), lds, sc, A + (size_t)j0 * N + j0, (long)N, n,
                            la.dinv + (size_t)(j0 / NB) * 128 * 128, la.status + status_slot, j0, la.bsA, la.bs_dinv, 2);
-        prof_end(sc, BC_DIAG, (double)n * n * n * la.batch);        // n^3/3 factor + 2 n^3/3 inverse
+        prof_end(h, sc, BC_DIAG, (double)n * n * n * la.batch);        // n^3/3 factor + 2 n^3/3 inverse
     };
     auto panel = [&](int jblk, int j0, int n, int row0) -> int {     // rows >= row0 of block column j0 <- . Linv_jj^T
         (void)jblk;
@@ -1076,7 +1067,7 @@ int potrf(Linalg& la, double* A, const char* what, bool defer_status = false, in
     const int NPAN = std::max(1, std::min(h->opt.potrf_panels, 16));
     const int W = NPAN * NB;
     hipStream_t s2 = nullptr;
-    if (la.lookahead && !g_prof.on && h->opt.potrf_lookahead_min > 0 && N >= h->opt.potrf_lookahead_min && N > 2 * W) s2 = magi_trail_stream(h);
+    if (la.lookahead && !h->prof.on && h->opt.potrf_lookahead_min > 0 && N >= h->opt.potrf_lookahead_min && N > 2 * W) s2 = magi_trail_stream(h);
     if (s2) {           // fork: the chains continue on the high-priority stream (their short launches then win the CUs an update's workgroups free)
         MAGI_HIP_CHECK(h, hipEventRecord(h->ev_la[2], la.s));
         MAGI_HIP_CHECK(h, hipStreamWaitEvent(h->stream_chain, h->ev_la[2], 0));
@@ -1230,11 +1221,11 @@ BesselConsts bessel_consts(double nu) {
     return bc;
 }
 
-int launch_matern(magi_handle* h, const double* dI, int N, double phi1, double phi2, double nu, double* dK, double* dP, double* dPP, const double* dyn = nullptr,
+int launch_matern(magi_handle* h, hipStream_t s, const double* dI, int N, double phi1, double phi2, double nu, double* dK, double* dP, double* dPP, const double* dyn = nullptr,
                   int nz = 1) {
     MaternArgs a{};
     a.dyn = dyn;
-    a.bsK = (long)N * N; a.bs_dyn = FD_COUNT;      // (used when nz > 1: the batched fit step, hyper-parameters from the components' dyn blocks)
+    a.bsK = (long)N * N; a.bs_dyn = FD_COUNT;      // (used when nz > 1: the fit, hyper-parameters from the components' dyn blocks)
     a.I = dI; a.Kappa = dK; a.pKappa = dP; a.Kappapp = dPP; a.N = N;
     a.phi1 = phi1; a.nu = nu; a.c = std::sqrt(2.0 * nu) / phi2;
     a.logA = std::log(phi1) + (1.0 - nu) * std::log(2.0) - std::lgamma(nu);
@@ -1243,9 +1234,9 @@ int launch_matern(magi_handle* h, const double* dI, int N, double phi1, double p
     a.rows = 64;
     while (a.rows > 4 && (long)((N + 63) / 64) * ((N + a.rows - 1) / a.rows) < 1024) a.rows /= 2;
     dim3 grid((N + 63) / 64, (N + a.rows - 1) / a.rows, nz);
-    prof_begin(h->stream);
-    hipLaunchKernelGGL(k_matern, grid, dim3(256), 0, h->stream, a);
-    prof_end(h->stream, BC_MATERN, 0.0);
+    prof_begin(h, s);
+    hipLaunchKernelGGL(k_matern, grid, dim3(256), 0, s, a);
+    prof_end(h, s, BC_MATERN, 0.0);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("matern launch: ") + hipGetErrorString(e));
     return MAGI_OK;
@@ -1261,62 +1252,45 @@ struct DevBuf {
 // One evaluation of the GP marginal log likelihood of component data x (mean mu) and its gradient with
 // respect to (phi1, phi2, sigma^2):  S = phi1 R(phi2) + (sigma^2 + jitter) I
 //   ll = -1/2 r^T S^-1 r - 1/2 log|S| - N/2 log 2pi ,  d ll/d. = 1/2 tr((a a^T - S^-1) dS/d.) , a = S^-1 r
-struct FitWork {          // one component: its own work space and stream, so the D independent fits overlap on the GPU
+// The D components are independent and go through the same launches, so every launch carries all of them on a grid axis:
+// their buffers lie N / N^2 / ... apart, their hyper-parameters in FitDyn blocks FD_COUNT apart.
+struct FitBatch {         // the work space of one fit; the destructor waits for the stream and releases everything
     DevBuf I, r, Kap, pK, Kpp, S, Sinv, alpha, part, out;
-    Linalg la{};
-    double* host = nullptr;          // pinned: 6 outputs
-    int* host_status = nullptr;      // pinned
+    DevBuf dyn, trace;               // [D][FD_COUNT]; [D][iters] per-step objective (device loop)
+    int* ist = nullptr;              // [D][4]: step counter, sticky failure (device loop)
+    Linalg la{};                     // batch = D, on `stream`
     hipStream_t stream = nullptr;
-    int N = 0, nblk = 0;
-    DevBuf dyn, trace;               // device-resident Adam loop: FitDyn block, per-step objective
-    int* ist = nullptr;              // device: step counter, sticky failure
-    hipGraph_t graph = nullptr;
+    hipGraph_t graph = nullptr;      // one Adam step of all components (device loop)
     hipGraphExec_t exec = nullptr;
+    int N = 0, D = 0, nblk = 0;
+    ~FitBatch() {
+        if (stream) (void)hipStreamSynchronize(stream);
+        if (exec) (void)hipGraphExecDestroy(exec);
+        if (graph) (void)hipGraphDestroy(graph);
+        linalg_free(la);
+        if (ist) (void)hipFree(ist);
+        if (stream) (void)hipStreamDestroy(stream);
+    }
 };
 
-// enqueue one evaluation of component `w` on ITS stream (w.la.s); nothing here waits for the device
-// dyn != nullptr: hyper-parameters come from the component's device block and nothing is read back (graph capture)
-int fit_issue(magi_handle* h, FitWork& w, double phi1, double phi2, double sig2, double nu, double jitter, const double* dyn = nullptr) {
-    const int N = w.N;
-    hipStream_t keep = h->stream;
-    h->stream = w.la.s;                       // the helpers below launch on the handle's stream
-    int rc = launch_matern(h, w.I.p, N, phi1, phi2, nu, w.Kap.p, w.pK.p, w.Kpp.p, dyn);
+// enqueue one evaluation of all components on the fit's stream, hyper-parameters from their dyn blocks, results in w.out
+// ([D][8]) and w.la.status ([D][2]); nothing here waits for the device (it runs inside the graph capture too)
+int fit_enqueue(magi_handle* h, FitBatch& w, double nu) {
+    const int N = w.N, D = w.D;
     const size_t nn = (size_t)N * N;
-    if (rc == MAGI_OK) {
-        hipLaunchKernelGGL(k_fit_shift, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, h->stream, w.Kap.p, w.S.p, N, sig2 + jitter, dyn);
-        rc = potrf(w.la, w.S.p, "GP marginal covariance", true);
-    }
-    if (rc == MAGI_OK) {
-        hipLaunchKernelGGL(k_fit_logdiag, dim3(1), dim3(256), 0, h->stream, w.S.p, N, w.out.p + 5);
-        rc = trtri(w.la, w.S.p);
-    }
-    if (rc == MAGI_OK) rc = lauum_tt(w.la, w.S.p, w.Sinv.p, 0);
-    if (rc == MAGI_OK) {
-        hipLaunchKernelGGL(k_fit_gemv, dim3((N + 3) / 4), dim3(256), 0, h->stream, w.Sinv.p, w.r.p, w.alpha.p, N);
-        hipLaunchKernelGGL(k_fit_terms, dim3(w.nblk), dim3(256), 0, h->stream, w.Kap.p, w.pK.p, w.Sinv.p, w.alpha.p, w.r.p, w.I.p, N, w.part.p);
-        hipLaunchKernelGGL(k_fit_final, dim3(1), dim3(256), 0, h->stream, w.part.p, w.nblk, w.out.p);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) rc = magi_fail(h, MAGI_E_HIP, std::string("fit launch: ") + hipGetErrorString(e));
-    }
-    if (rc == MAGI_OK && !dyn) {
-        hipError_t e = hipMemcpyAsync(w.host, w.out.p, 6 * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(w.host_status, w.la.status, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-        if (e != hipSuccess) rc = magi_fail(h, MAGI_E_HIP, std::string("fit readback: ") + hipGetErrorString(e));
-    }
-    h->stream = keep;
-    return rc;
-}
-
-int fit_finish(magi_handle* h, FitWork& w, double phi1, double phi2, double* ll, double* g3) {
-    MAGI_HIP_CHECK(h, hipStreamSynchronize(w.la.s));
-    if (*w.host_status >= 0)
-        return magi_fail(h, MAGI_E_NOTSPD, "Cholesky of GP marginal covariance: non-positive pivot at index " + std::to_string(*w.host_status));
-    const double* o = w.host;
-    const double logdet = 2.0 * o[5];
-    *ll = -0.5 * o[3] - 0.5 * logdet - 0.5 * w.N * std::log(2.0 * 3.141592653589793);
-    g3[0] = 0.5 * o[0] / phi1;
-    g3[1] = 0.5 * o[1] / phi2;
-    g3[2] = 0.5 * (o[4] - o[2]);
+    hipStream_t st = w.stream;
+    int rc = launch_matern(h, st, w.I.p, N, 1.0, 1.0, nu, w.Kap.p, w.pK.p, w.Kpp.p, w.dyn.p, D);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_fit_shift, dim3((unsigned)((nn + 255) / 256), D), dim3(256), 0, st, w.Kap.p, w.S.p, N, 1.0, w.dyn.p);
+    if ((rc = potrf(w.la, w.S.p, "GP marginal covariance", true))) return rc;
+    hipLaunchKernelGGL(k_fit_logdiag, dim3(D), dim3(256), 0, st, w.S.p, N, w.out.p + 5);
+    if ((rc = trtri(w.la, w.S.p))) return rc;
+    if ((rc = lauum_tt(w.la, w.S.p, w.Sinv.p, (long)nn))) return rc;
+    hipLaunchKernelGGL(k_fit_gemv, dim3((N + 3) / 4, D), dim3(256), 0, st, w.Sinv.p, w.r.p, w.alpha.p, N);
+    hipLaunchKernelGGL(k_fit_terms, dim3(w.nblk, D), dim3(256), 0, st, w.Kap.p, w.pK.p, w.Sinv.p, w.alpha.p, w.r.p, w.I.p, N, w.part.p);
+    hipLaunchKernelGGL(k_fit_final, dim3(D), dim3(256), 0, st, w.part.p, w.nblk, w.out.p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("fit launch: ") + hipGetErrorString(e));
     return MAGI_OK;
 }
 
@@ -1343,249 +1317,127 @@ int magi_fused_operators(magi_handle* h, int N, int D, double* dCs_inout_H, cons
 // Adam on the softplus-reparameterised (phi1, phi2, sigma^2) of every component, objective
 // D * sum_d [ GP marginal_d + TruncatedNormal priors_d ]  (the [D, D] broadcast of the reference's
 // log_prob, magi_v2.py:604-608, 649-665, summed by tape.gradient), tf_keras Adam(lr) defaults.
+// Device loop (default): one Adam step of all components = one captured graph (fit_enqueue -> k_fit_step) whose inputs live in
+// the dyn blocks; the host replays it `iters` times and synchronises once.  Host loop (option fit_host_loop, the tests'
+// reference): the same launches per step with the scalar tail and Adam on the host, one synchronisation per step.
 int magi_fit_hparams_device(magi_handle* h, const double* I, int N, int D, const double* X /* [N][D] */, const double* mu,
                             const double* mu_phi2, const double* sd_phi2, const double* sig_loc, double nu, int iters, double lr,
                             double jitter, double* phi1, double* phi2, double* sig2, double* loss_trace) {
-    std::vector<FitWork> ws(D);
-    const size_t nn = (size_t)N * N;
-    int rc = MAGI_OK;
-    auto cleanup = [&]() {
-        for (auto& w : ws) {
-            linalg_free(w.la);
-            if (w.host) (void)hipHostFree(w.host);
-            if (w.host_status) (void)hipHostFree(w.host_status);
-            if (w.exec) (void)hipGraphExecDestroy(w.exec);
-            if (w.graph) (void)hipGraphDestroy(w.graph);
-            if (w.ist) (void)hipFree(w.ist);
-            if (w.stream) (void)hipStreamDestroy(w.stream);
-        }
-    };
-    const bool batched_fit = !h->opt.fit_host_loop && !h->opt.fit_per_component && D <= 8;
-    for (int d = 0; d < D && rc == MAGI_OK && !batched_fit; ++d) {
-        FitWork& w = ws[d];
-        w.N = N;
-        w.nblk = (N + 3) / 4;
-        hipError_t e = hipSuccess;
-        auto chk = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-        chk(w.I.alloc(N)); chk(w.r.alloc(N)); chk(w.Kap.alloc(nn)); chk(w.pK.alloc(nn)); chk(w.Kpp.alloc(nn)); chk(w.S.alloc(nn));
-        chk(w.Sinv.alloc(nn)); chk(w.alpha.alloc(N)); chk(w.part.alloc((size_t)w.nblk * 5)); chk(w.out.alloc(8));
-        chk(hipHostMalloc(reinterpret_cast<void**>(&w.host), 8 * sizeof(double)));
-        chk(hipHostMalloc(reinterpret_cast<void**>(&w.host_status), sizeof(int)));
-        chk(hipStreamCreate(&w.stream));
-        if (e == hipSuccess) chk(hipMemcpy(w.I.p, I, sizeof(double) * N, hipMemcpyHostToDevice));
-        std::vector<double> r((size_t)N);
-        for (int i = 0; i < N; ++i) r[i] = X[(size_t)i * D + d] - mu[d];
-        if (e == hipSuccess) chk(hipMemcpy(w.r.p, r.data(), sizeof(double) * N, hipMemcpyHostToDevice));
-        if (e != hipSuccess) { rc = magi_fail(h, MAGI_E_HIP, std::string("fit setup: ") + hipGetErrorString(e)); break; }
-        rc = linalg_init(w.la, h, N);
-        w.la.s = w.stream;
-    }
-    if (rc) { cleanup(); return rc; }
-
+    h->prof.on = false;           // (the profile's events synchronise: never inside a capture)
+    const size_t nn = (size_t)N * N, ntr = (size_t)D * std::max(iters, 1);
+    const double lgam = std::lgamma(nu);
     auto softplus = [](double x) { return std::log1p(std::exp(x)); };
     auto softplus_inv = [](double y) { return std::log(std::expm1(y)); };
     auto sigmoid = [](double x) { return 1.0 / (1.0 + std::exp(-x)); };
-    // raw variables, order [phi1(D), phi2(D), sig2(D)] ; Adam state
-    std::vector<double> raw(3 * D), m(3 * D, 0.0), v(3 * D, 0.0), grad(3 * D);
+    auto pivot_fail = [&](int d, int t, int index) {
+        return magi_fail(h, MAGI_E_NOTSPD, "Cholesky of GP marginal covariance (component " + std::to_string(d) + ", Adam step " + std::to_string(t) +
+                                           "): non-positive pivot at index " + std::to_string(index));
+    };
+    // raw variables, order [phi1(D), phi2(D), sig2(D)]
+    std::vector<double> raw(3 * D);
     for (int d = 0; d < D; ++d) { raw[d] = softplus_inv(phi1[d]); raw[D + d] = softplus_inv(phi2[d]); raw[2 * D + d] = softplus_inv(sig2[d]); }
-    if (batched_fit) {
-        // Round 3 -- ONE captured graph per Adam step for ALL components: the components go through the same launches, so every kernel of
-        // the step carries them on a grid axis (Matern blocks, shift, the batched Cholesky / inverse of the matrix build, the reductions,
-        // the scalar tail), their hyper-parameters in per-component FitDyn blocks FD_COUNT apart.  (Round 1 / 2: one graph per component
-        // on four streams that share two hardware queues -- MAGI_FIT_PER_COMPONENT=1 keeps that path for comparison.)
-        g_prof.on = false;
-        ws.clear();                                                   // (no per-component work spaces on this path)
-        DevBuf bI, br, bKap, bpK, bKpp, bS, bSinv, balpha, bpart, bout, bdyn, btrace;
-        int* ist = nullptr;
-        hipStream_t st = nullptr;
-        hipGraph_t graph = nullptr;
-        hipGraphExec_t exec = nullptr;
-        Linalg la{};
-        const int nblk = (N + 3) / 4;
-        hipError_t e = hipSuccess;
-        auto chk = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-        chk(bI.alloc(N)); chk(br.alloc((size_t)D * N)); chk(bKap.alloc(nn * D)); chk(bpK.alloc(nn * D)); chk(bKpp.alloc(nn * D)); chk(bS.alloc(nn * D));
-        chk(bSinv.alloc(nn * D)); chk(balpha.alloc((size_t)D * N)); chk(bpart.alloc((size_t)D * nblk * 5)); chk(bout.alloc((size_t)D * 8));
-        chk(bdyn.alloc((size_t)D * FD_COUNT)); chk(btrace.alloc((size_t)D * std::max(iters, 1)));
-        chk(hipMalloc(reinterpret_cast<void**>(&ist), (size_t)D * 4 * sizeof(int)));
-        chk(hipStreamCreate(&st));
-        std::vector<double> rr((size_t)D * N), init((size_t)D * FD_COUNT, 0.0);
-        std::vector<int> ist0((size_t)D * 4, 0);
-        for (int d = 0; d < D; ++d) {
-            for (int i = 0; i < N; ++i) rr[(size_t)d * N + i] = X[(size_t)i * D + d] - mu[d];
-            for (int k = 0; k < 3; ++k) init[(size_t)d * FD_COUNT + FD_RAW + k] = raw[(size_t)k * D + d];
-            ist0[(size_t)d * 4 + 1] = -1;
-        }
-        if (e == hipSuccess) chk(hipMemcpy(bI.p, I, sizeof(double) * N, hipMemcpyHostToDevice));
-        if (e == hipSuccess) chk(hipMemcpy(br.p, rr.data(), sizeof(double) * rr.size(), hipMemcpyHostToDevice));
-        if (e == hipSuccess) chk(hipMemcpy(bdyn.p, init.data(), sizeof(double) * init.size(), hipMemcpyHostToDevice));
-        if (e == hipSuccess) chk(hipMemcpy(ist, ist0.data(), sizeof(int) * ist0.size(), hipMemcpyHostToDevice));
-        if (e == hipSuccess) chk(hipMemset(btrace.p, 0, (size_t)D * std::max(iters, 1) * sizeof(double)));
-        if (e != hipSuccess) rc = magi_fail(h, MAGI_E_HIP, std::string("fit setup: ") + hipGetErrorString(e));
-        if (rc == MAGI_OK) { rc = linalg_init(la, h, N, D, (long)nn); la.s = st; }
-        FitStepArgs sa{};
-        if (rc == MAGI_OK) {
-            sa.dyn = bdyn.p; sa.ist = ist; sa.out = bout.p; sa.status = la.status; sa.trace = btrace.p; sa.N = N; sa.D = D;
-            sa.nu = nu; sa.lgam_nu = std::lgamma(nu); sa.lr = lr; sa.jitter = jitter; sa.batched = 1; sa.iters = std::max(iters, 1);
-            for (int d = 0; d < D; ++d) { sa.mu_phi2_z[d] = mu_phi2[d]; sa.sd_phi2_z[d] = sd_phi2[d]; sa.sig_loc_z[d] = sig_loc[d]; }
-            hipLaunchKernelGGL(k_fit_step, dim3(D), dim3(64), 0, st, sa);             // t = 0: derive the first hyper-parameters
-            hipStream_t keep = h->stream;
-            h->stream = st;                                                           // (the helpers below launch on the handle's stream)
-            chk(hipStreamBeginCapture(st, hipStreamCaptureModeThreadLocal));
-            if (e == hipSuccess) {
-                rc = launch_matern(h, bI.p, N, 1.0, 1.0, nu, bKap.p, bpK.p, bKpp.p, bdyn.p, D);
-                if (rc == MAGI_OK) {
-                    hipLaunchKernelGGL(k_fit_shift, dim3((unsigned)((nn + 255) / 256), D), dim3(256), 0, st, bKap.p, bS.p, N, 1.0, bdyn.p);
-                    rc = potrf(la, bS.p, "GP marginal covariance", true);
-                }
-                if (rc == MAGI_OK) {
-                    hipLaunchKernelGGL(k_fit_logdiag, dim3(D), dim3(256), 0, st, bS.p, N, bout.p + 5);
-                    rc = trtri(la, bS.p);
-                }
-                if (rc == MAGI_OK) rc = lauum_tt(la, bS.p, bSinv.p, (long)nn);
-                if (rc == MAGI_OK) {
-                    hipLaunchKernelGGL(k_fit_gemv, dim3((N + 3) / 4, D), dim3(256), 0, st, bSinv.p, br.p, balpha.p, N);
-                    hipLaunchKernelGGL(k_fit_terms, dim3(nblk, D), dim3(256), 0, st, bKap.p, bpK.p, bSinv.p, balpha.p, br.p, bI.p, N, bpart.p);
-                    hipLaunchKernelGGL(k_fit_final, dim3(D), dim3(256), 0, st, bpart.p, nblk, bout.p);
-                    hipLaunchKernelGGL(k_fit_step, dim3(D), dim3(64), 0, st, sa);
-                }
-                chk(hipStreamEndCapture(st, &graph));
-            }
-            h->stream = keep;
-            if (e == hipSuccess && rc == MAGI_OK) chk(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-            if (e != hipSuccess && rc == MAGI_OK) rc = magi_fail(h, MAGI_E_HIP, std::string("fit graph: ") + hipGetErrorString(e));
-        }
-        for (int t = 1; t <= iters && rc == MAGI_OK; ++t)
-            if (hipGraphLaunch(exec, st) != hipSuccess) rc = magi_fail(h, MAGI_E_HIP, "fit graph launch");
-        std::vector<double> tr((size_t)std::max(iters, 1) * D, 0.0), fin((size_t)D * FD_COUNT, 0.0);
-        std::vector<int> istv((size_t)D * 4, 0);
-        if (st) (void)hipStreamSynchronize(st);
-        if (rc == MAGI_OK) {
-            hipError_t e2 = hipMemcpy(fin.data(), bdyn.p, sizeof(double) * fin.size(), hipMemcpyDeviceToHost);
-            if (e2 == hipSuccess) e2 = hipMemcpy(istv.data(), ist, sizeof(int) * istv.size(), hipMemcpyDeviceToHost);
-            if (e2 == hipSuccess && iters > 0) e2 = hipMemcpy(tr.data(), btrace.p, (size_t)iters * D * sizeof(double), hipMemcpyDeviceToHost);
-            if (e2 != hipSuccess) rc = magi_fail(h, MAGI_E_HIP, std::string("fit: ") + hipGetErrorString(e2));
-        }
-        for (int d = 0; d < D && rc == MAGI_OK; ++d) {
-            if (istv[(size_t)d * 4 + 1] >= 0)
-                rc = magi_fail(h, MAGI_E_NOTSPD, "Cholesky of GP marginal covariance (component " + std::to_string(d) + ", Adam step " + std::to_string(istv[(size_t)d * 4 + 2]) +
-                               "): non-positive pivot at index " + std::to_string(istv[(size_t)d * 4 + 1]));
-            for (int k = 0; k < 3; ++k) raw[(size_t)k * D + d] = fin[(size_t)d * FD_COUNT + FD_RAW + k];
-        }
-        if (exec) (void)hipGraphExecDestroy(exec);
-        if (graph) (void)hipGraphDestroy(graph);
-        linalg_free(la);
-        if (ist) (void)hipFree(ist);
-        if (st) (void)hipStreamDestroy(st);
-        if (rc) return rc;
-        if (loss_trace)
-            for (int t = 0; t < iters; ++t) {
-                double loss = 0.0;
-                for (int d = 0; d < D; ++d) loss -= tr[(size_t)d * iters + t];
-                loss_trace[t] = loss;
-            }
-        for (int d = 0; d < D; ++d) { phi1[d] = softplus(raw[d]); phi2[d] = softplus(raw[D + d]); sig2[d] = softplus(raw[2 * D + d]); }
-        return MAGI_OK;
+
+    // set-up: blocking copies on the null stream, which the fit's (blocking) stream is ordered against
+    FitBatch w;
+    w.N = N; w.D = D; w.nblk = (N + 3) / 4;
+    std::vector<double> rr((size_t)D * N), dyn((size_t)D * FD_COUNT, 0.0), tr(ntr, 0.0);
+    std::vector<int> ist((size_t)D * 4, 0);
+    for (int d = 0; d < D; ++d) {
+        for (int i = 0; i < N; ++i) rr[(size_t)d * N + i] = X[(size_t)i * D + d] - mu[d];
+        double* b = &dyn[(size_t)d * FD_COUNT];
+        for (int k = 0; k < 3; ++k) b[FD_RAW + k] = raw[(size_t)k * D + d];
+        b[FD_MU_PHI2] = mu_phi2[d]; b[FD_SD_PHI2] = sd_phi2[d]; b[FD_SIG_LOC] = sig_loc[d];
+        ist[(size_t)d * 4 + 1] = -1;
     }
-    if (!h->opt.fit_host_loop) {
-        // Device-resident loop: one Adam step of one component = one captured graph (Matern blocks -> Cholesky -> inverse ->
-        // reductions -> k_fit_step) whose inputs live in the component's FitDyn block; the host replays it `iters` times on
-        // the component's stream and synchronises once at the end.
-        g_prof.on = false;                                            // (its events would synchronise inside the capture)
-        const double lgam = std::lgamma(nu);
-        for (int d = 0; d < D && rc == MAGI_OK; ++d) {
-            FitWork& w = ws[d];
-            hipError_t e = hipSuccess;
-            auto chk = [&](hipError_t x) { if (e == hipSuccess) e = x; };
-            chk(w.dyn.alloc(FD_COUNT)); chk(w.trace.alloc((size_t)std::max(iters, 1)));
-            chk(hipMalloc(reinterpret_cast<void**>(&w.ist), 4 * sizeof(int)));
-            double init[FD_COUNT] = {0.0};
-            for (int k = 0; k < 3; ++k) init[FD_RAW + k] = raw[(size_t)k * D + d];
-            const int ist0[4] = {0, -1, 0, 0};
-            if (e == hipSuccess) chk(hipMemcpy(w.dyn.p, init, sizeof(init), hipMemcpyHostToDevice));
-            if (e == hipSuccess) chk(hipMemcpy(w.ist, ist0, sizeof(ist0), hipMemcpyHostToDevice));
-            if (e == hipSuccess) chk(hipMemset(w.trace.p, 0, (size_t)std::max(iters, 1) * sizeof(double)));
-            if (e != hipSuccess) { rc = magi_fail(h, MAGI_E_HIP, std::string("fit setup: ") + hipGetErrorString(e)); break; }
-            FitStepArgs sa{};
-            sa.dyn = w.dyn.p; sa.ist = w.ist; sa.out = w.out.p; sa.status = w.la.status; sa.trace = w.trace.p; sa.N = N; sa.D = D;
-            sa.nu = nu; sa.lgam_nu = lgam; sa.mu_phi2 = mu_phi2[d]; sa.sd_phi2 = sd_phi2[d]; sa.sig_loc = sig_loc[d]; sa.lr = lr; sa.jitter = jitter;
-            hipLaunchKernelGGL(k_fit_step, dim3(1), dim3(64), 0, w.stream, sa);          // t = 0: derive the first hyper-parameters
-            chk(hipStreamBeginCapture(w.stream, hipStreamCaptureModeThreadLocal));
-            if (e == hipSuccess) {
-                rc = fit_issue(h, w, 1.0, 1.0, 1.0, nu, jitter, w.dyn.p);
-                hipLaunchKernelGGL(k_fit_step, dim3(1), dim3(64), 0, w.stream, sa);
-                chk(hipStreamEndCapture(w.stream, &w.graph));
-            }
-            if (e == hipSuccess && rc == MAGI_OK) chk(hipGraphInstantiate(&w.exec, w.graph, nullptr, nullptr, 0));
-            if (e != hipSuccess && rc == MAGI_OK) rc = magi_fail(h, MAGI_E_HIP, std::string("fit graph: ") + hipGetErrorString(e));
-        }
-        for (int t = 1; t <= iters && rc == MAGI_OK; ++t)
-            for (int d = 0; d < D && rc == MAGI_OK; ++d)
-                if (hipGraphLaunch(ws[d].exec, ws[d].stream) != hipSuccess) rc = magi_fail(h, MAGI_E_HIP, "fit graph launch");
-        std::vector<double> tr((size_t)std::max(iters, 1) * D, 0.0);
-        for (int d = 0; d < D && rc == MAGI_OK; ++d) {
-            FitWork& w = ws[d];
-            hipError_t e = hipStreamSynchronize(w.stream);
-            double fin[FD_COUNT]; int ist[4] = {0, -1, 0, 0};
-            if (e == hipSuccess) e = hipMemcpy(fin, w.dyn.p, sizeof(fin), hipMemcpyDeviceToHost);
-            if (e == hipSuccess) e = hipMemcpy(ist, w.ist, sizeof(ist), hipMemcpyDeviceToHost);
-            if (e == hipSuccess && iters > 0) e = hipMemcpy(tr.data() + (size_t)d * iters, w.trace.p, (size_t)iters * sizeof(double), hipMemcpyDeviceToHost);
-            if (e != hipSuccess) { rc = magi_fail(h, MAGI_E_HIP, std::string("fit: ") + hipGetErrorString(e)); break; }
-            if (ist[1] >= 0) {
-                rc = magi_fail(h, MAGI_E_NOTSPD, "Cholesky of GP marginal covariance (component " + std::to_string(d) + ", Adam step " + std::to_string(ist[2]) +
-                               "): non-positive pivot at index " + std::to_string(ist[1]));
-                break;
-            }
-            for (int k = 0; k < 3; ++k) raw[(size_t)k * D + d] = fin[FD_RAW + k];
-        }
-        for (auto& w : ws) (void)hipStreamSynchronize(w.stream);
-        cleanup();
-        if (rc) return rc;
-        if (loss_trace)
-            for (int t = 0; t < iters; ++t) {
-                double loss = 0.0;
-                for (int d = 0; d < D; ++d) loss -= tr[(size_t)d * iters + t];
-                loss_trace[t] = loss;
-            }
-        for (int d = 0; d < D; ++d) { phi1[d] = softplus(raw[d]); phi2[d] = softplus(raw[D + d]); sig2[d] = softplus(raw[2 * D + d]); }
-        return MAGI_OK;
-    }
-    // host loop (MAGI_FIT_HOST_LOOP=1): the same arithmetic with the scalar tail and Adam on the host, one synchronisation per step
-    const double sD = std::sqrt((double)D);
-    const double b1 = 0.9, b2 = 0.999, eps = 1e-7;
-    std::vector<double> pv(3 * D);
-    for (int t = 1; t <= iters && rc == MAGI_OK; ++t) {
-        double loss = 0.0;
-        for (int d = 0; d < D && rc == MAGI_OK; ++d) {             // enqueue all components, then collect
-            pv[d] = softplus(raw[d]); pv[D + d] = softplus(raw[D + d]); pv[2 * D + d] = softplus(raw[2 * D + d]);
-            rc = fit_issue(h, ws[d], pv[d], pv[D + d], pv[2 * D + d], nu, jitter);
-        }
-        for (int d = 0; d < D && rc == MAGI_OK; ++d) {
-            const double p1 = pv[d], p2 = pv[D + d], s2 = pv[2 * D + d];
-            double ll, g3[3];
-            rc = fit_finish(h, ws[d], p1, p2, &ll, g3);
-            if (rc) break;
-            // TruncatedNormal(loc, scale, low = 1e-6) priors: only the quadratic depends on the value (magi_v2.py:611-627)
-            const double sc1 = 1000.0 * sD, sc2 = sd_phi2[d] * sD, sc3 = 1000.0 * sD;
-            const double z1 = (p1 - 1e-4) / sc1, z2 = (p2 - mu_phi2[d]) / sc2, z3 = (s2 - sig_loc[d]) / sc3;
-            const double lp = -0.5 * (z1 * z1 + z2 * z2 + z3 * z3);
-            loss -= D * (ll + lp);
-            grad[d] = -D * (g3[0] - z1 / sc1) * sigmoid(raw[d]);
-            grad[D + d] = -D * (g3[1] - z2 / sc2) * sigmoid(raw[D + d]);
-            grad[2 * D + d] = -D * (g3[2] - z3 / sc3) * sigmoid(raw[2 * D + d]);
-        }
-        if (rc) break;
-        if (loss_trace) loss_trace[t - 1] = loss;
-        const double a = lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t));
-        for (int k = 0; k < 3 * D; ++k) {
-            m[k] = b1 * m[k] + (1.0 - b1) * grad[k];
-            v[k] = b2 * v[k] + (1.0 - b2) * grad[k] * grad[k];
-            raw[k] -= a * m[k] / (std::sqrt(v[k]) + eps);
-        }
-    }
-    for (auto& w : ws) (void)hipStreamSynchronize(w.stream);
-    cleanup();
+    MAGI_HIP_CHECK(h, w.I.alloc(N)); MAGI_HIP_CHECK(h, w.r.alloc((size_t)D * N)); MAGI_HIP_CHECK(h, w.alpha.alloc((size_t)D * N));
+    MAGI_HIP_CHECK(h, w.Kap.alloc(nn * D)); MAGI_HIP_CHECK(h, w.pK.alloc(nn * D)); MAGI_HIP_CHECK(h, w.Kpp.alloc(nn * D));
+    MAGI_HIP_CHECK(h, w.S.alloc(nn * D)); MAGI_HIP_CHECK(h, w.Sinv.alloc(nn * D));
+    MAGI_HIP_CHECK(h, w.part.alloc((size_t)D * w.nblk * 5)); MAGI_HIP_CHECK(h, w.out.alloc((size_t)D * 8));
+    MAGI_HIP_CHECK(h, w.dyn.alloc(dyn.size())); MAGI_HIP_CHECK(h, w.trace.alloc(ntr));
+    MAGI_HIP_CHECK(h, hipMalloc(reinterpret_cast<void**>(&w.ist), ist.size() * sizeof(int)));
+    MAGI_HIP_CHECK(h, hipStreamCreate(&w.stream));
+    MAGI_HIP_CHECK(h, hipMemcpy(w.I.p, I, sizeof(double) * N, hipMemcpyHostToDevice));
+    MAGI_HIP_CHECK(h, hipMemcpy(w.r.p, rr.data(), sizeof(double) * rr.size(), hipMemcpyHostToDevice));
+    MAGI_HIP_CHECK(h, hipMemcpy(w.dyn.p, dyn.data(), sizeof(double) * dyn.size(), hipMemcpyHostToDevice));
+    MAGI_HIP_CHECK(h, hipMemcpy(w.ist, ist.data(), sizeof(int) * ist.size(), hipMemcpyHostToDevice));
+    MAGI_HIP_CHECK(h, hipMemset(w.trace.p, 0, ntr * sizeof(double)));
+    int rc = linalg_init(w.la, h, N, D, (long)nn);
     if (rc) return rc;
+    w.la.s = w.stream;
+
+    if (!h->opt.fit_host_loop) {
+        FitStepArgs sa{};
+        sa.dyn = w.dyn.p; sa.ist = w.ist; sa.out = w.out.p; sa.status = w.la.status; sa.trace = w.trace.p; sa.N = N; sa.D = D;
+        sa.iters = std::max(iters, 1); sa.nu = nu; sa.lgam_nu = lgam; sa.lr = lr; sa.jitter = jitter;
+        hipLaunchKernelGGL(k_fit_step, dim3(D), dim3(64), 0, w.stream, sa);             // t = 0: derive the first hyper-parameters
+        MAGI_HIP_CHECK(h, hipStreamBeginCapture(w.stream, hipStreamCaptureModeThreadLocal));
+        rc = fit_enqueue(h, w, nu);
+        if (rc == MAGI_OK) hipLaunchKernelGGL(k_fit_step, dim3(D), dim3(64), 0, w.stream, sa);
+        hipError_t e = hipStreamEndCapture(w.stream, &w.graph);                          // (also after an error: the stream must leave capture mode)
+        if (rc) return rc;
+        if (e == hipSuccess) e = hipGraphInstantiate(&w.exec, w.graph, nullptr, nullptr, 0);
+        if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("fit graph: ") + hipGetErrorString(e));
+        for (int t = 1; t <= iters; ++t)
+            if (hipGraphLaunch(w.exec, w.stream) != hipSuccess) return magi_fail(h, MAGI_E_HIP, "fit graph launch");
+        MAGI_HIP_CHECK(h, hipStreamSynchronize(w.stream));
+        MAGI_HIP_CHECK(h, hipMemcpy(dyn.data(), w.dyn.p, sizeof(double) * dyn.size(), hipMemcpyDeviceToHost));
+        MAGI_HIP_CHECK(h, hipMemcpy(ist.data(), w.ist, sizeof(int) * ist.size(), hipMemcpyDeviceToHost));
+        MAGI_HIP_CHECK(h, hipMemcpy(tr.data(), w.trace.p, ntr * sizeof(double), hipMemcpyDeviceToHost));
+        for (int d = 0; d < D; ++d) {
+            if (ist[(size_t)d * 4 + 1] >= 0) return pivot_fail(d, ist[(size_t)d * 4 + 2], ist[(size_t)d * 4 + 1]);
+            for (int k = 0; k < 3; ++k) raw[(size_t)k * D + d] = dyn[(size_t)d * FD_COUNT + FD_RAW + k];
+        }
+    } else {
+        const double sD = std::sqrt((double)D);
+        const double b1 = 0.9, b2 = 0.999, eps = 1e-7;
+        std::vector<double> m(3 * D, 0.0), v(3 * D, 0.0), grad(3 * D), out((size_t)D * 8);
+        std::vector<int> status((size_t)D * 2);
+        for (int t = 1; t <= iters; ++t) {
+            for (int d = 0; d < D; ++d) {          // what k_fit_step derives on the device, in host libm
+                double* b = &dyn[(size_t)d * FD_COUNT];
+                for (int k = 0; k < 3; ++k) b[FD_PV + k] = softplus(raw[(size_t)k * D + d]);
+                const double p1 = b[FD_PV], p2 = b[FD_PV + 1], s2 = b[FD_PV + 2];
+                b[FD_C] = std::sqrt(2.0 * nu) / p2;
+                b[FD_LOGA] = std::log(p1) + (1.0 - nu) * std::log(2.0) - lgam;
+                b[FD_DIAGPP] = nu * p1 / ((p2 * p2) * (nu - 1.0));
+                b[FD_SHIFT] = s2 + jitter;
+            }
+            MAGI_HIP_CHECK(h, hipMemcpy(w.dyn.p, dyn.data(), sizeof(double) * dyn.size(), hipMemcpyHostToDevice));
+            if ((rc = fit_enqueue(h, w, nu))) return rc;
+            MAGI_HIP_CHECK(h, hipMemcpyAsync(out.data(), w.out.p, sizeof(double) * out.size(), hipMemcpyDeviceToHost, w.stream));
+            MAGI_HIP_CHECK(h, hipMemcpyAsync(status.data(), w.la.status, sizeof(int) * status.size(), hipMemcpyDeviceToHost, w.stream));
+            MAGI_HIP_CHECK(h, hipStreamSynchronize(w.stream));
+            for (int d = 0; d < D; ++d) {
+                if (status[(size_t)2 * d] >= 0) return pivot_fail(d, t, status[(size_t)2 * d]);
+                const double* b = &dyn[(size_t)d * FD_COUNT];
+                const double p1 = b[FD_PV], p2 = b[FD_PV + 1], s2 = b[FD_PV + 2];
+                const double* o = &out[(size_t)d * 8];
+                const double logdet = 2.0 * o[5];
+                const double ll = -0.5 * o[3] - 0.5 * logdet - 0.5 * N * std::log(2.0 * 3.141592653589793);
+                const double g3[3] = {0.5 * o[0] / p1, 0.5 * o[1] / p2, 0.5 * (o[4] - o[2])};
+                // TruncatedNormal(loc, scale, low = 1e-6) priors: only the quadratic depends on the value (magi_v2.py:611-627)
+                const double sc1 = 1000.0 * sD, sc2 = sd_phi2[d] * sD, sc3 = 1000.0 * sD;
+                const double z1 = (p1 - 1e-4) / sc1, z2 = (p2 - mu_phi2[d]) / sc2, z3 = (s2 - sig_loc[d]) / sc3;
+                const double lp = -0.5 * (z1 * z1 + z2 * z2 + z3 * z3);
+                tr[(size_t)d * iters + t - 1] = D * (ll + lp);
+                grad[d] = -D * (g3[0] - z1 / sc1) * sigmoid(raw[d]);
+                grad[D + d] = -D * (g3[1] - z2 / sc2) * sigmoid(raw[D + d]);
+                grad[2 * D + d] = -D * (g3[2] - z3 / sc3) * sigmoid(raw[2 * D + d]);
+            }
+            const double a = lr * std::sqrt(1.0 - std::pow(b2, t)) / (1.0 - std::pow(b1, t));
+            for (int k = 0; k < 3 * D; ++k) {
+                m[k] = b1 * m[k] + (1.0 - b1) * grad[k];
+                v[k] = b2 * v[k] + (1.0 - b2) * grad[k] * grad[k];
+                raw[k] -= a * m[k] / (std::sqrt(v[k]) + eps);
+            }
+        }
+    }
+    if (loss_trace)
+        for (int t = 0; t < iters; ++t) {
+            double loss = 0.0;
+            for (int d = 0; d < D; ++d) loss -= tr[(size_t)d * iters + t];
+            loss_trace[t] = loss;
+        }
     for (int d = 0; d < D; ++d) { phi1[d] = softplus(raw[d]); phi2[d] = softplus(raw[D + d]); sig2[d] = softplus(raw[2 * D + d]); }
     return MAGI_OK;
 }
@@ -1600,7 +1452,7 @@ int magi_matern_blocks_device(magi_handle* h, const double* I, int N, double phi
     MAGI_HIP_CHECK(h, dP.alloc(nn));
     MAGI_HIP_CHECK(h, dPP.alloc(nn));
     MAGI_HIP_CHECK(h, hipMemcpy(dI.p, I, sizeof(double) * N, hipMemcpyHostToDevice));
-    int rc = launch_matern(h, dI.p, N, phi1, phi2, nu, dK.p, dP.p, dPP.p);
+    int rc = launch_matern(h, h->stream, dI.p, N, phi1, phi2, nu, dK.p, dP.p, dPP.p);
     if (rc) return rc;
     MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     if (Kappa) MAGI_HIP_CHECK(h, hipMemcpy(Kappa, dK.p, nn * sizeof(double), hipMemcpyDeviceToHost));
@@ -1610,9 +1462,9 @@ int magi_matern_blocks_device(magi_handle* h, const double* I, int N, double phi
 }
 
 int magi_build_profile_get(const magi_handle* h, double* flops, double* ms, long* calls) {
-    for (int i = 0; i < BC_COUNT; ++i) { flops[i] = g_prof.flops[i]; ms[i] = g_prof.ms[i]; calls[i] = g_prof.calls[i]; }
+    for (int i = 0; i < BC_COUNT; ++i) { flops[i] = h->prof.flops[i]; ms[i] = h->prof.ms[i]; calls[i] = h->prof.calls[i]; }
     // one more row, filled by EVERY dense build of this handle: its two factorisations as a whole (N^3 / 3 flops per matrix)
-    flops[BC_COUNT] = h ? h->potrf_wall_flops : 0.0; ms[BC_COUNT] = h ? h->potrf_wall_ms : 0.0; calls[BC_COUNT] = h && h->potrf_wall_ms > 0.0 ? 2 : 0;
+    flops[BC_COUNT] = h->potrf_wall_flops; ms[BC_COUNT] = h->potrf_wall_ms; calls[BC_COUNT] = h->potrf_wall_ms > 0.0 ? 2 : 0;
     return BC_COUNT + 1;
 }
 
@@ -1638,10 +1490,12 @@ int magi_ensure_dense(magi_handle* h, int N, int D) {
 // Eqn. 6 matrices of the components sel[0 .. n_sel) (phi1 / phi2 indexed like sel) into the handle's dense stacks
 int magi_build_dense_device(magi_handle* h, const double* I, int N, int D, int n_sel, const int* sel, const double* phi1, const double* phi2,
                             double nu) {
-    g_prof.on = h->opt.build_profile != 0;
-    if (g_prof.on) {
-        if (!g_prof.e0) { (void)hipEventCreate(&g_prof.e0); (void)hipEventCreate(&g_prof.e1); }
-        for (int i = 0; i < BC_COUNT; ++i) { g_prof.flops[i] = 0.0; g_prof.ms[i] = 0.0; g_prof.calls[i] = 0; }
+    BuildProfile& prof = h->prof;
+    prof.on = h->opt.build_profile != 0;
+    if (prof.on) {
+        if (!prof.e0) (void)hipEventCreate(&prof.e0);
+        if (!prof.e1) (void)hipEventCreate(&prof.e1);
+        for (int i = 0; i < BC_COUNT; ++i) { prof.flops[i] = 0.0; prof.ms[i] = 0.0; prof.calls[i] = 0; }
     }
     for (int d = 0; d < n_sel; ++d) {
         if (!(phi1[d] > 0.0) || !(phi2[d] > 0.0)) return magi_fail(h, MAGI_E_BADARG, "phi1 and phi2 must be positive");
@@ -1681,7 +1535,7 @@ int magi_build_dense_device(magi_handle* h, const double* I, int N, int D, int n
         while (nb < B && d0 + nb < n_sel && sel[d0 + nb] == sel[d0 + nb - 1] + 1) ++nb;
         la.batch = nb;
         for (int z = 0; z < nb && rc == MAGI_OK; ++z)
-            rc = launch_matern(h, dI.p, N, phi1[d0 + z], phi2[d0 + z], nu, Kap.p + nn * z, P.p + nn * z, PP.p + nn * z);
+            rc = launch_matern(h, la.s, dI.p, N, phi1[d0 + z], phi2[d0 + z], nu, Kap.p + nn * z, P.p + nn * z, PP.p + nn * z);
         double* Cd = h->dDense[0] + nn * sel[d0];
         double* Md = h->dDense[1] + nn * sel[d0];
         double* Kd = h->dDense[2] + nn * sel[d0];

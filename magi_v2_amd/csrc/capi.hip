@@ -134,7 +134,6 @@ const OptRow kOptions[] = {
     {"potrf_lookahead_min", "MAGI_POTRF_LOOKAHEAD_MIN", RANGE,  0, INT64_MAX, store<&MagiOptions::potrf_lookahead_min>},
     {"no_graph",            "MAGI_NO_GRAPH",            FLAG,   0, 1,         store<&MagiOptions::no_graph>},
     {"fit_host_loop",       "MAGI_FIT_HOST_LOOP",       FLAG,   0, 1,         store<&MagiOptions::fit_host_loop>},
-    {"fit_per_component",   "MAGI_FIT_PER_COMPONENT",   FLAG,   0, 1,         store<&MagiOptions::fit_per_component>},
     {"build_profile",       "MAGI_BUILD_PROFILE",       FLAG,   0, 1,         store<&MagiOptions::build_profile>},
     {"build_serial",        "MAGI_BUILD_SERIAL",        FLAG,   0, 1,         store<&MagiOptions::build_serial>},
     {"slot_budget_graphs",  nullptr,                    CLAMP,  0, INT64_MAX, store<&MagiOptions::slot_budget_graphs>},
@@ -330,6 +329,8 @@ void magi_destroy(magi_handle* h) {
     for (int i = 0; i < 3; ++i) if (h->ev_la[i]) (void)hipEventDestroy(h->ev_la[i]);
     if (h->stream_chain) (void)hipStreamDestroy(h->stream_chain);
     for (int i = 0; i < 4; ++i) if (h->ev_pw[i]) (void)hipEventDestroy(h->ev_pw[i]);
+    if (h->prof.e0) (void)hipEventDestroy(h->prof.e0);
+    if (h->prof.e1) (void)hipEventDestroy(h->prof.e1);
     if (h->stream_trail) (void)hipStreamDestroy(h->stream_trail);
     if (h->stream) (void)hipStreamDestroy(h->stream);
     delete h;

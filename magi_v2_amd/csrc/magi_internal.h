@@ -915,13 +915,23 @@ struct MagiOptions {
     int potrf_lookahead_min = 4096;     // build.hip: grids from this size on factorise with look-ahead (0: never), see potrf
     long long slot_budget_graphs = 0;   // TEST HOOK: cap on the graph launches of one magi_sampler_run (0 = the computed bound)
     int no_graph = 0;                   // launch the leapfrog slots directly (debugging, long rocprofv3 kernel traces)
-    int fit_host_loop = 0, fit_per_component = 0;      // build.hip: A/B paths of the hyper-parameter fit
+    int fit_host_loop = 0;              // build.hip: the hyper-parameter fit with its scalar tail on the host (the tests' reference)
     int build_profile = 0, build_serial = 0;           // build.hip: per-class device times (serialises), one component per group
 };
 void magi_options_from_env(MagiOptions& o);               // capi.hip
 
 // The streaming kernels: k_stream<1>, k_stream<2> (VALU), k_stream_mc, k_stream_sep<CW = 8 | 16> (matrix cores)
 enum class StreamKernel { Valu1, Valu2, Mc, Sep8, Sep16 };
+
+// optional per-class timing of the build (MAGI_BUILD_PROFILE=1): HIP events around every launch, so the
+// build is serialised and slower -- diagnostics only
+enum BuildClass { BC_MATERN = 0, BC_DIAG, BC_PANEL, BC_TRAIL, BC_TRTRI, BC_LAUUM, BC_PROD, BC_FUSED, BC_COUNT };
+struct BuildProfile {
+    double flops[BC_COUNT] = {}, ms[BC_COUNT] = {};
+    long calls[BC_COUNT] = {};
+    bool on = false;                    // armed by a dense build with opt.build_profile (and through the pack that follows), disarmed by a fit
+    hipEvent_t e0 = nullptr, e1 = nullptr;      // created on the handle's device by the first profiled build
+};
 
 struct magi_handle {
     int device = 0;
@@ -984,6 +994,7 @@ struct magi_handle {
     bool trail_unavailable = false;  // the masked stream could not be created: factorise without look-ahead
     hipEvent_t ev_pw[4] = {nullptr, nullptr, nullptr, nullptr};      // begin / end of the two factorisations of a dense build
     double potrf_wall_ms = 0.0, potrf_wall_flops = 0.0;              // of the last dense build (whole factorisations, not serialised)
+    BuildProfile prof;                                               // of the last profiled dense build of THIS handle (build.hip)
     size_t apply_pin_cap = 0;
     // problem group (magi_group_create): group_n > 0 members whose chains this handle samples; it has no matrices of its own
     int group_n = 0;

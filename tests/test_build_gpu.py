@@ -132,6 +132,30 @@ def test_concurrent_and_serial_component_builds_are_identical(eng):
         assert np.array_equal(a, b)
 
 
+def test_build_profile_belongs_to_the_handle():
+    """Two engines in one process: a profiled build on B, and then an unprofiled one, leave every row and column of A's profile as A's own
+    build left it, and B reports its own grid (the flops of the triangular inverse grow with N)."""
+    from magi_v2_amd.engine import MagiEngine
+    phi1, phi2 = np.array([0.03, 0.2]), np.array([0.3, 0.15])
+    A, B = MagiEngine(0), MagiEngine(0)
+    try:
+        A.set_option("build_profile", 1)
+        A.build_matrices(np.arange(300) * 0.025, phi1, phi2, 2.01)
+        prof_a = A.build_profile()
+        assert prof_a["trtri"][0] > 0 and prof_a["single_phase_operators"][2] > 0
+        B.set_option("build_profile", 1)
+        B.build_matrices(np.arange(200) * 0.025, phi1, phi2, 2.01)
+        assert A.build_profile() == prof_a
+        prof_b = B.build_profile()
+        assert prof_b["trtri"][0] > 0 and prof_b["trtri"][0] != prof_a["trtri"][0]
+        B.set_option("build_profile", 0)
+        B.build_matrices(np.arange(200) * 0.025, phi1, phi2, 2.01)
+        assert A.build_profile() == prof_a
+    finally:
+        A.close()
+        B.close()
+
+
 def test_built_matrices_feed_logpost_and_band(eng):
     """End to end on the device-resident matrices: build (band 80 at N=161 -> masked dense) and
     evaluate the log posterior; compare with the oracle on the ORACLE's matrices.  Agreement is

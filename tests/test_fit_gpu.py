@@ -112,6 +112,51 @@ def test_multi_block_fit_equals_oracle_sorted_and_shuffled(order, host_loop):
         eng.close()
 
 
+_nine = {}
+
+
+def nine_component_truth(g):
+    """N = 81, D = 9: the three SEIR components at three scales and offsets.  Returns (I, X, priors, initial values, {k: (oracle result,
+    oracle loss trace)} for k = 1 and 8 Adam steps).  Computed once and shared: read-only."""
+    if not _nine:
+        I, X3 = g["seir3_I"][:81, 0], g["seir3_X_interp"][:81]
+        X = np.concatenate([X3 * (1 + 0.25 * k) + 0.1 * k for k in range(3)], axis=1)
+        pri = [orc.fourier_phi2_prior(X[:, d]) for d in range(X.shape[1])]
+        init = orc.hparams_initial(X)
+        want = {}
+        for k in (1, 8):
+            trace = []
+            want[k] = (orc.fit_kernel_hparams(I, X, num_iters=k, trace=trace), np.array(trace))
+        _nine["v"] = (I, X, pri, init, want)
+    return _nine["v"]
+
+
+@pytest.mark.parametrize("host_loop", [0, 1], ids=["device-loop", "host-loop"])
+def test_fit_with_more_than_eight_components_equals_oracle(data, host_loop):
+    """Every component of a fit rides on a grid axis of every launch and keeps its priors in its own device block, so their number is
+    not bounded by a launch's argument list: nine components, 1 and 8 Adam steps, both loops, against the oracle.  cond(S) at the initial
+    values is 2.4e2 - 1.2e3 for all nine, so the bars are those of test_single_adam_step_equals_oracle at the same N."""
+    from magi_v2_amd.engine import MagiEngine
+    I, X, pri, init, want = nine_component_truth(data[2])
+    assert X.shape == (81, 9)
+    eng = MagiEngine(0)
+    try:
+        eng.set_option("fit_host_loop", host_loop)
+        for iters in (1, 8):
+            got = eng.fit_hparams(I, X, X.mean(axis=0), [q[0] for q in pri], [q[1] for q in pri], init["sigma_sqs"],
+                                  init["phi1s"], init["phi2s"], init["sigma_sqs"], num_iters=iters, want_trace=True)
+            res, trace = want[iters]
+            dev = max(np.abs(got[k] / res[k] - 1.0).max() for k in ("phi1s", "phi2s", "sigma_sqs"))
+            print(f"NINE-COMPONENT-FIT host_loop={host_loop} iters={iters}: parameters {dev:.2e} (bar 1e-6), "
+                  f"loss trace {np.abs(got['loss'] / trace - 1.0).max():.2e} (bar 1e-8)")
+            for k in ("phi1s", "phi2s", "sigma_sqs"):
+                assert got[k].shape == (9,)
+                np.testing.assert_allclose(got[k], res[k], rtol=1e-6)
+            np.testing.assert_allclose(got["loss"], trace, rtol=1e-8)
+    finally:
+        eng.close()
+
+
 def test_fit_increases_the_marginal_likelihood(data):
     from magi_v2_amd.engine import MagiEngine
     I, X, g = data

@@ -32,7 +32,8 @@ def header_options():
 
 def test_header_lists_every_option_of_the_table():
     table = option_table()
-    assert len(table) >= 13 and ("slot_budget_graphs", None) in table
+    assert len(table) >= 12 and ("slot_budget_graphs", None) in table
+    assert "fit_per_component" not in [name for name, _ in table]          # (deleted with the per-component fit path)
     assert header_options() == table
 
 
