@@ -20,10 +20,16 @@ def f_vec(t, X, thetas):
                            (thetas[1] * X[:, 1:2])], axis=1)
 
 
-def report(tag, results):
+def report(tag, results, model):
     th = results["thetas_samps"].reshape(-1, 3)
     print(f"[{tag}] theta posterior mean {np.round(th.mean(axis=0), 3)} sd {np.round(th.std(axis=0), 3)} (truth 6, 0.6, 1.8); "
           f"mean tree depth {results['kernel_results']['tree_depth'].mean():.2f}, {results['minutes_elapsed']} min")
+    # the reconstructed trajectory: the ODE solved on the GPU from every draw's x(0) and theta; its posterior mean against the observations
+    pt = model.posterior_trajectories(results, return_draws=False)
+    at_obs = np.abs(pt["t"][:, None] - np.asarray(model.ts_obs, dtype=np.float64).reshape(1, -1)).argmin(axis=0)      # grid index of every observation time
+    rmse = np.sqrt(np.nanmean((pt["mean"][at_obs] - model.X_obs) ** 2, axis=0))
+    print(f"[{tag}] reconstructed-trajectory RMSE against the observations per component {np.round(rmse, 4)} "
+          f"({pt['n_failed']} of {pt['status'].size} trajectories not finite)")
 
 
 def main():
@@ -37,19 +43,19 @@ def main():
     #    1.77 is stale output of an unseeded run).
     model.initial_fit(discretization=1, verbose=True)
     print("fitted on the grid: phi2", np.round(model.phi2s, 3), "sigma", np.round(np.sqrt(model.sigma_sqs_init), 4), "theta_init", np.round(model.thetas_init, 3))
-    report("reference defaults", model.predict(num_results=500, num_burnin_steps=500, verbose=True))
+    report("reference defaults", model.predict(num_results=500, num_burnin_steps=500, verbose=True), model)
 
     # 2. this package's documented alternative: fit the hyper-parameters on the observation times, start theta at 1
     model.initial_fit(discretization=1, hparam_fit_on="observed")
     sigma_fit = model.sigma_sqs_init.copy()
     model.thetas_init = np.ones(3)
     print("fitted on the observed rows: phi2", np.round(model.phi2s, 3), "sigma", np.round(np.sqrt(sigma_fit), 4))
-    report("fit on observed rows", model.predict(num_results=500, num_burnin_steps=500, n_chains=4, seed=1))
+    report("fit on observed rows", model.predict(num_results=500, num_burnin_steps=500, n_chains=4, seed=1), model)
 
     # 3. user-supplied hyper-parameters (the reference lets users overwrite them, magi_v2.py:77-80)
     model.initial_fit(discretization=1, hparams={"phi2s": [0.5, 0.5, 0.5], "sigma_sqs": sigma_fit})
     model.thetas_init = np.ones(3)
-    report("phi2 = 0.5, fitted noise", model.predict(num_results=500, num_burnin_steps=500, n_chains=4, seed=1))
+    report("phi2 = 0.5, fitted noise", model.predict(num_results=500, num_burnin_steps=500, n_chains=4, seed=1), model)
 
 
 if __name__ == "__main__":

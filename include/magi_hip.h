@@ -287,6 +287,28 @@ int magi_drift_probe_at(magi_handle* h, int drift_id, int P, int path, int n,
                         const double* x, const double* th, const double* g,
                         double* f, double* c, double* t, const double* tt);
 
+/* ---- posterior trajectories ------------------------------------------------------------------ */
+
+/* Integrate THIS library's drift (DriftT<>::f, the arithmetic the sampler ran) for S draws at once, one lane per draw (unit
+ * csrc/ode.hip): draw s starts at x0[s][D] with the parameters theta[s][P] (natural scale, as the drift sees them) and is reported at
+ * the T times t_out (finite, strictly increasing; output 0 is x0 itself).
+ * Scheme: classical RK4 with `substeps` steps per output interval, exactly magi_v2_amd.drift_examples.rk4: h = (t[j+1] - t[j]) /
+ * substeps, sub-step k starts at s = t[j] + k h, stages at s, s + h/2, s + h/2, s + h, x += h/6 (k1 + 2 k2 + 2 k3 + k4).  A drift
+ * that does not use t is given the constant 0.
+ * status[s]: 0 when every output of draw s is finite, else j + 1 for the first interval [t[j], t[j+1]] whose output has a non-finite
+ * component -- the index of the first non-finite output, 1 for a non-finite x0 (the outputs after it hold whatever the arithmetic
+ * gives; other draws are not affected).  n_failed: draws with status != 0.
+ * mean / sd [T][D]: mean and sample standard deviation (ddof = 1) over the draws with status 0, two passes in a fixed summation
+ * order (bit-identical from run to run); the mean is NaN when no draw qualifies, the sd when fewer than two do.
+ * traj[S][T][D], mean, sd, status, n_failed: each optional (NULL: not computed / not copied).
+ * Drift ids as magi_drift_probe_at.  MAGI_E_BADARG (handle stays usable): S outside [1, 2^20], T outside [2, 2^16], substeps outside
+ * [1, 1024], roundup(S, 64) T D > 2^28 (a 2 GiB device buffer), a wrong P, a NULL x0 / theta / t_out, a t_out that is not finite or
+ * not strictly increasing.  Needs a handle only for its device and stream: no matrices, no problem; a group handle is fine. */
+int magi_ode_solve(magi_handle* h, int drift_id, int P, int S,
+                   const double* x0, const double* theta,
+                   int T, const double* t_out, int substeps,
+                   double* traj, double* mean, double* sd, int* status, int* n_failed);
+
 /* ---- multi-GPU ---------------------------------------------------------------------------------
  * There is deliberately NO magi_gather in this ABI (SURVEY 8b had listed one).  The path shards by independent (dataset, chain) units with
  * no exchange while sampling (one handle per GPU, one process per GPU); its only collective is ONE gather of the post-burn-in samples at

@@ -79,6 +79,7 @@ _SYMBOLS = {
     "magi_build_profile": (C.c_int, [C.c_void_p, _dp, _dp, _lp]),
     "magi_drift_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "magi_drift_probe_at": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
+    "magi_ode_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _ip, _ip]),
 }
 
 _libs = {}
@@ -163,6 +164,7 @@ class MagiEngine:
         self.N = self.D = self.P = None
         self.n_chains = 0
         self._cfg = None
+        self._problem_drift = None
 
     # -- plumbing -------------------------------------------------------------------------------
     def close(self):
@@ -215,6 +217,36 @@ class MagiEngine:
             times = _f64(np.asarray(t, dtype=np.float64).reshape(-1), (n,))
             self._check(self._lib.magi_drift_probe_at(self._h, drift_id, P, int(path), n, _ptr(X), _ptr(th), _ptr(g), _ptr(f), _ptr(c), _ptr(tt), _ptr(times)))
         return f, c, tt
+
+    def ode_solve(self, x0, theta, t_out, substeps=4, return_draws=True, drift=None):
+        """This library's drift integrated on the device for S draws at once (magi_ode_solve): draw s starts at x0[s] ([S, D]) with the
+        parameters theta[s] ([S, P], natural scale) and is reported at the increasing times t_out[T] (output 0 is x0).  Classical RK4,
+        ``substeps`` steps per output interval: the scheme of drift_examples.rk4.  Returns dict(trajectories [S, T, D] or None without
+        ``return_draws``, mean [T, D], sd [T, D] (ddof = 1) over the draws with status 0, status [S] (0, or the index of the first
+        non-finite output; 1 for a non-finite x0), n_failed).  ``drift``: built-in name or Drift; None: the Drift this engine was created for, else the drift
+        of the last set_problem."""
+        if drift is None:
+            drift = self.user_drift if self.user_drift is not None else getattr(self, "_problem_drift", None)
+            if drift is None:
+                raise ValueError("ode_solve on the base library needs drift= (a built-in name) or a problem set before")
+        if isinstance(drift, str):
+            D, drift_id = DRIFT_SHAPES[drift][0], DRIFT_IDS[drift]
+        else:
+            D, drift_id = drift.D, drift.device_id
+        x0, theta = _f64(x0), _f64(theta)
+        S = x0.shape[0]
+        x0 = _f64(x0, (S, D))
+        if theta.ndim != 2 or theta.shape[0] != S:
+            raise ValueError(f"expected theta of shape ({S}, P), got {theta.shape}")
+        P = theta.shape[1]                                   # (a wrong P is the library's to refuse)
+        t_out = _f64(np.asarray(t_out, dtype=np.float64).reshape(-1))
+        T = t_out.shape[0]
+        traj = np.empty((S, T, D)) if return_draws else None
+        mean, sd = np.empty((T, D)), np.empty((T, D))
+        status, nf = np.zeros(max(S, 1), dtype=np.int32), C.c_int32(0)
+        self._check(self._lib.magi_ode_solve(self._h, drift_id, P, S, _ptr(x0), _ptr(theta), T, _ptr(t_out), int(substeps), _ptr(traj),
+                                             _ptr(mean), _ptr(sd), status.ctypes.data_as(_ip), C.byref(nf)))
+        return {"trajectories": traj, "mean": mean, "sd": sd, "status": status[:S], "n_failed": int(nf.value)}
 
     def selftest(self, drift=None, force=False):
         """Self-test of the library this engine runs (magi_v2_amd.selftest.ensure: cached verdict, or a run on handles of its own);
@@ -338,6 +370,7 @@ class MagiEngine:
         self._check(self._lib.magi_set_problem(self._h, _ptr(mu), _ptr(N_ds), obs_idx.ctypes.data_as(_lp), _ptr(y),
                                                obs_idx.shape[0], float(beta), _ptr(LB), drift_id, P))
         self.P = P
+        self._problem_drift = drift
 
     def _states(self, X, sig_pre, th_pre):
         X = _f64(X)
