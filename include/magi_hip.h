@@ -309,6 +309,49 @@ int magi_ode_solve(magi_handle* h, int drift_id, int P, int S,
                    int T, const double* t_out, int substeps,
                    double* traj, double* mean, double* sd, int* status, int* n_failed);
 
+/* ---- posterior summaries and convergence diagnostics ----------------------------------------- */
+
+/* Summaries of K scalar columns of C chains x R draws (unit csrc/summary.hip; what the reference's notebooks do on the host with
+ * X_samps.mean(axis=0) and np.quantile(X_samps, [0.025, 0.975], axis=0), plus the mixing diagnostics it has none of).  draws: host
+ * [C][R][K].  Per column, with S = C R pooled draws:
+ *   mean, sd      two passes in a fixed summation order (bit-identical from run to run); sd with ddof = 1, NaN when S < 2.
+ *   quant[q][k]   v = the sorted pooled draws (exact order statistics), h = (S - 1) probs[q], lo = floor(h), g = h - lo:
+ *                 v[lo] + g (v[min(lo + 1, S - 1)] - v[lo])   (numpy's "linear" method).
+ *   rhat          split R-hat: n = R / 2, M = 2 C split chains (rows [0, n) and [R - n, R) of every chain: an odd R drops the middle draw),
+ *                 their means ybar_m and variances s2_m (ddof = 1); W = mean_m s2_m, B/n = var_m(ybar_m, ddof = 1),
+ *                 var+ = (n - 1) / n W + B/n, rhat = sqrt(var+ / W).
+ *   ess           acov_m(t) = 1/n sum_{i < n - t} (y_i - ybar_m)(y_{i+t} - ybar_m); rho_0 = 1, rho_t = 1 - (W - mean_m acov_m(t)) / var+ for
+ *                 1 <= t <= L = min(n - 1, max_lag) (max_lag <= 0: n - 1); pairs P_k = rho_{2k} + rho_{2k+1} for every k with 2 k + 1 <= L;
+ *                 K* = the first k with P_k < 0 (the number of pairs if there is none); for k = 1 .. K* - 1 in turn P_k = min(P_k, P_{k-1});
+ *                 tau = max(-1 + 2 sum_{k < K*} P_k, 1 / log10(M n)); ess = M n / tau.
+ *   mcse_mean     sd / sqrt(ess).
+ * rhat, ess and mcse_mean are NaN when R < 4.  A constant column (its smallest and largest draw are equal) has sd = 0 exactly and NaN
+ * rhat, ess, mcse_mean.  A column with a non-finite draw has NaN in every statistic and counts in *n_nonfinite.
+ * mean, sd, rhat, ess, mcse_mean [K], quant [n_q][K], n_nonfinite: each optional (NULL: not copied).
+ * MAGI_E_BADARG (handle stays usable): C outside [1, 4096], R outside [1, 2^20], C R > 2^22, K outside [1, 2^24], n_q outside [0, 16],
+ * a prob outside [0, 1] or not finite, draws NULL.  Needs a handle only for its device and stream: no matrices, no problem; a group
+ * handle is fine.  Device memory of a call: the columns are gathered in chunks of at most
+ * 64 MiB, with a staging buffer of the same size for the strided upload and at most 32 MiB of split-chain means -- 160 MiB whatever K is --
+ * plus the result arrays, (5 + n_q) K doubles, which grow with K (2.8 GB at K = 2^24, n_q = 16; 0.7 MB at the sampler's K = 4096). */
+int magi_summarize(magi_handle* h, int C, int R, int K, const double* draws,
+                   int n_q, const double* probs, int max_lag,
+                   double* mean, double* sd, double* quant, double* rhat, double* ess, double* mcse_mean,
+                   int* n_nonfinite);
+
+/* The same statistics of the sampler's device-resident post-burn-in samples, pooled over the chains [chain0, chain0 + n_sel): nothing
+ * but the summaries crosses to the host (magi_sampler_get_samples moves every draw).  Three blocks of columns, each with the six
+ * outputs of magi_summarize: X in the host layout ([N][D]; quant [n_q][N][D]) as stored, sigma_sqs [D] = softplus(sig_pre) + LB[d] and
+ * thetas [P] = softplus(th_pre) (magi_v2.py:418-419); *n_nonfinite counts the columns of all three.  Every output is optional.
+ * MAGI_E_STATE unless the sampler is initialised and every selected chain has finished all num_burnin_steps + num_results
+ * transitions.  MAGI_E_BADARG: a chain range outside the sampler's chains, n_sel > 4096 or n_sel num_results > 2^22, n_q / probs as
+ * magi_summarize; on a group handle a range that does not lie inside one member (chains are member-major; different members sample
+ * different posteriors) -- LB is that member's. */
+int magi_sampler_summarize(magi_handle* h, int chain0, int n_sel, int n_q, const double* probs, int max_lag,
+                           double* X_mean, double* X_sd, double* X_quant, double* X_rhat, double* X_ess, double* X_mcse_mean,
+                           double* sig_mean, double* sig_sd, double* sig_quant, double* sig_rhat, double* sig_ess, double* sig_mcse_mean,
+                           double* th_mean, double* th_sd, double* th_quant, double* th_rhat, double* th_ess, double* th_mcse_mean,
+                           int* n_nonfinite);
+
 /* ---- multi-GPU ---------------------------------------------------------------------------------
  * There is deliberately NO magi_gather in this ABI (SURVEY 8b had listed one).  The path shards by independent (dataset, chain) units with
  * no exchange while sampling (one handle per GPU, one process per GPU); its only collective is ONE gather of the post-burn-in samples at
@@ -368,7 +411,9 @@ int magi_stream_kernel_name(magi_handle* h, int n_chains, char* buf, int cap);
  *   "fit_host_loop"       MAGI_FIT_HOST_LOOP        flag
  *   "build_profile"       MAGI_BUILD_PROFILE        flag
  *   "build_serial"        MAGI_BUILD_SERIAL         flag
- *   "slot_budget_graphs"  (none: a test hook)       cap on the graph launches of one magi_sampler_run; 0 = the computed bound */
+ *   "slot_budget_graphs"  (none: a test hook)       cap on the graph launches of one magi_sampler_run; 0 = the computed bound
+ * Beside the options, one test switch of the summaries (no environment variable, no effect on any result): summary_chunk_cols, 0..2^24;
+ * > 0: magi_summarize / magi_sampler_summarize gather at most this many columns per chunk (0 = what the work space allows). */
 int magi_set_option(magi_handle* h, const char* name, int64_t value);
 
 /* Diagnostics: per-class device time of the last magi_build_matrices run with option "build_profile" set

@@ -23,12 +23,22 @@ import numpy as np
 
 from . import drift as _drift
 from . import host
-from .engine import DRIFT_SHAPES, MagiEngine, MagiGroup
+from .engine import DEFAULT_PROBS, DRIFT_SHAPES, MagiEngine, MagiGroup
 
 
 def _fresh_seed() -> int:
     """A 64-bit seed from the operating system's entropy (predict's seed when none is given)."""
     return int(np.random.SeedSequence().generate_state(2, dtype=np.uint32).astype(np.uint64) @ np.array([1, 1 << 32], dtype=np.uint64))
+
+
+def _warn_if_stuck(summary):
+    """predict(summary=True): one warning when every X column is constant -- no post-burn-in transition moved (with the
+    reference-faithful ``stale_cache=True`` a run can return ``num_results`` copies of one state).  Returns ``summary``."""
+    if np.all(summary["X"]["sd"] == 0.0):
+        import warnings
+        warnings.warn("predict: every X column of the posterior sample is constant -- no post-burn-in transition was accepted; "
+                      "rhat, ess and mcse_mean are NaN (try stale_cache=False, a smaller step_size or a longer burn-in)")
+    return summary
 
 
 def logarithmic_temperature_schedule(step, min_temp: float = 0.1):
@@ -341,11 +351,16 @@ class MAGI_v2:
     def predict(self, num_results: int = 1000, num_burnin_steps: int = 1000, sigma_sqs_LB=None, verbose=False, *,
                 n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[int]] = None,
                 stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
-                family_chains: Optional[int] = None):
+                family_chains: Optional[int] = None, summary: bool = False, keep_samples: bool = True):
         """magi_v2.py:286-425.  Returns the reference's results dictionary; with n_chains > 1 every
         sample array gains a leading chain axis.  ``family_chains``: in a job sharded over GPUs, the largest per-GPU share
         (shard.family_chains_for) -- every rank then samples with the same kernel family whatever its own share.
+        ``summary=True`` adds ``results["summary"]``: the posterior summaries and convergence diagnostics of all chains pooled, computed
+        on the GPU from the device-resident samples (``posterior_summary``, which also takes other ``probs`` / ``max_lag``).  ``keep_samples=False`` (only with ``summary=True``) skips
+        the download of the draws: ``X_samps``, ``sigma_sqs_samps``, ``thetas_samps`` and ``sample_results`` are then None.
         Many datasets on one GPU: ``predict_many``."""
+        if not keep_samples and not summary:
+            raise ValueError("keep_samples=False needs summary=True: the call would return nothing of the posterior")
         sigma_sqs_LB, sig_pre0, th_pre0 = self._predict_prepare(sigma_sqs_LB, family_chains)
         eng = self.engine
         if seed is None:                 # the reference calls sample_chain unseeded (magi_v2.py:389-395)
@@ -358,12 +373,25 @@ class MAGI_v2:
         start = time.time()
         eng.sampler_init(cfg, rep(self.Xhat_init), rep(sig_pre0), rep(th_pre0), seed=seed, chain_ids=chain_ids)
         eng.sampler_run(num_results + num_burnin_steps)
-        X_samps, sig_pre, th_pre = eng.sampler_samples()
+        self._predicted = True
+        X_samps, sig_pre, th_pre = eng.sampler_samples() if keep_samples else (None, None, None)
         end = time.time()
         minutes = np.round((end - start) / 60, 2)
         if verbose:
             print(f"Finished sampling in {minutes} minutes.")
-        return self._predict_results(X_samps, sig_pre, th_pre, eng.sampler_diag(), sigma_sqs_LB, seed, n_chains, num_burnin_steps, minutes)
+        results = self._predict_results(X_samps, sig_pre, th_pre, eng.sampler_diag(), sigma_sqs_LB, seed, n_chains, num_burnin_steps, minutes)
+        if summary:
+            results["summary"] = _warn_if_stuck(self.posterior_summary())
+        return results
+
+    def posterior_summary(self, probs=DEFAULT_PROBS, max_lag: int = 0):
+        """Posterior summaries and convergence diagnostics of the last ``predict``, all its chains pooled, computed on the GPU from the
+        samples the sampler left there (MagiEngine.sampler_summary): dict(X, sigma_sqs, thetas, probs, n_nonfinite), where X [N, D],
+        sigma_sqs [D] and thetas [P] each hold mean, sd (ddof = 1), quantiles [len(probs), ...], rhat (split), ess and mcse_mean.  What the
+        reference's notebooks compute on the host as ``X_samps.mean(axis=0)`` and ``np.quantile(X_samps, [0.025, 0.975], axis=0)``."""
+        if not getattr(self, "_predicted", False):
+            raise RuntimeError("posterior_summary summarises the samples of the last predict: run predict first")
+        return self.engine.sampler_summary(probs=probs, max_lag=max_lag)
 
     def _predict_prepare(self, sigma_sqs_LB, family_chains=None):
         """predict's set-up up to the sampler: matrices on the device, the problem set; returns (sigma_sqs_LB, sig_pre0, th_pre0)."""
@@ -388,8 +416,9 @@ class MAGI_v2:
 
     def _predict_results(self, X_samps, sig_pre, th_pre, diag, sigma_sqs_LB, seed, n_chains, num_burnin_steps, minutes):
         """predict's results dictionary from the chains' samples [n_chains, results, ...] and diagnostics."""
-        sig_samps, th_samps = host.transform_samples(sig_pre, th_pre, sigma_sqs_LB)
-        sq = (lambda a: a[0]) if n_chains == 1 else (lambda a: a)
+        kept = X_samps is not None                   # (predict(keep_samples=False): no draw was downloaded)
+        sig_samps, th_samps = host.transform_samples(sig_pre, th_pre, sigma_sqs_LB) if kept else (None, None)
+        sq = (lambda a: None if a is None else a[0]) if n_chains == 1 else (lambda a: a)
         B = num_burnin_steps
         kernel_results = {k: sq(getattr(diag, k)[:, B:]) for k in
                           ("step_size", "log_accept_ratio", "leapfrogs_taken", "tree_depth", "has_divergence",
@@ -404,7 +433,7 @@ class MAGI_v2:
                 "sigma_sqs_samps": sq(sig_samps),
                 "thetas_samps": sq(th_samps),
                 "kernel_results": kernel_results,
-                "sample_results": [sq(X_samps), sq(sig_pre), sq(th_pre)],
+                "sample_results": [sq(X_samps), sq(sig_pre), sq(th_pre)] if kept else None,
                 "minutes_elapsed": minutes}
 
     # ------------------------------------------------------------------------------------------
@@ -416,6 +445,8 @@ class MAGI_v2:
         forecasts.  Returns dict(t [T], trajectories [draws, T, D] or None without ``return_draws``, mean [T, D], sd [T, D] (ddof = 1,
         over the draws whose trajectory stayed finite), status [draws] (0, or the index of the first non-finite output), n_failed).  With
         a leading chain axis in ``results`` (n_chains > 1) trajectories and status keep it; mean and sd are over all chains' draws."""
+        if results.get("X_samps") is None or results.get("thetas_samps") is None:
+            raise ValueError("posterior_trajectories needs the draws: predict with keep_samples=True")
         I = np.asarray(results["I"], dtype=np.float64).reshape(-1)
         X, th = np.asarray(results["X_samps"], dtype=np.float64), np.asarray(results["thetas_samps"], dtype=np.float64)
         X0 = X[..., ::thin, start_index, :]
@@ -484,12 +515,16 @@ def partition_for_groups(keys):
 
 def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_steps: int = 1000, sigma_sqs_LB=None, verbose=False, *,
                  n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[Sequence[int]]] = None,
-                 stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1):
+                 stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
+                 summary: bool = False, keep_samples: bool = True):
     """``predict`` for several models (after their ``initial_fit``) at once.  Models of one library, device and problem shape are sampled
     as one problem group on their GPU -- one captured graph, one kernel pair per leapfrog slot for all their chains -- and the others by
     their own ``predict``.  ``sigma_sqs_LB``: None (each model's default) or one entry per model; ``chain_ids``: None (0 .. n_chains - 1
     for every model, as predict) or one id list per model.  Returns one results dictionary per model, in order: element k equals
-    ``models[k].predict(<same arguments>, seed=<the seed used>)`` array for array, bit for bit; ``minutes_elapsed`` is the group's."""
+    ``models[k].predict(<same arguments>, seed=<the seed used>)`` array for array, bit for bit; ``minutes_elapsed`` is the group's.
+    ``summary`` / ``keep_samples`` as in ``predict``: a grouped model's summary pools that model's chains alone."""
+    if not keep_samples and not summary:
+        raise ValueError("keep_samples=False needs summary=True: the call would return nothing of the posterior")
     models = list(models)
     n = len(models)
     lbs = [None] * n if sigma_sqs_LB is None else list(sigma_sqs_LB)
@@ -504,7 +539,7 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
     for grp in partition_for_groups([group_key(m, n_chains) for m in models]):
         if len(grp) == 1:
             k = grp[0]
-            out[k] = models[k].predict(num_results, num_burnin_steps, lbs[k], verbose, chain_ids=ids[k], **kw)
+            out[k] = models[k].predict(num_results, num_burnin_steps, lbs[k], verbose, chain_ids=ids[k], summary=summary, keep_samples=keep_samples, **kw)
             continue
         g = MagiGroup([models[k].engine for k in grp])
         try:
@@ -520,15 +555,19 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
             start = time.time()
             g.sampler_init(cfg, X0, s0, t0, seed=seed, chain_ids=gids)
             g.sampler_run(num_results + num_burnin_steps)
-            X_samps, sig_pre, th_pre = g.sampler_samples()
+            X_samps, sig_pre, th_pre = g.sampler_samples() if keep_samples else (None, None, None)
             minutes = np.round((time.time() - start) / 60, 2)
             if verbose:
                 print(f"Finished sampling in {minutes} minutes.")
             diag = g.sampler_diag()
+            summaries = [g.sampler_summary(member=j) for j in range(len(grp))] if summary else None
         finally:
             g.close()
         for j, k in enumerate(grp):
             sl = slice(j * n_chains, (j + 1) * n_chains)
             dk = type(diag)(*[getattr(diag, f)[sl] for f in diag.__dataclass_fields__])
-            out[k] = models[k]._predict_results(X_samps[sl], sig_pre[sl], th_pre[sl], dk, prep[k][0], seed, n_chains, num_burnin_steps, minutes)
+            part = (X_samps[sl], sig_pre[sl], th_pre[sl]) if keep_samples else (None, None, None)
+            out[k] = models[k]._predict_results(*part, dk, prep[k][0], seed, n_chains, num_burnin_steps, minutes)
+            if summary:
+                out[k]["summary"] = _warn_if_stuck(summaries[j])
     return out

@@ -1043,6 +1043,12 @@ int magi_fit_hparams(magi_handle* h, const double* I, int N, int D, const double
 
 int magi_set_option(magi_handle* h, const char* name, int64_t value) {
     if (!h || !name) return MAGI_E_BADARG;
+    // the test switch of csrc/summary.hip: no tuning option (no result depends on it), so it is no row of the table above
+    if (std::strcmp(name, "summary_chunk_cols") == 0) {
+        if (value < 0 || value > (1 << 24)) return magi_fail(h, MAGI_E_BADARG, "summary_chunk_cols in [0, 16777216]");
+        h->opt.summary_chunk_cols = (int)value;
+        return MAGI_OK;
+    }
     for (const OptRow& r : kOptions) {
         if (std::strcmp(r.name, name) != 0) continue;
         if (set_option(h->opt, r, value)) return MAGI_OK;

@@ -914,6 +914,7 @@ struct MagiOptions {
     int potrf_panels = 3;               // build.hip: 128-wide panels per block column of the Cholesky factorisation (3: best of 2..8 at N = 1024..8192, profiles/r04_potrf_lookahead_ab.txt)
     int potrf_lookahead_min = 4096;     // build.hip: grids from this size on factorise with look-ahead (0: never), see potrf
     long long slot_budget_graphs = 0;   // TEST HOOK: cap on the graph launches of one magi_sampler_run (0 = the computed bound)
+    int summary_chunk_cols = 0;         // TEST HOOK: summary.hip gathers at most this many columns per chunk (0 = what the work space allows)
     int no_graph = 0;                   // launch the leapfrog slots directly (debugging, long rocprofv3 kernel traces)
     int fit_host_loop = 0;              // build.hip: the hyper-parameter fit with its scalar tail on the host (the tests' reference)
     int build_profile = 0, build_serial = 0;           // build.hip: per-class device times (serialises), one component per group

@@ -80,7 +80,17 @@ _SYMBOLS = {
     "magi_drift_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "magi_drift_probe_at": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "magi_ode_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _ip, _ip]),
+    "magi_summarize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int] + [_dp] * 6 + [_ip]),
+    "magi_sampler_summarize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int] + [_dp] * 18 + [_ip]),
 }
+
+SUMMARY_STATS = ("mean", "sd", "quantiles", "rhat", "ess", "mcse_mean")       # the order of the six outputs in include/magi_hip.h
+DEFAULT_PROBS = (0.025, 0.5, 0.975)
+
+
+def _summary_arrays(shape, n_q):
+    """The six output arrays of one block of columns of shape ``shape`` (quantiles: [n_q] + shape)."""
+    return [np.empty((n_q,) + tuple(shape)) if s == "quantiles" else np.empty(shape) for s in SUMMARY_STATS]
 
 _libs = {}
 
@@ -247,6 +257,59 @@ class MagiEngine:
         self._check(self._lib.magi_ode_solve(self._h, drift_id, P, S, _ptr(x0), _ptr(theta), T, _ptr(t_out), int(substeps), _ptr(traj),
                                              _ptr(mean), _ptr(sd), status.ctypes.data_as(_ip), C.byref(nf)))
         return {"trajectories": traj, "mean": mean, "sd": sd, "status": status[:S], "n_failed": int(nf.value)}
+
+    @staticmethod
+    def _probs(probs):
+        probs = _f64(np.asarray(probs, dtype=np.float64).reshape(-1))
+        return probs, probs.shape[0]
+
+    def summarize(self, draws, probs=DEFAULT_PROBS, max_lag=0):
+        """Posterior summaries and convergence diagnostics of ``draws`` [C chains, R draws, ...] on the device (magi_summarize; the
+        definitions are in include/magi_hip.h): dict(mean, sd (ddof = 1), rhat (split), ess, mcse_mean -- each of the trailing shape --
+        quantiles [len(probs), ...] (numpy's "linear" method on the pooled draws), probs, n_nonfinite (columns with a non-finite draw:
+        all their statistics are NaN)).  ``max_lag``: the largest autocorrelation lag of the ESS, <= 0: all."""
+        draws = _f64(draws)
+        if draws.ndim < 2:
+            raise ValueError(f"expected draws of shape (chains, draws, ...), got {draws.shape}")
+        n_c, n_r, shape = draws.shape[0], draws.shape[1], draws.shape[2:]
+        K = int(np.prod(shape, dtype=np.int64))
+        probs, n_q = self._probs(probs)
+        outs = _summary_arrays(shape, n_q)
+        nf = C.c_int32(0)
+        self._check(self._lib.magi_summarize(self._h, n_c, n_r, K, _ptr(draws), n_q, _ptr(probs), int(max_lag), *[_ptr(o) for o in outs], C.byref(nf)))
+        out = dict(zip(SUMMARY_STATS, outs))
+        out.update(probs=probs, n_nonfinite=int(nf.value))
+        return out
+
+    def sampler_summary(self, chains=None, probs=DEFAULT_PROBS, max_lag=0, member=None):
+        """Summaries of the finished sampler run, computed on the device-resident samples (magi_sampler_summarize): no draw is copied to the
+        host.  Returns dict(X, sigma_sqs, thetas, probs, n_nonfinite); X, sigma_sqs (= softplus(sig_pre) + LB) and thetas
+        (= softplus(th_pre)) each a dict as ``summarize`` returns, of shapes [N, D], [D] and [P].  ``chains``: None (all) or a contiguous
+        run of chain indices (a range, or (first, count) as a slice) pooled into one summary.  ``member`` (a MagiGroup): the chains of
+        that member -- a group's members sample different posteriors and are never pooled."""
+        if member is not None:
+            if chains is not None:
+                raise ValueError("give chains or member, not both")
+            if not getattr(self, "members", None):
+                raise ValueError("member= selects a member of a MagiGroup; this engine is not a group")
+            per = self.n_chains // len(self.members)
+            chain0, n_sel = int(member) * per, per
+        elif chains is None:
+            chain0, n_sel = 0, self.n_chains
+        else:
+            idx = np.arange(self.n_chains)[chains] if isinstance(chains, slice) else np.asarray(list(chains), dtype=np.int64)
+            if idx.size == 0 or np.any(np.diff(idx) != 1):
+                raise ValueError("chains must be a contiguous, increasing run of chain indices")
+            chain0, n_sel = int(idx[0]), int(idx.size)
+        probs, n_q = self._probs(probs)
+        blocks = {"X": _summary_arrays((self.N, self.D), n_q), "sigma_sqs": _summary_arrays((self.D,), n_q),
+                  "thetas": _summary_arrays((self.P,), n_q)}
+        nf = C.c_int32(0)
+        self._check(self._lib.magi_sampler_summarize(self._h, chain0, n_sel, n_q, _ptr(probs), int(max_lag),
+                                                     *[_ptr(o) for b in ("X", "sigma_sqs", "thetas") for o in blocks[b]], C.byref(nf)))
+        out = {b: dict(zip(SUMMARY_STATS, arrs)) for b, arrs in blocks.items()}
+        out.update(probs=probs, n_nonfinite=int(nf.value))
+        return out
 
     def selftest(self, drift=None, force=False):
         """Self-test of the library this engine runs (magi_v2_amd.selftest.ensure: cached verdict, or a run on handles of its own);
