@@ -563,3 +563,166 @@ DOMAIN_CASES = [
 
 def domain_case(name):
     return next(c for c in DOMAIN_CASES if c.name == name)
+
+
+# ---- one handle through many states ---------------------------------------------------------------------------------------------------
+# The drivers keep one handle alive and move it through states (new band, new shape, new data, new drift, new batch, a sampler after a
+# sampler, the instruments of bench.py); every other GPU comparison builds a fresh handle per state.  Case tables of
+# tests/test_reuse_cpu.py (the proof, on the oracle alone, that a stale answer would be seen and that every history passes through the
+# kernel families and storage modes it names) and tests/test_reuse_gpu.py (the re-used handle against a fresh one bit for bit, the fresh
+# one against the oracle).
+#
+# States (ReuseState): "A" = structureless_problem(384, "sirw", spd=True) -- three block rows, three basis functions; "A/b<k>": A's matrices
+# under the band mask k; "B": the same shape from another seed; "A+B": B's data on A's matrices; "E" = the seir4 fixture of that N;
+# "A+E": E's data and drift on A's matrices (P = 3 against 5: dimp changes); "C41" / "C161": g4_logpost_sirw_N41 / g4_logpost_seir3_N161;
+# "T" / "T+0.37": seir_seasonal at N = 41 on oracle-built matrices, the drift evaluated at the grid / at the grid + 0.37.
+
+REUSE_TB = 128                                              # edge of an operator block (csrc/magi_internal.h: MAGI_TB)
+REUSE_N = 384
+REUSE_BANDS = (None, 20, 0, 43, None, 20)                   # transition 1: dense -> 20 -> 0 -> 43 -> dense -> 20
+REUSE_SHAPES = ("A", "C41", "C161", "A")                    # transition 2
+REUSE_DATA = ("A", "A+B", "A", "A+E", "A")                  # transition 3: other data, back, other drift (P 5 -> 3), back
+# transition 4: (batch, option stream_family set on the live handle, the kernel that then serves the batch)
+REUSE_BATCHES = ((9, "mc", "k_stream_sep<CW=16>"), (2, "auto", "k_stream<2>"), (16, "auto", "k_stream_sep<CW=16>"),
+                 (8, "auto", "k_stream_sep<CW=8>"), (1, "valu", "k_stream<1>"), (3, "mc", "k_stream_sep<CW=8>"),
+                 (17, "auto", "k_stream_sep<CW=16>"))
+REUSE_BYTES = (("A", None), ("A", 20), ("A", 43), ("A", 0), ("C161", 20))   # transition 7: (state, band); at band 0 only "none missing"
+REUSE_TIME_SHIFT = 0.37
+REUSE_NUTS = dict(num_burnin_steps=4, num_results=3, step_size=2e-3, max_tree_depth=6, stale_cache=0)
+REUSE_HMC = dict(num_burnin_steps=3, num_results=2, step_size=2e-3, mode=1, hmc_leapfrogs=8, stale_cache=0)
+REUSE_SEED = 808
+
+
+def reuse_band_tables(N, band):
+    """What csrc/pack.hip derives from (N, band), restated from its comments: (three-phase storage banded?, W, fb, wb, nb) -- banded rows of
+    W = 2 b + 1 columns when 2 b + 1 < N; the single-phase operators have band fb = 3 b when 6 b + 1 < N (else dense, fb = -1); a block is
+    kept when |bi - bj| <= wb = min(nb, (max(fb, 1) - 1) / TB + 1), every block when fb < 0."""
+    nb = (N + REUSE_TB - 1) // REUSE_TB
+    banded = band is not None and 2 * band + 1 < N
+    fb = 3 * band if band is not None and 6 * band + 1 < N else -1
+    wb = nb if fb < 0 else min(nb, (max(fb, 1) - 1) // REUSE_TB + 1)
+    return banded, (2 * band + 1 if banded else N), fb, wb, nb
+
+
+def reuse_block_counts(N, D, band):
+    """(independent count, the library's count) of 128 x 128 operator blocks.  Independent: the masked index set {|i - j| <= fb} (all pairs
+    when the single-phase operators are dense) built in numpy, the blocks that hold at least one of its entries counted -- lower block
+    triangle for FH and FK, all blocks for FE.  The library's: |bi - bj| <= wb over the same triangles."""
+    _, _, fb, wb, nb = reuse_band_tables(N, band)
+    i = np.arange(N)
+    inside = np.ones((N, N), dtype=bool) if fb < 0 else np.abs(i[:, None] - i[None, :]) <= fb
+    pad = np.zeros((nb * REUSE_TB, nb * REUSE_TB), dtype=bool)
+    pad[:N, :N] = inside
+    hit = pad.reshape(nb, REUSE_TB, nb, REUSE_TB).any(axis=(1, 3))
+    lower = np.tril(np.ones((nb, nb), dtype=bool))
+    bi = np.arange(nb)
+    kept = np.abs(bi[:, None] - bi[None, :]) <= wb
+    count = lambda keep: D * (2 * int((keep & lower).sum()) + int(keep.sum()))
+    assert not (hit & ~kept).any()                           # the library never drops a block the mask leaves an entry in
+    return count(hit), count(kept)
+
+
+def reuse_auto_kernel(n_tasks, n, family, separable=True):
+    """The streaming kernel of a batch of n chains as tests/conftest.py documents the rule: "mc" -> the matrix-core kernel; "valu" ->
+    k_stream<1> / <2>; "auto" -> matrix cores from three chains up when blocks x chain pairs > 320.  Separable drifts (all built-in ones,
+    seir_seasonal) take k_stream_sep with the 8-column mirror up to 8 chains, the 16-column one beyond."""
+    mc = family == "mc" or (family == "auto" and n >= 3 and n_tasks * ((n + 1) // 2) > 320)
+    if not mc:
+        return "k_stream<2>" if n >= 2 else "k_stream<1>"
+    return "k_stream_mc" if not separable else "k_stream_sep<CW=8>" if n <= 8 else "k_stream_sep<CW=16>"
+
+
+class ReuseState:
+    """One state of a handle: ``pr`` the oracle's problem (band mask applied), ``matrices`` the unmasked stacks the engine is given next to
+    ``band``, ``drift`` a traced Drift or None, ``times`` what set_times gets (traced drifts), ``batch`` = (X[17, N, D], sig_pre[17, D],
+    th_pre[17, P]): pre-transformed states, no two alike; a batch of n evaluates / starts its chains at the first n, chain k with id 20 + k."""
+
+    def __init__(self, name, pr, matrices, band, batch, drift=None, times=None):
+        self.name, self.pr, self.matrices, self.band, self.batch, self.drift, self.times = name, pr, matrices, band, batch, drift, times
+
+    def states(self, n):
+        return tuple(a[:n] for a in self.batch)
+
+    def __repr__(self):
+        return self.name
+
+
+_reuse_states = {}
+REUSE_MAX_BATCH = 17
+
+
+def _reuse_batch_around(X0, s0, t0, seed):
+    """17 states around (X0, sig_pre0, th_pre0): X + 1e-3 max|X| z, sig_pre + 0.1 z, th_pre + 0.05 z."""
+    rng = np.random.default_rng(seed)
+    n = REUSE_MAX_BATCH
+    return (X0[None] + 1e-3 * np.abs(X0).max() * rng.standard_normal((n,) + X0.shape), s0[None] + 0.1 * rng.standard_normal((n, len(s0))),
+            t0[None] + 0.05 * rng.standard_normal((n, len(t0))))
+
+
+def reuse_state(name):
+    """The ReuseState of a name of the table above; built once per session and shared: read-only."""
+    import dataclasses
+    if name in _reuse_states:
+        return _reuse_states[name]
+    from tests.test_structureless_cpu import fixture
+    base, _, band = name.partition("/b")
+    if band:
+        a, b = reuse_state(base), int(band)
+        pr = dataclasses.replace(a.pr, C_inv=orc.band_part(a.pr.C_inv, b), m=orc.band_part(a.pr.m, b), K_inv=orc.band_part(a.pr.K_inv, b))
+        st = ReuseState(name, pr, a.matrices, b, a.batch, a.drift, a.times)
+    elif name in ("A", "B", "E"):
+        pr, X = fixture(REUSE_N, "seir4" if name == "E" else "sirw", spd=True, salt=1 if name == "B" else 0)
+        st = ReuseState(name, pr, (pr.C_inv, pr.m, pr.K_inv), None, structureless_states(pr, X, REUSE_MAX_BATCH, 0))
+    elif name in ("A+B", "A+E"):
+        a, o = reuse_state("A"), reuse_state(name[2:])
+        pr = dataclasses.replace(o.pr, C_inv=a.pr.C_inv, m=a.pr.m, K_inv=a.pr.K_inv)
+        st = ReuseState(name, pr, a.matrices, None, o.batch)
+    elif name in ("C41", "C161"):
+        g = load_g4("sirw_N41" if name == "C41" else "seir3_N161")
+        pr = problem_from_g4(g, None)
+        st = ReuseState(name, pr, (pr.C_inv, pr.m, pr.K_inv), None,
+                        _reuse_batch_around(g["state_X"][1], g["state_sig_pre"][1], g["state_th_pre"][1], len(pr.I)))
+    elif name == "C41*":                                                   # other data on C41's matrices (a group member changed later)
+        a = reuse_state("C41")
+        st = ReuseState(name, dataclasses.replace(a.pr, y=a.pr.y * 1.02, mu=a.pr.mu * 1.01), a.matrices, None, a.batch)
+    elif name in ("T", "T+0.37"):
+        from magi_v2_amd import drift as drift_mod
+        from magi_v2_amd.drift_examples import TIME_EXAMPLES
+        from tests.test_time_drift_cpu import fixture_data, oracle_drift_at
+        f_vec, D, P = TIME_EXAMPLES["seir_seasonal"]
+        I, X, X_obs, truth, phi2 = fixture_data("seir_seasonal")
+        times = I + (REUSE_TIME_SHIFT if name != "T" else 0.0)
+        oname = "seir_seasonal@reuse" + name[1:]                       # (in the oracle's drift table only inside reuse_oracle_logpost)
+        Xi = orc.linear_interpolate(X_obs)
+        hp = orc.hparams_initial(Xi)
+        C_inv, m, K_inv = orc.build_all(I, hp["phi1s"], np.full(D, phi2), 2.01, bandsize=None)
+        N_ds = (~np.isnan(X_obs)).sum(axis=0).astype(np.float64)
+        idx = np.where(~np.isnan(X_obs).flatten())[0]
+        Xhat = orc.cubic_smoother(I, Xi)
+        LB = orc.sigma_sqs_lower_bound(Xhat)
+        pr = orc.Problem(I=I, mu=Xi.mean(axis=0), C_inv=C_inv, m=m, K_inv=K_inv, N_ds=N_ds, obs_idx=idx, y=X_obs.reshape(-1)[idx],
+                         beta=float(D * len(I) / N_ds.sum()), LB=LB, drift=oname, P=P)
+        X0, s0, t0 = orc.initial_state(Xhat, hp["sigma_sqs"], truth, LB)
+        st = ReuseState(name, pr, (C_inv, m, K_inv), None, _reuse_batch_around(X0, s0, t0, 41), drift_mod.resolve(f_vec, D, P), times)
+        st.oracle_entry = (oracle_drift_at(f_vec, times), D, P)
+    else:
+        raise KeyError(name)
+    _reuse_states[name] = st
+    return st
+
+
+def reuse_band_state(band):
+    return reuse_state("A" if band is None else f"A/b{band}")
+
+
+def reuse_oracle_logpost(st, X, sp, tp, temp):
+    """orc.logpost_grad of a ReuseState; the drift-table entry of a traced state is registered for the call only (other tests iterate
+    over that table)."""
+    entry = getattr(st, "oracle_entry", None)
+    if entry is None:
+        return orc.logpost_grad(X, sp, tp, temp, st.pr)
+    orc.DRIFTS[st.pr.drift] = entry
+    try:
+        return orc.logpost_grad(X, sp, tp, temp, st.pr)
+    finally:
+        del orc.DRIFTS[st.pr.drift]
