@@ -248,6 +248,40 @@ int magi_sampler_get_state(magi_handle* h, double* X, double* sig_pre, double* t
 int magi_sampler_get_checkpoint(magi_handle* h, double* scalars /* [n_chains][MAGI_CKPT_SCALARS] */);
 int magi_sampler_set_checkpoint(magi_handle* h, const double* scalars /* [n_chains][MAGI_CKPT_SCALARS] */);
 
+/* Diagonal mass matrix (opt-in; TFP's NoUTurnSampler, hence the reference, has the identity metric only, and that stays the default).
+ * A chain's metric is its inverse mass per entry of the state, in the host layouts of magi_sampler_init: inv_mass_X[n_chains][N][D],
+ * inv_mass_sig[n_chains][D], inv_mass_th[n_chains][P].  With M^-1 = diag(s^2) the device keeps the WHITENED momentum (HMC on z = q / s
+ * with the identity metric): the momentum draw, the kinetic energy, the U-turn tests, the energies and every diagnostic are those of
+ * the identity metric on z, and s enters the two updates p_half = p + eps/2 (s . grad), q' = q + eps (s . p_half) alone.  The reference
+ * run of a chain under metric s is therefore the oracle's NUTS / HMC step on z with fn(z) = (L(s . z), s . grad L(s . z)) and the same
+ * Philox draws.  All four calls return MAGI_E_STATE before magi_sampler_init, which resets every chain to the identity metric with no
+ * window open; they work on a group handle as on a handle (over all its chains).
+ *   magi_sampler_set_metric   all three pointers NULL: back to the identity metric; else all three non-NULL, every entry finite and
+ *       > 0 (MAGI_E_BADARG otherwise, nothing changed).  Legal between magi_sampler_run calls: the chains stand at a transition
+ *       boundary with nothing of the next transition staged, so the new metric governs it from its first half step.
+ *   magi_sampler_get_metric   the metric in force (ones under the identity metric); any pointer may be NULL.
+ *   magi_sampler_metric_window(on)   1: open a window -- shift := the state every chain holds now, sums := 0; from now on the state a
+ *       chain holds after each finished transition is added on the device.  0: close it without adapting.
+ *   magi_sampler_adapt_metric   the open window -> the metric: per chain and entry, var = sample variance (ddof 1) of the n window
+ *       states, inverse mass = n / (n + kappa) var + kappa / (n + kappa) rel_floor median(var) (the median over the chain's entries:
+ *       a floor RELATIVE to the chain's own scale; Stan's constants are kappa = 5, and 1e-3 for its absolute floor).  n must be the
+ *       number of transitions every chain has finished since the window was opened, n >= 2 (MAGI_E_BADARG otherwise, nothing changed,
+ *       the window stays open).  A chain whose median variance is 0 or whose window holds a non-finite state keeps its metric; the call
+ *       returns the number of such chains (>= 0; errors are negative).  restart_adapt_steps >= 0: dual averaging of every chain
+ *       restarts at eps_new = eps_old min(s_old) / min(s_new) -- the step along the stiffest coordinate is kept; eps_old for a chain
+ *       that kept its metric -- as a fresh DualAveragingStepSizeAdaptation(eps_new), and the sampler's num_adaptation_steps becomes
+ *       restart_adapt_steps (counted from the restart).  restart_adapt_steps < 0: step size and adaptation are left alone.  step_size_out[n_chains] (may be NULL):
+ *       every chain's step size after the call.  The window is closed.  (The metric is written in place and the dual-averaging state
+ *       uploaded behind it: a MAGI_E_HIP from this call leaves the sampler undefined until the next magi_sampler_init.)
+ * A call that switches between "no metric" and "a metric", or opens / closes a window, rebuilds the captured graph at the next
+ * magi_sampler_run (the pointers are kernel arguments): keep such switches to one per window.
+ * Checkpoints do not carry the metric: resume with magi_sampler_init (num_adaptation_steps = the value in force when the checkpoint was
+ * taken), then magi_sampler_set_metric(what magi_sampler_get_metric returned), then magi_sampler_set_checkpoint. */
+int magi_sampler_set_metric(magi_handle* h, const double* inv_mass_X, const double* inv_mass_sig, const double* inv_mass_th);
+int magi_sampler_get_metric(magi_handle* h, double* inv_mass_X, double* inv_mass_sig, double* inv_mass_th);
+int magi_sampler_metric_window(magi_handle* h, int on);
+int magi_sampler_adapt_metric(magi_handle* h, int n, double kappa, double rel_floor, int restart_adapt_steps, double* step_size_out /* [n_chains] */);
+
 /* One-call form: init + run(num_burnin + num_results) + get_samples. */
 int magi_sample(magi_handle* h, const magi_sampler_cfg* cfg, int n_chains,
                 const double* X0, const double* sig_pre0, const double* th_pre0,

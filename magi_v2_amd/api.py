@@ -351,13 +351,18 @@ class MAGI_v2:
     def predict(self, num_results: int = 1000, num_burnin_steps: int = 1000, sigma_sqs_LB=None, verbose=False, *,
                 n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[int]] = None,
                 stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
-                family_chains: Optional[int] = None, summary: bool = False, keep_samples: bool = True):
+                family_chains: Optional[int] = None, summary: bool = False, keep_samples: bool = True, adapt_metric: bool = False):
         """magi_v2.py:286-425.  Returns the reference's results dictionary; with n_chains > 1 every
         sample array gains a leading chain axis.  ``family_chains``: in a job sharded over GPUs, the largest per-GPU share
         (shard.family_chains_for) -- every rank then samples with the same kernel family whatever its own share.
         ``summary=True`` adds ``results["summary"]``: the posterior summaries and convergence diagnostics of all chains pooled, computed
         on the GPU from the device-resident samples (``posterior_summary``, which also takes other ``probs`` / ``max_lag``).  ``keep_samples=False`` (only with ``summary=True``) skips
         the download of the draws: ``X_samps``, ``sigma_sqs_samps``, ``thetas_samps`` and ``sample_results`` are then None.
+        ``adapt_metric=True`` (the reference, like TFP's NoUTurnSampler, has the identity metric only): a per-chain diagonal mass matrix is
+        adapted during the ``int(0.8 * num_burnin_steps)`` adaptation transitions over Stan's windows (``host.warmup_schedule``), dual
+        averaging restarting after each window; ``results["metric"]`` = dict(inv_mass_X, inv_mass_sigma_pre, inv_mass_theta_pre: the
+        metric the results were drawn with, leading chain axis as the samples; windows: per adapted window start, stop, the step sizes
+        after it and the number of chains it left unchanged).
         Many datasets on one GPU: ``predict_many``."""
         if not keep_samples and not summary:
             raise ValueError("keep_samples=False needs summary=True: the call would return nothing of the posterior")
@@ -372,7 +377,12 @@ class MAGI_v2:
             print("Starting NUTS posterior sampling ...")
         start = time.time()
         eng.sampler_init(cfg, rep(self.Xhat_init), rep(sig_pre0), rep(th_pre0), seed=seed, chain_ids=chain_ids)
-        eng.sampler_run(num_results + num_burnin_steps)
+        if adapt_metric:
+            n_adapt = int(0.8 * num_burnin_steps)
+            _, _, windows = eng.sampler_warmup(host.warmup_schedule(num_burnin_steps, n_adapt))
+            eng.sampler_run(num_results + num_burnin_steps - n_adapt)
+        else:
+            eng.sampler_run(num_results + num_burnin_steps)
         self._predicted = True
         X_samps, sig_pre, th_pre = eng.sampler_samples() if keep_samples else (None, None, None)
         end = time.time()
@@ -380,6 +390,10 @@ class MAGI_v2:
         if verbose:
             print(f"Finished sampling in {minutes} minutes.")
         results = self._predict_results(X_samps, sig_pre, th_pre, eng.sampler_diag(), sigma_sqs_LB, seed, n_chains, num_burnin_steps, minutes)
+        if adapt_metric:
+            sq = (lambda a: a[0]) if n_chains == 1 else (lambda a: a)
+            mX, ms, mt = eng.sampler_metric()
+            results["metric"] = {"inv_mass_X": sq(mX), "inv_mass_sigma_pre": sq(ms), "inv_mass_theta_pre": sq(mt), "windows": windows}
         if summary:
             results["summary"] = _warn_if_stuck(self.posterior_summary())
         return results

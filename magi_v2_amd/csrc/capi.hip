@@ -52,8 +52,11 @@ void free_chains(magi_handle* h) {
     free_dev(c.d_step_size); free_dev(c.d_lar); free_dev(c.d_target); free_dev(c.d_energy); free_dev(c.d_beta);
     free_dev(c.d_leapfrogs); free_dev(c.d_depth); free_dev(c.d_flags);
     free_dev(h->d_chain_ids); free_dev(h->d_fin);
+    free_dev(h->d_scale); free_dev(h->d_macc); free_dev(h->d_mwork);
     c = DevChains{};
     h->d_chain_ids = nullptr; h->d_fin = nullptr;
+    h->d_scale = h->d_macc = h->d_mwork = nullptr;
+    h->window_k0.clear();
     h->cap_chains = 0; h->n_chains = 0; h->samples_cap = 0; h->diag_cap = 0;
     h->sampler_ready = false;
 }
@@ -711,6 +714,9 @@ int magi_sampler_init(magi_handle* h, const magi_sampler_cfg* cfg, int n_chains,
         for (int* p : {d.d_leapfrogs, d.d_depth, d.d_flags}) MAGI_HIP_CHECK(h, hipMemsetAsync(p, 0xFF, need_d * sizeof(int), h->stream));
     }
     drop_graph(h);   // kernel arguments (cfg, buffers) are baked into the captured graph
+    h->ch.scale = nullptr;       // a fresh sampler: identity metric, no metric window
+    h->ch.macc = nullptr;
+    h->window_k0.clear();
 
     if ((rc = upload_states(h, n_chains, X0, sig_pre0, th_pre0))) return rc;
     std::vector<long long> ids(n_chains);
@@ -1015,6 +1021,157 @@ int magi_sampler_set_checkpoint(magi_handle* h, const double* scalars) {
     }
     MAGI_HIP_CHECK(h, hipMemcpy(h->ch.ctl, ctl.data(), sizeof(ChainCtl) * h->n_chains, hipMemcpyHostToDevice));
     return MAGI_OK;
+}
+
+// ---- diagonal metric (include/magi_hip.h; kernels: DevChains::scale / macc in leap_point.h, leap_reduce.h, metric.hip) ----
+// the three device buffers, sized for the chains the handle has room for (freed with them: free_chains)
+static int metric_buffers(magi_handle* h) {
+    const size_t n = (size_t)h->cap_chains, dimp = (size_t)h->pb.dimp;
+    if (!h->d_scale) MAGI_HIP_CHECK(h, hipMalloc(&h->d_scale, sizeof(double) * n * dimp));
+    if (!h->d_macc) MAGI_HIP_CHECK(h, hipMalloc(&h->d_macc, sizeof(double) * n * 3 * dimp));
+    if (!h->d_mwork) MAGI_HIP_CHECK(h, hipMalloc(&h->d_mwork, sizeof(double) * n * (dimp + 4)));
+    return MAGI_OK;
+}
+
+// (copies ride on the handle's own stream, as magi_sampler_run's do)
+static hipError_t metric_copy(magi_handle* h, void* dst, const void* src, size_t bytes, hipMemcpyKind kind) {
+    hipError_t e = hipMemcpyAsync(dst, src, bytes, kind, h->stream);
+    return e != hipSuccess ? e : hipStreamSynchronize(h->stream);
+}
+
+static int metric_idle_ctl(magi_handle* h, const char* who, std::vector<ChainCtl>& ctl) {
+    ctl.resize(h->n_chains);
+    MAGI_HIP_CHECK(h, metric_copy(h, ctl.data(), h->ch.ctl, sizeof(ChainCtl) * h->n_chains, hipMemcpyDeviceToHost));
+    for (int c = 0; c < h->n_chains; ++c)
+        if (ctl[c].phase != PH_IDLE) return magi_fail(h, MAGI_E_STATE, std::string(who) + ": chain " + std::to_string(c) + " is inside a transition");
+    return MAGI_OK;
+}
+
+int magi_sampler_set_metric(magi_handle* h, const double* inv_mass_X, const double* inv_mass_sig, const double* inv_mass_th) {
+    if (!h) return MAGI_E_BADARG;
+    if (!h->sampler_ready) return magi_fail(h, MAGI_E_STATE, "sampler not initialised");
+    (void)hipSetDevice(h->device);
+    const int given = (inv_mass_X ? 1 : 0) + (inv_mass_sig ? 1 : 0) + (inv_mass_th ? 1 : 0);
+    if (given != 0 && given != 3) return magi_fail(h, MAGI_E_BADARG, "magi_sampler_set_metric: give all three arrays, or none for the identity metric");
+    if (given == 0) {
+        if (h->ch.scale) { h->ch.scale = nullptr; drop_graph(h); }
+        return MAGI_OK;
+    }
+    int rc;
+    {   // (between two magi_sampler_run calls every chain is idle; after magi_sampler_profile it is not, and the header's promise would not hold)
+        std::vector<ChainCtl> ctl;
+        if ((rc = metric_idle_ctl(h, "magi_sampler_set_metric", ctl))) return rc;
+    }
+    const DevProblem& pb = h->pb;
+    std::vector<double> s((size_t)h->n_chains * pb.dimp);
+    for (int c = 0; c < h->n_chains; ++c) {
+        double* q = s.data() + (size_t)c * pb.dimp;
+        pack_state(pb, inv_mass_X + (size_t)c * pb.ND, inv_mass_sig + (size_t)c * pb.D, inv_mass_th + (size_t)c * pb.P, q);
+        for (int e = 0; e < pb.dim; ++e) {
+            if (!(q[e] > 0.0) || !std::isfinite(q[e]))
+                return magi_fail(h, MAGI_E_BADARG, "magi_sampler_set_metric: inverse mass of chain " + std::to_string(c) + ", state entry " + std::to_string(e) +
+                                                   " is not a finite positive number");
+            q[e] = std::sqrt(q[e]);
+        }
+        for (int e = pb.dim; e < pb.dimp; ++e) q[e] = 1.0;
+    }
+    if ((rc = metric_buffers(h))) return rc;
+    MAGI_HIP_CHECK(h, metric_copy(h, h->d_scale, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice));
+    if (!h->ch.scale) { h->ch.scale = h->d_scale; drop_graph(h); }
+    return MAGI_OK;
+}
+
+int magi_sampler_get_metric(magi_handle* h, double* inv_mass_X, double* inv_mass_sig, double* inv_mass_th) {
+    if (!h) return MAGI_E_BADARG;
+    if (!h->sampler_ready) return magi_fail(h, MAGI_E_STATE, "sampler not initialised");
+    (void)hipSetDevice(h->device);
+    const DevProblem& pb = h->pb;
+    std::vector<double> s((size_t)h->n_chains * pb.dimp, 1.0);
+    if (h->ch.scale) MAGI_HIP_CHECK(h, metric_copy(h, s.data(), h->d_scale, sizeof(double) * s.size(), hipMemcpyDeviceToHost));
+    for (double& v : s) v = v * v;                    // (sqrt(v * v) == v in binary floating point: set_metric(get_metric()) restores s exactly)
+    for (int c = 0; c < h->n_chains; ++c)
+        unpack_state(pb, s.data() + (size_t)c * pb.dimp, 1.0, inv_mass_X ? inv_mass_X + (size_t)c * pb.ND : nullptr,
+                     inv_mass_sig ? inv_mass_sig + (size_t)c * pb.D : nullptr, inv_mass_th ? inv_mass_th + (size_t)c * pb.P : nullptr);
+    return MAGI_OK;
+}
+
+int magi_sampler_metric_window(magi_handle* h, int on) {
+    if (!h) return MAGI_E_BADARG;
+    if (!h->sampler_ready) return magi_fail(h, MAGI_E_STATE, "sampler not initialised");
+    (void)hipSetDevice(h->device);
+    if (!on) {
+        if (h->ch.macc) { h->ch.macc = nullptr; drop_graph(h); }
+        h->window_k0.clear();
+        return MAGI_OK;
+    }
+    int rc;
+    std::vector<ChainCtl> ctl;
+    if ((rc = metric_idle_ctl(h, "magi_sampler_metric_window", ctl))) return rc;
+    if ((rc = metric_buffers(h))) return rc;
+    const DevProblem& pb = h->pb;
+    const size_t row = sizeof(double) * pb.dimp;
+    // sums := 0, shift := the state every chain holds (its trajectory-level proposal: what magi_sampler_get_state returns)
+    MAGI_HIP_CHECK(h, hipMemsetAsync(h->d_macc, 0, row * 3 * h->n_chains, h->stream));
+    MAGI_HIP_CHECK(h, hipMemcpy2DAsync(h->d_macc, row * 3, h->ch.vec + vec_off(pb, 0, V_CANDQ), row * V_COUNT, row, h->n_chains, hipMemcpyDeviceToDevice, h->stream));
+    MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    h->window_k0.resize(h->n_chains);
+    for (int c = 0; c < h->n_chains; ++c) h->window_k0[c] = ctl[c].k;
+    if (!h->ch.macc) { h->ch.macc = h->d_macc; drop_graph(h); }
+    return MAGI_OK;
+}
+
+int magi_sampler_adapt_metric(magi_handle* h, int n, double kappa, double rel_floor, int restart_adapt_steps, double* step_size_out) {
+    if (!h) return MAGI_E_BADARG;
+    if (!h->sampler_ready) return magi_fail(h, MAGI_E_STATE, "sampler not initialised");
+    if (!h->ch.macc || (int)h->window_k0.size() != h->n_chains) return magi_fail(h, MAGI_E_STATE, "magi_sampler_adapt_metric: no metric window is open");
+    if (n < 2) return magi_fail(h, MAGI_E_BADARG, "magi_sampler_adapt_metric: a variance needs n >= 2 states");
+    if (!(kappa >= 0.0) || !std::isfinite(kappa) || !(rel_floor > 0.0) || !std::isfinite(rel_floor))
+        return magi_fail(h, MAGI_E_BADARG, "magi_sampler_adapt_metric: need a finite kappa >= 0 and a finite rel_floor > 0");
+    (void)hipSetDevice(h->device);
+    int rc;
+    std::vector<ChainCtl> ctl;
+    if ((rc = metric_idle_ctl(h, "magi_sampler_adapt_metric", ctl))) return rc;
+    for (int c = 0; c < h->n_chains; ++c)
+        if (ctl[c].k - h->window_k0[c] != n)
+            return magi_fail(h, MAGI_E_BADARG, "magi_sampler_adapt_metric: n = " + std::to_string(n) + ", but chain " + std::to_string(c) + " has finished " +
+                                               std::to_string(ctl[c].k - h->window_k0[c]) + " transitions since the window was opened");
+    const DevProblem& pb = h->pb;
+    const size_t dimp = (size_t)pb.dimp;
+    // min s of the metric in force (1 under the identity metric, whose ones the kernel must find where it leaves a chain alone)
+    std::vector<double> s((size_t)h->n_chains * dimp, 1.0), min_old(h->n_chains, 1.0);
+    if (h->ch.scale) {
+        MAGI_HIP_CHECK(h, metric_copy(h, s.data(), h->d_scale, sizeof(double) * s.size(), hipMemcpyDeviceToHost));
+        for (int c = 0; c < h->n_chains; ++c) min_old[c] = *std::min_element(s.begin() + c * dimp, s.begin() + c * dimp + pb.dim);
+    } else {
+        MAGI_HIP_CHECK(h, metric_copy(h, h->d_scale, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice));
+    }
+    if ((rc = magi_launch_metric_adapt(h, h->n_chains, n, kappa, rel_floor, h->d_macc, h->d_scale, h->d_mwork, h->stream))) return rc;
+    std::vector<double> tail((size_t)h->n_chains * 4);
+    MAGI_HIP_CHECK(h, hipMemcpy2DAsync(tail.data(), sizeof(double) * 4, h->d_mwork + dimp, sizeof(double) * (dimp + 4), sizeof(double) * 4, h->n_chains,
+                                       hipMemcpyDeviceToHost, h->stream));
+    MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    int kept = 0;
+    for (int c = 0; c < h->n_chains; ++c) {
+        const bool keep = tail[(size_t)c * 4 + 2] != 0.0;
+        kept += keep ? 1 : 0;
+        if (restart_adapt_steps >= 0) {
+            // the step along the stiffest coordinate is kept: eps min(s) is what bounds a stable leapfrog step
+            const double eps = keep ? ctl[c].da_step_size : ctl[c].da_step_size * min_old[c] / tail[(size_t)c * 4 + 1];
+            ctl[c].da_step_size = eps;
+            ctl[c].da_error_sum = 0.0; ctl[c].da_log_avg = 0.0; ctl[c].da_step = 0;
+            ctl[c].da_log_shrink = std::log(10.0 * eps);
+        }
+        if (step_size_out) step_size_out[c] = ctl[c].da_step_size;
+    }
+    if (restart_adapt_steps >= 0) {
+        MAGI_HIP_CHECK(h, metric_copy(h, h->ch.ctl, ctl.data(), sizeof(ChainCtl) * h->n_chains, hipMemcpyHostToDevice));
+        h->cfg.n_adapt = restart_adapt_steps;
+    }
+    h->ch.scale = h->d_scale;
+    h->ch.macc = nullptr;              // the window is closed
+    h->window_k0.clear();
+    drop_graph(h);
+    return kept;
 }
 
 int magi_sample(magi_handle* h, const magi_sampler_cfg* cfg, int n_chains, const double* X0, const double* sig_pre0,

@@ -141,6 +141,9 @@ __device__ __forceinline__ void decide_block(const DevProblem& pb, const DevChai
     constexpr int OPS_PER = (OPS_COUNT * OPS_W + PT_THREADS - 1) / PT_THREADS;
     double ops_v[OPS_PER];
     reduce_prefetch_ops_load<OPS_PER>(pb, ch.vec + vec_off(pb, chain, 0), DriftT<DRIFT>::D + DriftT<DRIFT>::P, ops_v);
+    // diagonal metric: s of the D + P parameter entries, for the lanes of leap_reduce that finish them (waves 0 and 1)
+    double msc = 1.0;
+    if (ch.scale && tid < 128 && (tid & 63) < DriftT<DRIFT>::D + DriftT<DRIFT>::P) msc = ch.scale[(size_t)chain * pb.dimp + pb.ND + (tid & 63)];
     __builtin_amdgcn_sched_barrier(0);
     if (all_done) return;
     if (chain == 0 && tid == PT_THREADS - 4) __hip_atomic_fetch_add(&ch.gctl->slots, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);     // (no return value: fire and forget)
@@ -236,7 +239,7 @@ __device__ __forceinline__ void decide_block(const DevProblem& pb, const DevChai
         MAGI_STAMP(decide, 1);
         if (!leaf && tid == 64) shs[16] = cfg.anneal ? temperature(0, cfg.min_temp) : 1.0;
         // ---- add the streaming kernel's partial sums, finish the parameter entries -----------------------
-        const ReduceOut ro = leap_reduce<DRIFT>(pb, ch, chain, vb, par, s_par, lp, pre, sh, shs, s_ops, s_cst);
+        const ReduceOut ro = leap_reduce<DRIFT>(pb, ch, chain, vb, par, s_par, lp, pre, sh, shs, s_ops, s_cst, msc);
         MAGI_STAMP(decide, 4);
         const double L = ro.L;
         double* qcur = vb + (size_t)(V_Q + lp.cur) * sv;      // the state that was evaluated
@@ -386,6 +389,7 @@ __device__ __forceinline__ void decide_block(const DevProblem& pb, const DevChai
             ch.d_flags[o] = (c.not_div ? 0 : 1) | (continue_tree ? 2 : 0) | (c.is_accepted ? 4 : 0);
         }
         if (k >= cfg.burnin) vop |= VOP_OUT;
+        if (ch.macc) vop |= VOP_ACC;                 // a metric window is open: the point phase adds the state this transition leaves
         if (c.is_accepted) c.beta_cache = c.beta_k;
         c.da_step_size = shs[1];
         c.da_error_sum = shs[2];

@@ -126,7 +126,7 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
     const int ngrp = min(nch - c0, MC), kpw = (ngrp + 3) >> 2;       // chains of this group; chains per wave for theta'
     auto ldb = [](const double* sbase, unsigned boff) { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(sbase) + boff); };
     double rows[4][P];
-    int lcur = 0; double lhs = 0.0, leps = 0.0, qv0 = 0.0, qv1 = 0.0, pv0 = 0.0, pv1 = 0.0, parv = 0.0; bool lder = false;
+    int lcur = 0; double lhs = 0.0, leps = 0.0, qv0 = 0.0, qv1 = 0.0, pv0 = 0.0, pv1 = 0.0, parv = 0.0, msc = 1.0; bool lder = false;
     const int cg = wave * kpw + lj;                                    // this lane's own (chain cg of the group, parameter li)
     const bool mine = lj < kpw && cg < ngrp && li < P;
     if (kind != TK_FH) {
@@ -153,6 +153,7 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
             qv0 = vb[(size_t)V_Q * pb.dimp]; qv1 = vb[(size_t)V_Q1 * pb.dimp];
             pv0 = vb[(size_t)V_P * pb.dimp]; pv1 = vb[(size_t)V_P1 * pb.dimp];
             parv = ch.par[(size_t)cc * PAR_COUNT + PAR_TH + li];
+            msc = metric_scale(ch, pb.dimp, cc, pb.ND + D + li);         // (diagonal metric: s of this parameter entry)
         }
     }
     // which of the 16 chain columns take part in this slot (bit c): every lane fetches its own chain's flag now, not at the stores
@@ -233,7 +234,7 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
             const double qv = lcur ? qv1 : qv0, pv = lcur ? pv1 : pv0;
             const double ex = m_exp(qv);
             const double sg = ex / (1.0 + ex);                       // == par[PAR_SGT] of that state (compute_par_entry)
-            const double qnx = next_entry_pre(pv, qv, lhs, leps, theta_entry_grad(pb.beta_inv, tpp, sg));
+            const double qnx = next_entry_pre(pv, qv, lhs, leps, theta_entry_grad(pb.beta_inv, tpp, sg), msc);
             thp = m_log(1.0 + m_exp(qnx));                           // == par'[PAR_TH] (compute_par_entry)
         }
         if (mine) th_s[cg * 8 + li] = thp;

@@ -20,7 +20,7 @@ template <int DRIFT>
 struct GridPoint {     // component d of grid index i of one chain (one lane)
     using DR = DriftT<DRIFT>;
     static constexpr int D = DR::D, P = DR::P;
-    struct Ops { double y, phe, rhoe, cpk[4], crk[4], x[D], th[P], sig2, qprev, gold, tm; };
+    struct Ops { double y, phe, rhoe, cpk[4], crk[4], x[D], th[P], sig2, qprev, gold, tm, sc; };
 
     // the lane's own operands: independent of the products, so their latency overlaps the partial sums
     static __device__ __forceinline__ Ops load(const DevProblem& pb, const DevChains& ch, const LeafPlan& lp, int cc, int i, int d) {
@@ -32,7 +32,7 @@ struct GridPoint {     // component d of grid index i of one chain (one lane)
         const int e = d * N + i;
         o.y = pb.yobs[e];
         o.tm = point_time<DR>(pb, i);
-        o.phe = 0.0; o.rhoe = 0.0; o.qprev = 0.0; o.gold = 0.0;
+        o.phe = 0.0; o.rhoe = 0.0; o.qprev = 0.0; o.gold = 0.0; o.sc = 1.0;
 #pragma unroll
         for (int k = 0; k < 4; ++k) { o.cpk[k] = 0.0; o.crk[k] = 0.0; }
         if (lp.leaf) {
@@ -41,6 +41,7 @@ struct GridPoint {     // component d of grid index i of one chain (one lane)
                 o.gold = (vb + (size_t)V_G * dimp)[e];
             }
             o.phe = (vb + (size_t)(V_P + lp.cur) * dimp)[e];
+            o.sc = metric_scale(ch, dimp, cc, e);      // (diagonal metric: s of this entry, 1 when none is set)
             o.rhoe = (vb + (size_t)V_RHOSUB * dimp)[e];
             const double* ckp = vb + (size_t)V_CKP0 * dimp;
             const double* ckr = vb + (size_t)V_CKRHO0 * dimp;
@@ -94,7 +95,8 @@ struct GridPoint {     // component d of grid index i of one chain (one lane)
             double* rho = vb + (size_t)V_RHOSUB * dimp;
             double* ckp = vb + (size_t)V_CKP0 * dimp;
             double* ckr = vb + (size_t)V_CKRHO0 * dimp;
-            const double pn = o.phe + lp.hs * gx;
+            const double sgx = o.sc * gx;           // whitened momentum: p += hs (s . g), x += eps (s . p)
+            const double pn = o.phe + lp.hs * sgx;
             *(vb + (size_t)V_PLEAF * dimp + e) = pn;
             const double rs = o.rhoe + pn;
             *(rho + e) = rs;
@@ -104,9 +106,9 @@ struct GridPoint {     // component d of grid index i of one chain (one lane)
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (k < lp.nchk) { const double df = rs - o.crk[k]; pk[PK_DOT + 2 * k] = df * o.cpk[k]; pk[PK_DOT + 2 * k + 1] = df * pn; }
-            const double pnext = pn + lp.hs * gx;
+            const double pnext = pn + lp.hs * sgx;
             *(vb + (size_t)(V_P + (lp.cur ^ 1)) * dimp + e) = pnext;
-            const double xn = xd + lp.eps * pnext;
+            const double xn = xd + lp.eps * (o.sc * pnext);
             *(vb + (size_t)(V_Q + (lp.cur ^ 1)) * dimp + e) = xn;
             if (ch.mc) ch.xop[xop_off(pb, ch.n_chains, xop_buf, cc, d, i)] = xn;      // (three or more chains: the matrix-core stream of the NEXT slot reads this mirror)
         }
@@ -303,7 +305,8 @@ __device__ __forceinline__ void point_block_sep(const DevProblem& pb, const DevC
                 double* rho = vb + (size_t)V_RHOSUB * dimp;
                 double* ckp = vb + (size_t)V_CKP0 * dimp;
                 double* ckr = vb + (size_t)V_CKRHO0 * dimp;
-                const double pn = ops.phe + lp.hs * gx;
+                const double sgx = ops.sc * gx;       // (whitened momentum, as GridPoint::finish)
+                const double pn = ops.phe + lp.hs * sgx;
                 *(vb + (size_t)V_PLEAF * dimp + e) = pn;
                 const double rs = ops.rhoe + pn;
                 *(rho + e) = rs;
@@ -313,9 +316,9 @@ __device__ __forceinline__ void point_block_sep(const DevProblem& pb, const DevC
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
                     if (k < lp.nchk) { const double df = rs - ops.crk[k]; pk[PK_DOT + 2 * k] = df * ops.cpk[k]; pk[PK_DOT + 2 * k + 1] = df * pn; }
-                const double pnext = pn + lp.hs * gx;
+                const double pnext = pn + lp.hs * sgx;
                 *(vb + (size_t)(V_P + (lp.cur ^ 1)) * dimp + e) = pnext;
-                xn = xd + lp.eps * pnext;
+                xn = xd + lp.eps * (ops.sc * pnext);
                 *(vb + (size_t)(V_Q + (lp.cur ^ 1)) * dimp + e) = xn;
             }
         }
@@ -381,7 +384,7 @@ __device__ __forceinline__ void boundary_block(const DevProblem& pb, const DevCh
     const size_t dimp = pb.dimp;
     const int vop = lp.vop;
     const bool ends = (vop & VOP_ENDS) != 0, cand = (vop & VOP_CAND) != 0, takel = (vop & VOP_TAKE_LEAF) != 0, outp = (vop & VOP_OUT) != 0;
-    const bool draw = (vop & VOP_DRAW) != 0, dbl = (vop & VOP_DOUBLE) != 0;
+    const bool draw = (vop & VOP_DRAW) != 0, dbl = (vop & VOP_DOUBLE) != 0, acc = (vop & VOP_ACC) != 0;
     double* vb = ch.vec + vec_off(pb, cc, 0);
     if (t == PT_THREADS - 1) {
 #pragma unroll
@@ -419,8 +422,10 @@ __device__ __forceinline__ void boundary_block(const DevProblem& pb, const DevCh
                 if (ends || (cand && takel)) { ql = qleaf[e]; gl = g[e]; }
                 if (ends) { pn = pleaf[e]; rho_v = rho[e]; rs_v = rhosub[e]; po = pO[e]; }
                 if (cand && !takel) { sq = subq[e]; sg = subg[e]; }
-                if ((outp || draw) && !cand) { cq = candq[e]; cg = candg[e]; }
+                if ((outp || draw || acc) && !cand) { cq = candq[e]; cg = candg[e]; }
                 if (start_loads) { p0 = pS[e]; q0 = qS[e]; g0 = gS[e]; }
+                double sc = 1.0;
+                if (dbl) sc = metric_scale(ch, dimp, cc, e);
                 // ---- merge ----
                 if (ends) {
                     pE[e] = pn; qE[e] = ql; gE[e] = gl;
@@ -435,6 +440,14 @@ __device__ __forceinline__ void boundary_block(const DevProblem& pb, const DevCh
                     candq[e] = cq; candg[e] = cg;
                 }
                 if (outp) ch.samples[(size_t)lp.vout * dimp + e] = cq;
+                // ---- metric window: the state the chain holds after the transition that has just ended (`acc` is raised with ch.macc set
+                //      only: decide.h).  Once per transition: a round trip of its own here keeps the sums out of the registers of every other op ----
+                if (acc) {
+                    double* m = ch.macc + (size_t)cc * 3 * dimp + e;
+                    const double dq = cq - m[0];
+                    m[dimp] += dq;
+                    m[2 * dimp] += dq * dq;
+                }
                 // ---- next transition: momentum, both ends = the proposal ----
                 if (draw) {
                     const double z = rng_normal_elem((unsigned)e, lp.step_k, lp.chain_id, lp.seed);
@@ -443,11 +456,11 @@ __device__ __forceinline__ void boundary_block(const DevProblem& pb, const DevCh
                     pk[PK_PP] += z * z;
                     p0 = z; q0 = cq; g0 = cg;
                 }
-                // ---- next doubling: first half / full step from the selected end (identity mass: p_half = p + eps/2 grad, q' = q + eps p_half) ----
+                // ---- next doubling: first half / full step from the selected end (whitened momentum: p_half = p + eps/2 (s . grad), q' = q + eps (s . p_half); s = 1 without a metric) ----
                 if (dbl) {
-                    const double ph = p0 + lp.hs * g0;
+                    const double ph = p0 + lp.hs * (sc * g0);
                     *(vb + (size_t)(V_P + lp.cur) * dimp + e) = ph;
-                    const double qn = q0 + lp.eps * ph;
+                    const double qn = q0 + lp.eps * (sc * ph);
                     *(vb + (size_t)(V_Q + lp.cur) * dimp + e) = qn;
                     rhosub[e] = 0.0;
                     if (grid) {

@@ -39,9 +39,11 @@ __device__ __forceinline__ void part_rows_sum(const double* part, int nwg, int r
 // d L / d theta_pre_p from the global sum tp_p (magi_v2.py:318-323, 335-337 chained through softplus)
 __device__ __forceinline__ double theta_entry_grad(double beta_inv, double tpp, double sg) { return -0.5 * beta_inv * tpp * sg + (1.0 - sg); }
 // position of a parameter entry after completing this leaf's momentum step and taking the next half step
-__device__ __forceinline__ double next_entry_pre(double ph, double q, double hs, double eps, double gj) {
-    const double pn = ph + hs * gj;
-    return q + eps * (pn + hs * gj);
+// (`s`: the entry's metric scale, 1 under the identity metric -- the momentum is the whitened one, DevChains::scale)
+__device__ __forceinline__ double next_entry_pre(double ph, double q, double hs, double eps, double gj, double s) {
+    const double sg = s * gj;
+    const double pn = ph + hs * sg;
+    return q + eps * (s * (pn + hs * sg));
 }
 
 struct ReduceOut {
@@ -115,7 +117,8 @@ template <int DRIFT>
 __device__ __forceinline__ ReduceOut leap_reduce(const DevProblem& pb, const DevChains& ch, int chain, double* vb, double* par, const double* par_r,
                                                  const LeafPlan& lp, const double (&pre)[RedLayout<DRIFT>::PER_WAVE], double* sh, double* shs,
                                                  const double* ops = nullptr /* LDS copy made by reduce_prefetch_ops, or null */,
-                                                 const double* cst = nullptr /* LDS: N_ds[MAX_D], LB[MAX_D], or null */) {
+                                                 const double* cst = nullptr /* LDS: N_ds[MAX_D], LB[MAX_D], or null */,
+                                                 double msc = 1.0 /* threads j and 64 + j, j < D + P: metric scale of parameter entry j (DevChains::scale) */) {
     using DR = DriftT<DRIFT>;
     constexpr int D = DR::D, P = DR::P;
     const int ND = pb.ND, dimp = pb.dimp;
@@ -191,7 +194,8 @@ __device__ __forceinline__ ReduceOut leap_reduce(const DevProblem& pb, const Dev
         if (plane) {
             g[ND + j] = gj;
             if (leaf) {
-                const double pn = pj + lp.hs * gj;
+                const double sgj = msc * gj;                   // (whitened momentum, as the point phase: leap_point.h)
+                const double pn = pj + lp.hs * sgj;
                 const double rs = rj + pn;
                 pleaf[ND + j] = pn;
                 rho[ND + j] = rs;
@@ -200,9 +204,9 @@ __device__ __forceinline__ ReduceOut leap_reduce(const DevProblem& pb, const Dev
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
                     if (k < lp.nchk) { const double df = rs - crj[k]; a[k] = df * cpj[k]; b[k] = df * pn; }
-                const double pnext = pn + lp.hs * gj;          // speculative next half step
+                const double pnext = pn + lp.hs * sgj;         // speculative next half step
                 phn[ND + j] = pnext;
-                qn[ND + j] = qj + lp.eps * pnext;
+                qn[ND + j] = qj + lp.eps * (msc * pnext);
             }
         }
         t4 = row16_sum(t4); lj = row16_sum(lj); ppj = row16_sum(ppj);
@@ -235,7 +239,7 @@ __device__ __forceinline__ ReduceOut leap_reduce(const DevProblem& pb, const Dev
                 gj = theta_entry_grad(pb.beta_inv, tpp, sg);
             }
             const double phv = ops ? ops[(OPS_P + lp.cur) * OPS_W + jj] : ph[ND + jj], qv = ops ? ops[(OPS_Q + lp.cur) * OPS_W + jj] : q[ND + jj];
-            sh[21 * 16 + jj] = next_entry_pre(phv, qv, lp.hs, lp.eps, gj);      // parking block of 64 doubles behind block_sum's scratch: read by leap_next_par
+            sh[21 * 16 + jj] = next_entry_pre(phv, qv, lp.hs, lp.eps, gj, msc);      // parking block of 64 doubles behind block_sum's scratch: read by leap_next_par
         }
     } else if (threadIdx.x < 192) {
         // wave 2, concurrently: t3 = sum_d N_d log(2 pi sigma_d^2) of the evaluated state (one m_log; combined after the barrier)

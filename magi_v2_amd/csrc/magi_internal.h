@@ -118,7 +118,8 @@ enum BoundaryOp {
     VOP_TAKE_LEAF = 4,
     VOP_OUT = 8,         // sample row `vout` <- trajectory proposal
     VOP_DRAW = 16,       // transition `step_k` starts: momentum ~ N(0, I) at both ends, ends <- proposal, sum p.p
-    VOP_DOUBLE = 32      // a doubling starts from end `ndir`: first half / full step into buffer `cur` (+ operand mirrors, parameter block)
+    VOP_DOUBLE = 32,     // a doubling starts from end `ndir`: first half / full step into buffer `cur` (+ operand mirrors, parameter block)
+    VOP_ACC = 64         // a transition has ended while a metric window is open (DevChains::macc): window sums += the state the chain now holds
 };
 
 // Per-chain scalar state of the device-resident sampler ---------------------------------------
@@ -233,7 +234,19 @@ struct DevChains {
     int* d_leapfrogs;
     int* d_depth;
     int* d_flags;         // bit0 has_divergence, bit1 reach_max_depth, bit2 is_accepted
+    // diagonal metric (metric.hip, magi_sampler_set_metric).  HMC with M^-1 = diag(s^2) on q is HMC with the identity metric on z = q / s: the
+    // momentum vectors hold the WHITENED momentum, and s enters only where momentum meets gradient or position,
+    //     p_half = p + hs (s . g),   q' = q + eps (s . p_half);
+    // the draw, p.p, rho, the checkpoints, every U-turn sum and the energies are those of the identity metric.
+    const double* scale;  // [n_chains][dimp] s = sqrt(inverse mass) in state order; nullptr: identity
+    double* macc;         // [n_chains][3][dimp] metric window: shift c, S1 = sum (q - c), S2 = sum (q - c)^2 over the states held after each
+                          // transition that ended while the window was open (VOP_ACC); nullptr: no window
 };
+
+// s of entry e of chain cc (1 under the identity metric: a wave-uniform branch around the load, and x * 1.0 is x)
+__device__ __forceinline__ double metric_scale(const DevChains& ch, size_t dimp, int cc, int e) {
+    return ch.scale ? ch.scale[(size_t)cc * dimp + e] : 1.0;
+}
 
 // element (slot parity b, chain, component d, grid index i) of the operand-order mirror.  A grid point's chains are contiguous:
 // 16 per point (one 128-B line), or 8 (64 B) when there are at most 8 chains -- every stream workgroup reads its operand slices of
@@ -982,6 +995,12 @@ struct magi_handle {
     int epoch = 0;
     long long* d_chain_ids = nullptr;
     double* d_fin = nullptr;         // [cap_chains][8] finalize outputs
+    // diagonal metric (capi.hip: magi_sampler_set_metric ...; metric.hip).  ch.scale / ch.macc point at these while a metric is set / a
+    // window is open and are null otherwise: kernel arguments, so a change between null and non-null drops the captured graph
+    double* d_scale = nullptr;       // [cap_chains][dimp]
+    double* d_macc = nullptr;        // [cap_chains][3][dimp]
+    double* d_mwork = nullptr;       // [cap_chains][dimp + 4] k_metric_adapt: variances | median, min s, status
+    std::vector<int> window_k0;      // transition index of every chain when the open window was opened (empty: no window)
     size_t samples_cap = 0, diag_cap = 0, vop_elems = 0;
     // magi_sampler_profile: when set, the launchers of k_stream / k_point attach these events to the launch (hipExtLaunchKernel:
     // they take the kernel's own begin / end time stamps, what rocprofv3's kernel trace reports)
@@ -1057,6 +1076,10 @@ size_t magi_sep_tpart_elems(const DevProblem& pb, int n_chains);        // leap.
 size_t magi_sep_vop_elems(const DevProblem& pb, int n_chains);
 void magi_sep_traffic(const DevProblem& pb, int n_chains, double* stores, double* operands, double* point_reads, double* mirror_writes);   // leap.hip
 int magi_launch_init_chains(magi_handle* h, const long long* d_chain_ids, hipStream_t s);
+// metric.hip: the regularised diagonal metric of every chain from the window sums macc ([n][3][dimp], n_win states each) ->
+// scale [n][dimp]; work [n][dimp + 4]: the variances, then {median, min s, status (0 set, 1 median 0: scale left as it was), -}
+int magi_launch_metric_adapt(magi_handle* h, int n_chains, int n_win, double kappa, double rel_floor, const double* macc, double* scale,
+                             double* work, hipStream_t s);
 int magi_ensure_chains(magi_handle* h, int n_chains);
 // build.hip: dense device matrices -> packed device storage (sym / transpose / band)
 int magi_pack_matrices(magi_handle* h, int N, int D, int bandsize, const double* dC_inv, const double* dM,

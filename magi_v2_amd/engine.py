@@ -69,6 +69,10 @@ _SYMBOLS = {
     "magi_sample": (C.c_int, [C.c_void_p, C.POINTER(SamplerCfg), C.c_int, _dp, _dp, _dp, C.c_uint64, _lp, _dp, _dp, _dp]),
     "magi_sampler_get_checkpoint": (C.c_int, [C.c_void_p, _dp]),
     "magi_sampler_set_checkpoint": (C.c_int, [C.c_void_p, _dp]),
+    "magi_sampler_set_metric": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    "magi_sampler_get_metric": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    "magi_sampler_metric_window": (C.c_int, [C.c_void_p, C.c_int]),
+    "magi_sampler_adapt_metric": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_int, _dp]),
     "magi_sampler_run_stats": (C.c_int, [C.c_void_p, _lp, _lp]),
     "magi_sampler_profile": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _lp]),
     "magi_time_gradient": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
@@ -529,11 +533,74 @@ class MagiEngine:
         self._check(self._lib.magi_sampler_get_checkpoint(self._h, _ptr(sc)))
         return {"X": X, "sig_pre": sp, "th_pre": tp, "scalars": sc}
 
-    def sampler_resume(self, cfg: SamplerCfg, ckpt, seed: int, chain_ids: Optional[Sequence[int]] = None):
-        """sampler_init at the checkpointed states + the checkpoint's scalars: the next sampler_run continues the run."""
+    def sampler_resume(self, cfg: SamplerCfg, ckpt, seed: int, chain_ids: Optional[Sequence[int]] = None, metric=None):
+        """sampler_init at the checkpointed states + the checkpoint's scalars: the next sampler_run continues the run.  A checkpoint does
+        not carry the metric: ``metric`` = what sampler_metric() returned when it was taken (and ``cfg.num_adaptation_steps`` the value
+        in force then: after a sampler_warmup, the ``n_adapt - stop`` of its last adapted window)."""
         self.sampler_init(cfg, ckpt["X"], ckpt["sig_pre"], ckpt["th_pre"], seed, chain_ids)
+        if metric is not None:
+            self.sampler_set_metric(*metric)
         sc = _f64(ckpt["scalars"], (self.n_chains, self.CKPT_SCALARS))
         self._check(self._lib.magi_sampler_set_checkpoint(self._h, _ptr(sc)))
+
+    # -- diagonal metric (include/magi_hip.h: magi_sampler_set_metric ...) ---------------------------
+    def sampler_set_metric(self, inv_mass_X=None, inv_mass_sig=None, inv_mass_th=None):
+        """Per-chain diagonal inverse mass in the layouts of sampler_init ([n, N, D], [n, D], [n, P]; one chain may drop the leading
+        axis); no argument: back to the identity metric.  Governs the next transition from its first half step."""
+        given = [a is not None for a in (inv_mass_X, inv_mass_sig, inv_mass_th)]
+        if not any(given):
+            self._check(self._lib.magi_sampler_set_metric(self._h, None, None, None))
+            return
+        if not all(given):
+            raise ValueError("give all three inverse-mass arrays, or none for the identity metric")
+        n, X, sp, tp = self._states(inv_mass_X, inv_mass_sig, inv_mass_th)
+        if n != self.n_chains:
+            raise ValueError(f"the sampler has {self.n_chains} chains, the metric {n}")
+        self._check(self._lib.magi_sampler_set_metric(self._h, _ptr(X), _ptr(sp), _ptr(tp)))
+
+    def sampler_metric(self):
+        """(inv_mass_X [n, N, D], inv_mass_sig [n, D], inv_mass_th [n, P]) in force; ones under the identity metric."""
+        n = self.n_chains
+        X, sp, tp = np.empty((n, self.N, self.D)), np.empty((n, self.D)), np.empty((n, self.P))
+        self._check(self._lib.magi_sampler_get_metric(self._h, _ptr(X), _ptr(sp), _ptr(tp)))
+        return X, sp, tp
+
+    def sampler_metric_window(self, on=True):
+        """Open (shift := the chains' current states, sums := 0) or close the window whose states sampler_adapt_metric turns into a metric."""
+        self._check(self._lib.magi_sampler_metric_window(self._h, 1 if on else 0))
+
+    def sampler_adapt_metric(self, n, kappa=5.0, rel_floor=1e-3, restart_adapt_steps=-1):
+        """The open window of n transitions -> every chain's metric (regularised sample variances; the floor is rel_floor x the chain's
+        median variance); restart_adapt_steps >= 0 restarts dual averaging at the rescaled step with that many adaptation steps left.
+        Returns (step sizes [n_chains] after the call, number of chains whose metric was left unchanged)."""
+        ss = np.empty(self.n_chains)
+        rc = self._lib.magi_sampler_adapt_metric(self._h, int(n), float(kappa), float(rel_floor), int(restart_adapt_steps), _ptr(ss))
+        if rc < 0:
+            self._check(rc)
+        return ss, rc
+
+    def sampler_warmup(self, schedule, n_adapt=None, kappa=5.0, rel_floor=1e-3):
+        """Run the transitions of ``schedule`` = [(start, stop, adapt_metric_at_stop)] (magi_v2_amd.host.warmup_schedule; contiguous, from
+        the transition the chains stand at): a window with adapt_metric_at_stop set is accumulated on the device and turned into the
+        metric at its end, dual averaging restarting with ``n_adapt - stop`` adaptation steps left.  ``n_adapt``: the sampler's adaptation
+        steps, by default the schedule's end (warmup_schedule tiles [0, n_adapt)).  Returns (leapfrogs, device ms,
+        [per adapted window: dict(start, stop, step_size, unchanged)])."""
+        schedule = list(schedule)
+        if n_adapt is None:
+            n_adapt = schedule[-1][1] if schedule else 0
+        lf = ms = 0
+        windows = []
+        for start, stop, adapt in schedule:
+            if stop <= start:
+                raise ValueError(f"empty window [{start}, {stop})")
+            if adapt:
+                self.sampler_metric_window(True)
+            a, b = self.sampler_run(stop - start)
+            lf, ms = lf + a, ms + b
+            if adapt:
+                ss, kept = self.sampler_adapt_metric(stop - start, kappa, rel_floor, restart_adapt_steps=max(int(n_adapt) - stop, 0))
+                windows.append({"start": int(start), "stop": int(stop), "step_size": ss, "unchanged": int(kept)})
+        return lf, ms, windows
 
     def sampler_run_stats(self):
         """(leapfrog slots issued, graph launches) of the last sampler_run."""

@@ -149,6 +149,44 @@ def resolve_drift(f_vec, D: int, P: int) -> str:
 
 
 # --------------------------------------------------------------------------------------------
+# warm-up windows of the diagonal-metric adaptation (MAGI_v2.predict(adapt_metric=True))
+# --------------------------------------------------------------------------------------------
+
+
+def warmup_schedule(num_burnin: int, n_adapt: int, init_buffer: int = 75, base_window: int = 25, term_buffer: int = 50):
+    """Stan's windowed warm-up over the adaptation transitions [0, n_adapt) of a burn-in of ``num_burnin``: a fast initial buffer (step
+    size only), slow windows whose states become the metric at their end -- the first ``base_window`` long, each next one twice as long,
+    the last one stretched to the terminal buffer when the one after it would not fit -- and a fast terminal buffer.  When the three
+    do not fit into n_adapt (with the defaults: n_adapt < 150) they become 15 % / 75 % / 10 % of it; a slow part too short for a
+    variance (fewer than 2 transitions) leaves one fast window.  Returns [(start, stop, adapt_metric_at_stop)], tiling [0, n_adapt);
+    empty for n_adapt = 0.  A pure function."""
+    num_burnin, n_adapt = int(num_burnin), int(n_adapt)
+    init_buffer, base_window, term_buffer = int(init_buffer), int(base_window), int(term_buffer)
+    if not 0 <= n_adapt <= num_burnin:
+        raise ValueError(f"need 0 <= n_adapt <= num_burnin, got {n_adapt}, {num_burnin}")
+    if init_buffer < 0 or base_window < 1 or term_buffer < 0:
+        raise ValueError("need init_buffer >= 0, base_window >= 1, term_buffer >= 0")
+    if n_adapt == 0:
+        return []
+    if init_buffer + base_window + term_buffer > n_adapt:
+        init_buffer, term_buffer = int(0.15 * n_adapt), int(0.1 * n_adapt)
+        base_window = n_adapt - init_buffer - term_buffer
+    if base_window < 2:
+        return [(0, n_adapt, False)]
+    out = [(0, init_buffer, False)] if init_buffer else []
+    start, size, end_slow = init_buffer, base_window, n_adapt - term_buffer
+    while start < end_slow:
+        stop = start + size
+        if stop + 2 * size > end_slow:          # the next (doubled) window would not fit: this one runs to the terminal buffer
+            stop = end_slow
+        out.append((start, stop, True))
+        start, size = stop, 2 * size
+    if term_buffer:
+        out.append((end_slow, n_adapt, False))
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # synthetic SEIR grids (BASELINE.json configs 2, 3, 5; SURVEY 8d)
 # --------------------------------------------------------------------------------------------
 
