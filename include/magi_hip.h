@@ -141,6 +141,28 @@ int magi_set_problem(magi_handle* h, const double* mu, const double* N_ds,
  * independent of the grid the matrices were built on.  A group handle has none of its own: MAGI_E_STATE. */
 int magi_set_times(magi_handle* h, const double* t, int n);
 
+/* Support of every ODE parameter (opt-in; the reference has theta = softplus(theta_pre) for all of them, magi_v2.py:303-306, 319, and
+ * that stays the default).  The sampler, the momentum, the metric and dual averaging act on theta_pre as before; the support of
+ * parameter p decides how theta_p, d theta_p / d pre and the log-Jacobian term of the target follow from it, with
+ * sp = log(1 + exp(pre)) and sg = exp(pre) / (1 + exp(pre)):
+ *   MAGI_THETA_POSITIVE   theta = sp              d theta = sg     log-Jacobian pre - sp   (its derivative 1 - sg)
+ *   MAGI_THETA_LOWER      theta = bound + sp      d theta = sg     log-Jacobian pre - sp   (1 - sg)
+ *   MAGI_THETA_UPPER      theta = bound - sp      d theta = -sg    log-Jacobian pre - sp   (1 - sg)
+ *   MAGI_THETA_REAL       theta = pre             d theta = 1      log-Jacobian 0          (0)
+ * kind[P], bound[P]; the bound of a POSITIVE or REAL entry is ignored and reported as 0.  kind = NULL: back to all-POSITIVE.  A handle
+ * whose support was never set, or was set to all-POSITIVE, computes bit for bit what it computed without this call (the kernels test one
+ * pointer and run the instructions they ran before).  The support belongs to the problem: magi_set_problem resets it to all-POSITIVE, so
+ * the call comes after it; it governs magi_logpost_grad*, the next magi_sampler_init (it invalidates the sampler state and the captured
+ * graph, as magi_set_times does), the theta block of magi_sampler_summarize, and the handle as a member of a group (each member brings
+ * its own; members of one group may differ).  sigma^2 is not affected.  theta_pre in and out of every call stays theta_pre.
+ * Errors, each leaving the handle as it was: MAGI_E_BADARG for P other than the problem's, a kind out of range, a non-finite bound of a
+ * LOWER or UPPER entry; MAGI_E_STATE before magi_set_problem and on a group handle.  Checkpoints carry the support in their tag: a
+ * checkpoint taken under one support is refused under another.
+ *   magi_get_theta_support   the support in force; either output may be NULL. */
+enum { MAGI_THETA_POSITIVE = 0, MAGI_THETA_LOWER = 1, MAGI_THETA_UPPER = 2, MAGI_THETA_REAL = 3 };
+int magi_set_theta_support(magi_handle* h, int P, const int* kind, const double* bound);
+int magi_get_theta_support(magi_handle* h, int P, int* kind, double* bound);
+
 /* unnormalized_log_prob (magi_v2.py:308-348) and its gradient (TF autodiff in the reference,
  * induced by magi_v2.py:360-364) for n_chains independent states.
  * X[n_chains][N][D], sig_pre[n_chains][D], th_pre[n_chains][P] -> logp[n_chains],

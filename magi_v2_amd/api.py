@@ -351,7 +351,8 @@ class MAGI_v2:
     def predict(self, num_results: int = 1000, num_burnin_steps: int = 1000, sigma_sqs_LB=None, verbose=False, *,
                 n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[int]] = None,
                 stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
-                family_chains: Optional[int] = None, summary: bool = False, keep_samples: bool = True, adapt_metric: bool = False):
+                family_chains: Optional[int] = None, summary: bool = False, keep_samples: bool = True, adapt_metric: bool = False,
+                theta_support=None):
         """magi_v2.py:286-425.  Returns the reference's results dictionary; with n_chains > 1 every
         sample array gains a leading chain axis.  ``family_chains``: in a job sharded over GPUs, the largest per-GPU share
         (shard.family_chains_for) -- every rank then samples with the same kernel family whatever its own share.
@@ -363,10 +364,14 @@ class MAGI_v2:
         averaging restarting after each window; ``results["metric"]`` = dict(inv_mass_X, inv_mass_sigma_pre, inv_mass_theta_pre: the
         metric the results were drawn with, leading chain axis as the samples; windows: per adapted window start, stop, the step sizes
         after it and the number of chains it left unchanged).
+        ``theta_support`` (the reference constrains every ODE parameter to be positive, and None keeps that): one entry per parameter out
+        of "positive", "real", ("lower", lo), ("upper", hi) -- theta = softplus(pre), pre, lo + softplus(pre), hi - softplus(pre).  The
+        sampler works on ``pre`` as before; ``thetas_samps`` and ``summary["thetas"]`` are on the natural scale under the supports,
+        ``sample_results[2]`` stays ``pre``, and ``results["theta_support"]`` echoes the normalised specification.
         Many datasets on one GPU: ``predict_many``."""
         if not keep_samples and not summary:
             raise ValueError("keep_samples=False needs summary=True: the call would return nothing of the posterior")
-        sigma_sqs_LB, sig_pre0, th_pre0 = self._predict_prepare(sigma_sqs_LB, family_chains)
+        sigma_sqs_LB, sig_pre0, th_pre0 = self._predict_prepare(sigma_sqs_LB, family_chains, theta_support)
         eng = self.engine
         if seed is None:                 # the reference calls sample_chain unseeded (magi_v2.py:389-395)
             seed = _fresh_seed()
@@ -407,8 +412,9 @@ class MAGI_v2:
             raise RuntimeError("posterior_summary summarises the samples of the last predict: run predict first")
         return self.engine.sampler_summary(probs=probs, max_lag=max_lag)
 
-    def _predict_prepare(self, sigma_sqs_LB, family_chains=None):
-        """predict's set-up up to the sampler: matrices on the device, the problem set; returns (sigma_sqs_LB, sig_pre0, th_pre0)."""
+    def _predict_prepare(self, sigma_sqs_LB, family_chains=None, theta_support=None):
+        """predict's set-up up to the sampler: matrices on the device, the problem and the parameters' supports set; returns
+        (sigma_sqs_LB, sig_pre0, th_pre0)."""
         assert ~np.any(np.isnan(self.Xhat_init)), "Please make sure Xhat_init does not have NaNs."
         assert ~np.any(np.isnan(self.sigma_sqs_init)), "Please make sure sigma_sqs_init does not have NaNs."
         assert ~np.any(np.isnan(self.thetas_init)), "Please make sure thetas_init does not have NaNs."
@@ -426,19 +432,28 @@ class MAGI_v2:
                         np.asarray(self.y_tau_ds_observed), float(self.beta), sigma_sqs_LB, self.drift)
         sig_pre0, th_pre0 = host.softplus_inverse_inits(np.asarray(self.sigma_sqs_init, dtype=np.float64),
                                                         np.asarray(self.thetas_init, dtype=np.float64), sigma_sqs_LB)
+        self._theta_support = None                   # (set_problem has reset the engine's supports to all-positive)
+        if theta_support is not None:
+            self._theta_support = host.theta_support(theta_support, self.drift.P)
+            eng.set_theta_support(theta_support)
+            th_pre0 = host.theta_pre_inits(np.asarray(self.thetas_init, dtype=np.float64), *self._theta_support)
         return sigma_sqs_LB, sig_pre0, th_pre0
 
     def _predict_results(self, X_samps, sig_pre, th_pre, diag, sigma_sqs_LB, seed, n_chains, num_burnin_steps, minutes):
         """predict's results dictionary from the chains' samples [n_chains, results, ...] and diagnostics."""
         kept = X_samps is not None                   # (predict(keep_samples=False): no draw was downloaded)
         sig_samps, th_samps = host.transform_samples(sig_pre, th_pre, sigma_sqs_LB) if kept else (None, None)
+        support = getattr(self, "_theta_support", None)
+        if kept and support is not None:
+            th_samps = host.transform_thetas(th_pre, *support)
         sq = (lambda a: None if a is None else a[0]) if n_chains == 1 else (lambda a: a)
         B = num_burnin_steps
         kernel_results = {k: sq(getattr(diag, k)[:, B:]) for k in
                           ("step_size", "log_accept_ratio", "leapfrogs_taken", "tree_depth", "has_divergence",
                            "reach_max_depth", "is_accepted", "target_log_prob", "energy", "beta_temp")}
         kernel_results["seed"] = seed
-        return {"phi1s": self.phi1s, "phi2s": self.phi2s,
+        extra = {} if support is None else {"theta_support": host.theta_support_spec(*support)}
+        return {**extra, "phi1s": self.phi1s, "phi2s": self.phi2s,
                 "Xhat_init": self.Xhat_init,
                 "sigma_sqs_init": self.sigma_sqs_init,
                 "thetas_init": self.thetas_init,
@@ -530,30 +545,40 @@ def partition_for_groups(keys):
 def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_steps: int = 1000, sigma_sqs_LB=None, verbose=False, *,
                  n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[Sequence[int]]] = None,
                  stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
-                 summary: bool = False, keep_samples: bool = True):
+                 summary: bool = False, keep_samples: bool = True, theta_support=None):
     """``predict`` for several models (after their ``initial_fit``) at once.  Models of one library, device and problem shape are sampled
     as one problem group on their GPU -- one captured graph, one kernel pair per leapfrog slot for all their chains -- and the others by
     their own ``predict``.  ``sigma_sqs_LB``: None (each model's default) or one entry per model; ``chain_ids``: None (0 .. n_chains - 1
     for every model, as predict) or one id list per model.  Returns one results dictionary per model, in order: element k equals
     ``models[k].predict(<same arguments>, seed=<the seed used>)`` array for array, bit for bit; ``minutes_elapsed`` is the group's.
-    ``summary`` / ``keep_samples`` as in ``predict``: a grouped model's summary pools that model's chains alone."""
+    ``summary`` / ``keep_samples`` as in ``predict``: a grouped model's summary pools that model's chains alone.  ``theta_support``: None, one
+    specification for all models (entries "positive", "real", ("lower", lo), ("upper", hi), as in ``predict``) or one per model (each None
+    or such a specification); the members of one group may differ."""
     if not keep_samples and not summary:
         raise ValueError("keep_samples=False needs summary=True: the call would return nothing of the posterior")
     models = list(models)
     n = len(models)
     lbs = [None] * n if sigma_sqs_LB is None else list(sigma_sqs_LB)
     ids = [None] * n if chain_ids is None else [None if c is None else list(c) for c in chain_ids]
-    if len(lbs) != n or len(ids) != n:
-        raise ValueError("sigma_sqs_LB and chain_ids take one entry per model")
+    is_entry = lambda e: isinstance(e, str) or (isinstance(e, (tuple, list)) and len(e) == 2 and e[0] in ("lower", "upper"))
+    if theta_support is None:
+        sups = [None] * n
+    elif len(theta_support) > 0 and all(is_entry(e) for e in theta_support):       # one specification for all
+        sups = [list(theta_support)] * n
+    else:
+        sups = list(theta_support)
+    if len(lbs) != n or len(ids) != n or len(sups) != n:
+        raise ValueError("sigma_sqs_LB, chain_ids and per-model theta_support take one entry per model")
     if seed is None:
         seed = _fresh_seed()
     kw = dict(n_chains=n_chains, seed=seed, stale_cache=stale_cache, anneal=anneal, max_tree_depth=max_tree_depth, step_size=step_size)
-    prep = [m._predict_prepare(lb) for m, lb in zip(models, lbs)]
+    prep = [m._predict_prepare(lb, None, sp) for m, lb, sp in zip(models, lbs, sups)]
     out = [None] * n
     for grp in partition_for_groups([group_key(m, n_chains) for m in models]):
         if len(grp) == 1:
             k = grp[0]
-            out[k] = models[k].predict(num_results, num_burnin_steps, lbs[k], verbose, chain_ids=ids[k], summary=summary, keep_samples=keep_samples, **kw)
+            out[k] = models[k].predict(num_results, num_burnin_steps, lbs[k], verbose, chain_ids=ids[k], summary=summary, keep_samples=keep_samples,
+                                        theta_support=sups[k], **kw)
             continue
         g = MagiGroup([models[k].engine for k in grp])
         try:

@@ -324,6 +324,7 @@ void magi_destroy(magi_handle* h) {
     free_chains(h);
     free_matrices(h);
     free_dev(h->d_members);          // (a group's members are the caller's)
+    free_dev(h->dTsup);
     for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     if (h->ev_t0) (void)hipEventDestroy(h->ev_t0);
     if (h->ev_t1) (void)hipEventDestroy(h->ev_t1);
@@ -360,6 +361,7 @@ int magi_group_create(magi_handle* const* members, int n_members, magi_handle** 
     g->pb.Csym = g->pb.M = g->pb.Mt = g->pb.Ksym = g->pb.yobs = g->pb.tiles = nullptr;
     g->pb.tasks = g->pb.stasks = nullptr;
     g->pb.tgrid = nullptr;
+    g->pb.tsup = nullptr;                          // (every member brings its own supports)
     hipError_t e = hipMalloc(&g->d_members, sizeof(DevProblem) * n_members);
     if (e != hipSuccess) {
         magi_destroy(g);
@@ -550,6 +552,8 @@ int magi_set_problem(magi_handle* h, const double* mu, const double* N_ds, const
         pb.N_ds[d] = d < D ? N_ds[d] : 0.0;
         pb.LB[d] = d < D ? LB[d] : 0.0;
     }
+    for (int p = 0; p < MAGI_MAX_P; ++p) { h->th_kind[p] = MAGI_THETA_POSITIVE; h->th_bound[p] = 0.0; }      // (a new problem: every parameter positive)
+    pb.tsup = nullptr;
     h->have_problem = true;
     free_chains(h);          // dimp may have changed
     drop_graph(h);
@@ -583,6 +587,53 @@ int magi_set_times(magi_handle* h, const double* t, int n) {
     MAGI_HIP_CHECK(h, hipMemcpy(h->dTimes, pad.data(), np_ * sizeof(double), hipMemcpyHostToDevice));
     h->pb.tgrid = h->dTimes;
     h->times_N = n;
+    return MAGI_OK;
+}
+
+int magi_set_theta_support(magi_handle* h, int P, const int* kind, const double* bound) {
+    if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_set_theta_support");
+    if (!h->have_problem) return magi_fail(h, MAGI_E_STATE, "magi_set_theta_support: set the problem first (magi_set_problem resets the supports)");
+    if (P != h->pb.P) return magi_fail(h, MAGI_E_BADARG, "magi_set_theta_support: P = " + std::to_string(P) + ", the problem has " + std::to_string(h->pb.P) + " parameters");
+    int kd[MAGI_MAX_P] = {};
+    double bd[MAGI_MAX_P] = {};
+    double2 tab[MAGI_MAX_P];
+    bool plain = true;
+    for (int p = 0; p < MAGI_MAX_P; ++p) tab[p] = make_double2(1.0, 0.0);
+    for (int p = 0; kind && p < P; ++p) {
+        const int k = kind[p];
+        if (k != MAGI_THETA_POSITIVE && k != MAGI_THETA_LOWER && k != MAGI_THETA_UPPER && k != MAGI_THETA_REAL)
+            return magi_fail(h, MAGI_E_BADARG, "magi_set_theta_support: kind[" + std::to_string(p) + "] = " + std::to_string(k) + " is none of MAGI_THETA_*");
+        const bool bounded = k == MAGI_THETA_LOWER || k == MAGI_THETA_UPPER;
+        if (bounded && (!bound || !std::isfinite(bound[p])))
+            return magi_fail(h, MAGI_E_BADARG, "magi_set_theta_support: the bound of parameter " + std::to_string(p) + " is missing or not finite");
+        kd[p] = k;
+        bd[p] = bounded ? bound[p] : 0.0;
+        tab[p] = make_double2(k == MAGI_THETA_REAL ? 0.0 : k == MAGI_THETA_UPPER ? -1.0 : 1.0, bd[p]);
+        plain = plain && k == MAGI_THETA_POSITIVE;
+    }
+    (void)hipSetDevice(h->device);
+    if (h->stream) MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // (nothing in flight reads the old table)
+    if (!plain) {
+        if (!h->dTsup) MAGI_HIP_CHECK(h, hipMalloc(&h->dTsup, sizeof(double2) * MAGI_MAX_P));
+        MAGI_HIP_CHECK(h, hipMemcpy(h->dTsup, tab, sizeof(tab), hipMemcpyHostToDevice));
+    }
+    h->sampler_ready = false;
+    drop_graph(h);                                                           // (the problem, pointer included, is a kernel argument of the captured graph)
+    for (int p = 0; p < MAGI_MAX_P; ++p) { h->th_kind[p] = kd[p]; h->th_bound[p] = bd[p]; }
+    h->pb.tsup = plain ? nullptr : h->dTsup;                                 // all-positive: no table, the kernels' default path
+    return MAGI_OK;
+}
+
+int magi_get_theta_support(magi_handle* h, int P, int* kind, double* bound) {
+    if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_get_theta_support");
+    if (!h->have_problem) return magi_fail(h, MAGI_E_STATE, "magi_get_theta_support: set the problem first");
+    if (P != h->pb.P) return magi_fail(h, MAGI_E_BADARG, "magi_get_theta_support: P = " + std::to_string(P) + ", the problem has " + std::to_string(h->pb.P) + " parameters");
+    for (int p = 0; p < P; ++p) {
+        if (kind) kind[p] = h->th_kind[p];
+        if (bound) bound[p] = h->th_bound[p];
+    }
     return MAGI_OK;
 }
 
@@ -963,7 +1014,7 @@ int magi_sampler_get_state(magi_handle* h, double* X, double* sig_pre, double* t
 // per-chain scalars of a checkpoint (magi_sampler_get_checkpoint / magi_sampler_set_checkpoint)
 enum { CKPT_K = 0, CKPT_DA_STEP, CKPT_STEP_SIZE, CKPT_ERR_SUM, CKPT_LOG_AVG, CKPT_LOG_SHRINK, CKPT_BETA_CACHE, CKPT_TOTAL_LF, CKPT_TAG, CKPT_COUNT };
 
-// What a checkpoint belongs to: the sampler configuration, the seed, the chain's Philox id and the state size, folded into 52 bits (exact in a
+// What a checkpoint belongs to: the sampler configuration, the seed, the chain's Philox id, the state size and the parameters' supports, folded into 52 bits (exact in a
 // double).  A resume promises the uninterrupted run bit for bit, which only holds under the same configuration: set_checkpoint compares.
 static double ckpt_tag(const magi_handle* h, long long chain_id) {
     unsigned long long x = 1469598103934665603ull;
@@ -972,6 +1023,8 @@ static double ckpt_tag(const magi_handle* h, long long chain_id) {
     const int ints[9] = {c.total, c.burnin, c.n_adapt, c.max_depth, c.mode, c.mode == MAGI_MODE_HMC ? c.hmc_L : 0, c.anneal, c.stale, h->pb.dimp};
     const double dbl[4] = {c.step_size, c.target_accept, c.max_energy_diff, c.min_temp};
     mix(ints, sizeof(ints)); mix(dbl, sizeof(dbl)); mix(&c.seed, sizeof(c.seed)); mix(&chain_id, sizeof(chain_id));
+    // (the parameters' supports, when any is set: without one the tag is what it was before supports existed)
+    if (h->pb.tsup) { mix(h->th_kind, sizeof(int) * h->pb.P); mix(h->th_bound, sizeof(double) * h->pb.P); }
     return (double)(x & ((1ull << 52) - 1));
 }
 
@@ -1013,7 +1066,7 @@ int magi_sampler_set_checkpoint(magi_handle* h, const double* scalars) {
             !std::isfinite(o[CKPT_LOG_SHRINK]) || !(o[CKPT_BETA_CACHE] > 0.0) || !(o[CKPT_BETA_CACHE] <= 1.4426950408889636))      // (the schedule starts at 1 / ln 2, magi_v2.py:833-835)
             return magi_fail(h, MAGI_E_BADARG, who + ": non-finite dual-averaging state, step size <= 0 or cached temperature outside (0, 1 / ln 2]");
         if (o[CKPT_TAG] != ckpt_tag(h, ctl[c].chain_id))
-            return magi_fail(h, MAGI_E_BADARG, who + " was taken under another sampler configuration, seed, chain id or problem size: a resume continues "
+            return magi_fail(h, MAGI_E_BADARG, who + " was taken under another sampler configuration, seed, chain id, problem size or parameter support: a resume continues "
                                                "the SAME run (magi_hip.h)");
         ctl[c].k = (int)o[CKPT_K]; ctl[c].da_step = (int)o[CKPT_DA_STEP]; ctl[c].da_step_size = o[CKPT_STEP_SIZE];
         ctl[c].da_error_sum = o[CKPT_ERR_SUM]; ctl[c].da_log_avg = o[CKPT_LOG_AVG]; ctl[c].da_log_shrink = o[CKPT_LOG_SHRINK];

@@ -127,6 +127,8 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
     auto ldb = [](const double* sbase, unsigned boff) { return *reinterpret_cast<const double*>(reinterpret_cast<const char*>(sbase) + boff); };
     double rows[4][P];
     int lcur = 0; double lhs = 0.0, leps = 0.0, qv0 = 0.0, qv1 = 0.0, pv0 = 0.0, pv1 = 0.0, parv = 0.0, msc = 1.0; bool lder = false;
+    const bool hsup = pb.tsup != nullptr;
+    double2 se = make_double2(1.0, 0.0);
     const int cg = wave * kpw + lj;                                    // this lane's own (chain cg of the group, parameter li)
     const bool mine = lj < kpw && cg < ngrp && li < P;
     if (kind != TK_FH) {
@@ -154,6 +156,7 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
             pv0 = vb[(size_t)V_P * pb.dimp]; pv1 = vb[(size_t)V_P1 * pb.dimp];
             parv = ch.par[(size_t)cc * PAR_COUNT + PAR_TH + li];
             msc = metric_scale(ch, pb.dimp, cc, pb.ND + D + li);         // (diagonal metric: s of this parameter entry)
+            se = ThetaSup::load(pb.tsup, li);                            // (supports: the entry's (sign, bound), in the same round)
         }
     }
     // which of the 16 chain columns take part in this slot (bit c): every lane fetches its own chain's flag now, not at the stores
@@ -233,9 +236,9 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
         if (lder && mine) {
             const double qv = lcur ? qv1 : qv0, pv = lcur ? pv1 : pv0;
             const double ex = m_exp(qv);
-            const double sg = ex / (1.0 + ex);                       // == par[PAR_SGT] of that state (compute_par_entry)
+            const double sg = ThetaSup::dtheta(hsup, se, ex / (1.0 + ex));      // == par[PAR_SGT] of that state (compute_par_entry)
             const double qnx = next_entry_pre(pv, qv, lhs, leps, theta_entry_grad(pb.beta_inv, tpp, sg), msc);
-            thp = m_log(1.0 + m_exp(qnx));                           // == par'[PAR_TH] (compute_par_entry)
+            thp = ThetaSup::theta(hsup, se, qnx, m_log(1.0 + m_exp(qnx)));      // == par'[PAR_TH] (compute_par_entry)
         }
         if (mine) th_s[cg * 8 + li] = thp;
     }

@@ -36,8 +36,10 @@ __device__ __forceinline__ void part_rows_sum(const double* part, int nwg, int r
     for (int k = 0; k < P; ++k) out[k] = wave_sum(out[k]);
 }
 
-// d L / d theta_pre_p from the global sum tp_p (magi_v2.py:318-323, 335-337 chained through softplus)
-__device__ __forceinline__ double theta_entry_grad(double beta_inv, double tpp, double sg) { return -0.5 * beta_inv * tpp * sg + (1.0 - sg); }
+// d L / d theta_pre_p from the global sum tp_p (magi_v2.py:318-323, 335-337 chained through the parameter's transform).
+// dth = d theta / d pre (PAR_SGT): sg for a positive or lower-bounded parameter, -sg for an upper-bounded one, 1 for a real one; the
+// log-Jacobian's derivative is 1 - |dth| for all of them (ThetaSup, magi_internal.h), and |sg| is sg bit for bit.
+__device__ __forceinline__ double theta_entry_grad(double beta_inv, double tpp, double dth) { return -0.5 * beta_inv * tpp * dth + (1.0 - fabs(dth)); }
 // position of a parameter entry after completing this leaf's momentum step and taking the next half step
 // (`s`: the entry's metric scale, 1 under the identity metric -- the momentum is the whitened one, DevChains::scale)
 __device__ __forceinline__ double next_entry_pre(double ph, double q, double hs, double eps, double gj, double s) {

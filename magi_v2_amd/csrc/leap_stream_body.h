@@ -84,6 +84,8 @@
             const int e = pb.ND + D + min(lane, P - 1);
             const double qv = (vb + (size_t)(V_Q + lp->cur) * pb.dimp)[e], pv = (vb + (size_t)(V_P + lp->cur) * pb.dimp)[e];
             const double msc = metric_scale(ch, pb.dimp, cc, e);          // (diagonal metric: s of this parameter entry)
+            const bool hsup = pb.tsup != nullptr;                         // (supports: the entry's (sign, bound), in the same round of loads)
+            const double2 se = ThetaSup::load(pb.tsup, min(lane, P - 1));
             double rows[P];
             part_rows_sum<P>(part, ch.n_wg, PK_TP, lane, rows);
             double tpp = 0.0;
@@ -91,9 +93,9 @@
             for (int k = 0; k < P; ++k) if (lane == k) tpp = rows[k];
             if (lane < P) {
                 const double ex = m_exp(qv);
-                const double sg = ex / (1.0 + ex);                       // == par[PAR_SGT] of that state (compute_par_entry)
+                const double sg = ThetaSup::dtheta(hsup, se, ex / (1.0 + ex));      // == par[PAR_SGT] of that state (compute_par_entry)
                 const double qnx = next_entry_pre(pv, qv, lp->hs, lp->eps, theta_entry_grad(pb.beta_inv, tpp, sg), msc);
-                thp = m_log(1.0 + m_exp(qnx));                           // == par'[PAR_TH] (compute_par_entry)
+                thp = ThetaSup::theta(hsup, se, qnx, m_log(1.0 + m_exp(qnx)));      // == par'[PAR_TH] (compute_par_entry)
             }
         } else if (lane < P) {
             thp = ch.par[(size_t)cc * PAR_COUNT + PAR_TH + lane];

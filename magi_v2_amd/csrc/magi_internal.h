@@ -73,6 +73,25 @@ struct DevProblem {
     int bandf;     // -1 dense; else half-width 3b of the fused operators (products of band-b matrices)
     const double* tgrid;   // [Np] times of the grid points (magi_set_times), padded with the last one; read by the kernels of a library whose
                            // drift uses t (DriftT<>::TDEP, point_time below) and by no other; nullptr until they are set
+    const double2* tsup;   // [MAGI_MAX_P] support of every parameter (magi_set_theta_support; ThetaSup below): (sign, bound); nullptr: every
+                           // parameter is positive, theta = softplus(pre) -- the kernels then run the instructions they ran without supports
+};
+
+// Support of one parameter entry, as a table entry (x, y) = (sign, bound):
+//   sign +1  theta = bound + softplus(pre)    (positive: bound 0; lower)      d theta / d pre =  sg
+//   sign -1  theta = bound - softplus(pre)    (upper)                         d theta / d pre = -sg
+//   sign  0  theta = pre                      (real)                          d theta / d pre =  1
+// with sg = e^pre / (1 + e^pre).  The log-Jacobian term is pre - softplus(pre) for the bounded kinds and 0 for a real one, and its derivative
+// is 1 - |d theta / d pre| for all of them (1 - sg, and 1 - 1 = 0): whoever holds d theta / d pre needs no second table look-up.
+// `sup` is null (wave-uniform) when no support is set: the value is then formed by the expression it always was.
+struct ThetaSup {
+    static __device__ __forceinline__ double theta(bool has, double2 se, double pre, double sp) {
+        return has ? (se.x == 0.0 ? pre : se.y + se.x * sp) : sp;
+    }
+    static __device__ __forceinline__ double dtheta(bool has, double2 se, double sg) { return has ? (se.x == 0.0 ? 1.0 : se.x * sg) : sg; }
+    static __device__ __forceinline__ double logjac(bool has, double2 se, double pre, double sp) { return (has && se.x == 0.0) ? 0.0 : pre - sp; }
+    // entry p of the table; (1, 0) without one.  p is clamped by the caller.
+    static __device__ __forceinline__ double2 load(const double2* sup, int p) { return sup ? sup[p] : make_double2(1.0, 0.0); }
 };
 
 // Member m of a problem group's device table (magi_group_create; leap.hip: k_stream_group).  The index is wave-uniform and the table
@@ -381,15 +400,18 @@ __device__ inline void compute_par_entry(const DevProblem& pb, int j, double pre
         par[PAR_LJS + j] = pre - sp;
         if (with_log2pis) par[PAR_LOG2PIS + j] = m_log(2.0 * 3.141592653589793 * s2);      // (leap_reduce evaluates it at the consumer)
     } else {
+        // PAR_SGT holds d theta / d pre under the parameter's support (ThetaSup above; sg itself without a table)
         const int p = j - pb.D;
-        par[PAR_TH + p] = sp;
-        par[PAR_SGT + p] = sg;
-        par[PAR_LJT + p] = pre - sp;
+        const bool has = pb.tsup != nullptr;                       // (wave-uniform)
+        const double2 se = ThetaSup::load(pb.tsup, min(p, MAGI_MAX_P - 1));
+        par[PAR_TH + p] = ThetaSup::theta(has, se, pre, sp);
+        par[PAR_SGT + p] = ThetaSup::dtheta(has, se, sg);
+        par[PAR_LJT + p] = ThetaSup::logjac(has, se, pre, sp);
     }
 }
 
 // ------------------------------------------------------------------------------------------
-// Drifts.  x[] = state at one grid point, th[] = softplus'ed parameters.
+// Drifts.  x[] = state at one grid point, th[] = the parameters on their natural scale (softplus'ed; ThetaSup under a support).
 // A library built with -DMAGI_USER_DRIFT_HEADER="<file>" carries ONE drift traced from the caller's f_vec
 // (magi_v2_amd/drift.py, jit.py) and instantiates the sampler's kernels for it alone.
 // ------------------------------------------------------------------------------------------
@@ -885,10 +907,10 @@ __device__ inline FinalizeOut finalize_gradient(const DevProblem& pb, double* vb
             g[ND + j] = -0.5 * dsig * sg + (1.0 - sg);
         } else if (j < D + P) {
             const int p = j - D;
-            const double sg = par[PAR_SGT + p];
+            const double sg = par[PAR_SGT + p];                     // d theta / d pre; the log-Jacobian's derivative is 1 - |sg| (ThetaSup)
             const double tpp = select_lane<K>(red, 2 + MAGI_MAX_D, MAGI_MAX_P, p);
             lj = par[PAR_LJT + p];
-            g[ND + D + p] = -0.5 * pb.beta_inv * tpp * sg + (1.0 - sg);
+            g[ND + D + p] = -0.5 * pb.beta_inv * tpp * sg + (1.0 - fabs(sg));
         }
         t3 = wave_sum(t3);
         t4 = wave_sum(t4);
@@ -961,6 +983,11 @@ struct magi_handle {
     double* dTimes = nullptr;        // pb.tgrid: the times of the grid points (magi_set_times), [times_cap >= pb.Np]
     int times_N = 0;                 // the N they were set for (0: not set; forgotten when the matrices change to another N)
     size_t times_cap = 0;
+    // supports of the parameters (magi_set_theta_support): the host copy, and the device table pb.tsup points at while any parameter is
+    // not positive (allocated once, MAGI_MAX_P entries, freed with the handle: a group's device table may hold the pointer)
+    int th_kind[MAGI_MAX_P] = {};
+    double th_bound[MAGI_MAX_P] = {};
+    double2* dTsup = nullptr;
     size_t mat_elems = 0;
     // dense C^-1, m, K^-1 ([D][N][N], unmasked) as built or uploaded: authoritative until the caller uploads others; packed
     // (band mask, symmetrised / transposed copies, single-phase operator blocks) by magi_pack_matrices

@@ -1,7 +1,8 @@
 """Classic MAGI benchmark systems written the way a user of the reference writes ``f_vec`` (numpy in place of
 tf.*): used by the tests of the generic-drift path and pre-built by ``__graft_entry__.build()``.  ``EXAMPLES`` ignore their first
 argument; ``TIME_EXAMPLES`` are forced systems that use it; ``DOMAIN_EXAMPLES`` are defined on part of the state space only (a square root, a logarithm);
-``EDGE_EXAMPLES`` sit at the documented shape limits (D = 1, 7, 8; P = 8) and at the edges of what the tracer prints and separates."""
+``EDGE_EXAMPLES`` sit at the documented shape limits (D = 1, 7, 8; P = 8) and at the edges of what the tracer prints and separates;
+``SIGNED_EXAMPLES`` have parameters that are negative at the truth (supports of theta: ``predict(theta_support=...)``)."""
 import numpy as np
 
 
@@ -147,6 +148,17 @@ EDGE_EXAMPLES = {"logistic1": (logistic_1, 1, 2), "chain8": (chain_8, 8, 8), "ca
                  "mixed3": (mixed_3, 3, 6)}
 # traced on the CPU only: no library is built for it
 EDGE_TRACE_ONLY = {"five_term": (five_terms, 2, 5)}
+
+
+def linear_oscillator(t, X, thetas):
+    """Damped linear oscillator: x' = a y,  y' = b x + c y;  theta = (a, b, c).  A restoring force (b < 0) and a damping (c < 0): parameters
+    the reference's positivity rule cannot reach -- sampled with ``predict(theta_support=["positive", "real", "real"])``."""
+    x, y = X[:, 0:1], X[:, 1:2]
+    return np.concatenate([thetas[0] * y, thetas[1] * x + thetas[2] * y], axis=1)
+
+
+# systems with parameters of either sign (tests/test_support_*.py)
+SIGNED_EXAMPLES = {"linear_oscillator": (linear_oscillator, 2, 3)}
 
 
 def rk4(f_vec, x0, thetas, T, n, substeps=20, grid=None):

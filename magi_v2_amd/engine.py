@@ -12,6 +12,8 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from .host import theta_support
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmagi_hip.so")
 
@@ -57,6 +59,8 @@ _SYMBOLS = {
     "magi_dense_apply": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp]),
     "magi_set_problem": (C.c_int, [C.c_void_p, _dp, _dp, _lp, _dp, C.c_int64, C.c_double, _dp, C.c_int, C.c_int]),
     "magi_set_times": (C.c_int, [C.c_void_p, _dp, C.c_int]),
+    "magi_set_theta_support": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp]),
+    "magi_get_theta_support": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp]),
     "magi_logpost_grad": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "magi_logpost_grad_fused": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "magi_sampler_cfg_default": (None, [C.POINTER(SamplerCfg)]),
@@ -288,7 +292,8 @@ class MagiEngine:
     def sampler_summary(self, chains=None, probs=DEFAULT_PROBS, max_lag=0, member=None):
         """Summaries of the finished sampler run, computed on the device-resident samples (magi_sampler_summarize): no draw is copied to the
         host.  Returns dict(X, sigma_sqs, thetas, probs, n_nonfinite); X, sigma_sqs (= softplus(sig_pre) + LB) and thetas
-        (= softplus(th_pre)) each a dict as ``summarize`` returns, of shapes [N, D], [D] and [P].  ``chains``: None (all) or a contiguous
+        (= softplus(th_pre); under ``set_theta_support`` the natural scale of each parameter's support, a group member's own) each a dict as
+        ``summarize`` returns, of shapes [N, D], [D] and [P].  ``chains``: None (all) or a contiguous
         run of chain indices (a range, or (first, count) as a slice) pooled into one summary.  ``member`` (a MagiGroup): the chains of
         that member -- a group's members sample different posteriors and are never pooled."""
         if member is not None:
@@ -438,6 +443,24 @@ class MagiEngine:
                                                obs_idx.shape[0], float(beta), _ptr(LB), drift_id, P))
         self.P = P
         self._problem_drift = drift
+
+    def set_theta_support(self, spec):
+        """The support of every ODE parameter (magi_set_theta_support), after ``set_problem`` -- which resets it to all-positive: None, or
+        P entries out of "positive", "real", ("lower", lo), ("upper", hi) (host.theta_support).  It governs ``logpost_grad``, the next
+        ``sampler_init`` and the theta block of ``sampler_summary``; theta_pre stays theta_pre everywhere."""
+        if self.P is None:
+            raise MagiHipError(-5, "set_theta_support: set the problem first (magi_set_problem)")
+        kinds, bounds = theta_support(spec, self.P)
+        kinds = np.ascontiguousarray(kinds, dtype=np.int32)
+        self._check(self._lib.magi_set_theta_support(self._h, int(self.P), None if spec is None else kinds.ctypes.data_as(_ip), _ptr(bounds)))
+
+    def theta_support(self):
+        """The supports in force as (kinds int32[P], bounds float64[P]) (magi_get_theta_support; host.theta_support_spec names them)."""
+        if self.P is None:
+            raise MagiHipError(-5, "theta_support: set the problem first (magi_set_problem)")
+        kinds, bounds = np.zeros(self.P, dtype=np.int32), np.zeros(self.P)
+        self._check(self._lib.magi_get_theta_support(self._h, int(self.P), kinds.ctypes.data_as(_ip), _ptr(bounds)))
+        return kinds, bounds
 
     def _states(self, X, sig_pre, th_pre):
         X = _f64(X)

@@ -107,6 +107,74 @@ def transform_samples(sig_pre, th_pre, LB):
     return np.log(np.exp(sig_pre) + 1.0) + LB, np.log(np.exp(th_pre) + 1.0)
 
 
+# supports of the ODE parameters (include/magi_hip.h: magi_set_theta_support).  The codes are the header's MAGI_THETA_*.
+THETA_POSITIVE, THETA_LOWER, THETA_UPPER, THETA_REAL = 0, 1, 2, 3
+
+
+def theta_support(spec, P: int):
+    """Normalises a support specification for P parameters into (kinds int32[P], bounds float64[P]).  ``spec`` is None (every
+    parameter positive: the reference's rule, magi_v2.py:303-306, 319) or P entries out of "positive", "real", ("lower", lo),
+    ("upper", hi) with finite bounds; anything else raises ValueError.  The bound of a positive or real entry is 0."""
+    P = int(P)
+    kinds, bounds = np.zeros(P, dtype=np.int32), np.zeros(P, dtype=np.float64)
+    if spec is None:
+        return kinds, bounds
+    if isinstance(spec, (str, bytes)) or not hasattr(spec, "__len__"):
+        raise ValueError(f"theta_support: expected None or a sequence of {P} entries, got {spec!r}")
+    if len(spec) != P:
+        raise ValueError(f"theta_support: {len(spec)} entries for {P} parameters")
+    for p, e in enumerate(spec):
+        if isinstance(e, str):
+            if e == "positive":
+                continue
+            if e == "real":
+                kinds[p] = THETA_REAL
+                continue
+            raise ValueError(f"theta_support[{p}]: {e!r} is none of 'positive', 'real', ('lower', lo), ('upper', hi)")
+        if isinstance(e, (tuple, list)) and len(e) == 2 and e[0] in ("lower", "upper"):
+            try:
+                b = float(e[1])
+            except (TypeError, ValueError):
+                raise ValueError(f"theta_support[{p}]: the bound {e[1]!r} is not a number") from None
+            if not np.isfinite(b):
+                raise ValueError(f"theta_support[{p}]: the bound {b} is not finite")
+            kinds[p] = THETA_LOWER if e[0] == "lower" else THETA_UPPER
+            bounds[p] = b
+            continue
+        raise ValueError(f"theta_support[{p}]: {e!r} is none of 'positive', 'real', ('lower', lo), ('upper', hi)")
+    return kinds, bounds
+
+
+def theta_support_spec(kinds, bounds):
+    """The normalised specification (a list of "positive", "real", ("lower", lo), ("upper", hi)) of (kinds, bounds)."""
+    names = {THETA_POSITIVE: "positive", THETA_REAL: "real"}
+    return [names[int(k)] if int(k) in names else ("lower" if int(k) == THETA_LOWER else "upper", float(b)) for k, b in zip(kinds, bounds)]
+
+
+def theta_pre_inits(thetas_init, kinds, bounds):
+    """theta_pre of the starting values under the supports: theta itself for a real parameter, the softplus inverse of the distance to
+    the bound for a bounded one -- with the reference's -5.0 fallback (magi_v2.py:374-380) when the value lies on the wrong side of the
+    bound -- and for a positive one exactly what softplus_inverse_inits gives."""
+    th = np.asarray(thetas_init, dtype=np.float64)
+    kinds, bounds = np.asarray(kinds), np.asarray(bounds, dtype=np.float64)
+    # the distance to the bound (theta itself for a positive parameter: th - 0.0 is th bit for bit)
+    dist = np.where(kinds == THETA_UPPER, bounds - th, np.where(kinds == THETA_LOWER, th - bounds, th))
+    ok = dist > 0.0
+    with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+        pre = np.where(ok, np.log(np.exp(np.where(ok, dist, 1.0)) - 1.0), -5.0)
+    return np.where(kinds == THETA_REAL, th, pre)
+
+
+def transform_thetas(th_pre, kinds, bounds):
+    """theta on the natural scale from theta_pre[..., P] under the supports (for a positive parameter: transform_samples)."""
+    th_pre = np.asarray(th_pre, dtype=np.float64)
+    kinds, bounds = np.asarray(kinds), np.asarray(bounds, dtype=np.float64)
+    with np.errstate(over="ignore"):
+        sp = np.log(np.exp(th_pre) + 1.0)
+    out = np.where(kinds == THETA_LOWER, bounds + sp, np.where(kinds == THETA_UPPER, bounds - sp, sp))
+    return np.where(kinds == THETA_REAL, th_pre, out)
+
+
 def observation_bookkeeping(X_obs: np.ndarray, X_grid: np.ndarray):
     """magi_v2.py:53, 89, 96-100: N_ds, beta, flat indices and values of the non-NaN grid entries."""
     N_ds = (~np.isnan(X_obs)).sum(axis=0)
