@@ -163,6 +163,34 @@ enum { MAGI_THETA_POSITIVE = 0, MAGI_THETA_LOWER = 1, MAGI_THETA_UPPER = 2, MAGI
 int magi_set_theta_support(magi_handle* h, int P, const int* kind, const double* bound);
 int magi_get_theta_support(magi_handle* h, int P, int* kind, double* bound);
 
+/* Priors on the parameter entries and known noise variances (opt-in; the reference has a flat prior on every sigma^2 and theta, and that
+ * stays the default).  The n = D + P entries are ordered as in the parameter block: sigma^2_0 .. sigma^2_{D-1}, then theta_0 .. theta_{P-1}.
+ * A prior acts on the NATURAL scale v of its entry -- sigma^2 = softplus(pre) + LB, theta under its support -- with the unnormalised log
+ * density
+ *   MAGI_PRIOR_FLAT       0
+ *   MAGI_PRIOR_NORMAL     a = mean m, b = sd s > 0         -(v - m)^2 / (2 s^2)
+ *   MAGI_PRIOR_LOGNORMAL  a = m, b = s > 0                 -log v - (log v - m)^2 / (2 s^2)
+ *   MAGI_PRIOR_GAMMA      a = shape k > 0, b = rate r > 0  (k - 1) log v - r v
+ *   MAGI_PRIOR_INVGAMMA   a = shape > 0, b = scale > 0     -(a + 1) log v - b / v
+ *   MAGI_PRIOR_FIXED      a = value c > 0 (sigma^2 entries only; b ignored, reported as 0)
+ * The log prior joins the log-Jacobian terms of the target: beta_temp (-(1/2)((1/beta)(t1 + t2) + (t3 + t4)) + logJ + sum log p) -- tempered
+ * like the rest, not divided by the prior temperature beta; the gradient with respect to pre gains (d log p / dv)(dv / dpre).
+ * FIXED: sigma^2_j = c whatever pre_j is (t3, t4 use c and give that entry no gradient); the entry's log-Jacobian term is replaced by
+ * -pre_j^2 / 2, so pre_j stays in the state as an independent standard-normal coordinate and the marginal of everything else is the posterior
+ * with sigma^2_j = c; the sigma^2 block of magi_sampler_summarize reports c.
+ * kind = NULL: back to all-FLAT.  A handle whose priors were never set, or set to all-FLAT, computes bit for bit what it computed without
+ * this call (the kernels test one pointer).  The priors belong to the problem: magi_set_problem resets them, and the call comes after
+ * magi_set_theta_support where both are used; it governs magi_logpost_grad*, the next magi_sampler_init (it invalidates the sampler state and
+ * the captured graph), and the handle as a member of a group (each member brings its own).
+ * Errors, each leaving the handle as it was: MAGI_E_BADARG for n other than D + P, a kind out of range, a missing or non-finite parameter, a
+ * parameter out of its range, FIXED on a theta entry, LOGNORMAL / GAMMA / INVGAMMA on a theta entry whose support is not inside (0, inf)
+ * (POSITIVE, or LOWER with bound >= 0; magi_set_theta_support in turn refuses a support an installed prior does not allow); MAGI_E_STATE
+ * before magi_set_problem and on a group handle.  Checkpoints carry the priors in their tag when any is set.
+ *   magi_get_prior   the priors in force; any output may be NULL. */
+enum { MAGI_PRIOR_FLAT = 0, MAGI_PRIOR_NORMAL = 1, MAGI_PRIOR_LOGNORMAL = 2, MAGI_PRIOR_GAMMA = 3, MAGI_PRIOR_INVGAMMA = 4, MAGI_PRIOR_FIXED = 5 };
+int magi_set_prior(magi_handle* h, int n /* D + P */, const int* kind, const double* a, const double* b);
+int magi_get_prior(magi_handle* h, int n /* D + P */, int* kind, double* a, double* b);
+
 /* unnormalized_log_prob (magi_v2.py:308-348) and its gradient (TF autodiff in the reference,
  * induced by magi_v2.py:360-364) for n_chains independent states.
  * X[n_chains][N][D], sig_pre[n_chains][D], th_pre[n_chains][P] -> logp[n_chains],

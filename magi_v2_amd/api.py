@@ -352,7 +352,7 @@ class MAGI_v2:
                 n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[int]] = None,
                 stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
                 family_chains: Optional[int] = None, summary: bool = False, keep_samples: bool = True, adapt_metric: bool = False,
-                theta_support=None):
+                theta_support=None, theta_prior=None, sigma_sq_prior=None):
         """magi_v2.py:286-425.  Returns the reference's results dictionary; with n_chains > 1 every
         sample array gains a leading chain axis.  ``family_chains``: in a job sharded over GPUs, the largest per-GPU share
         (shard.family_chains_for) -- every rank then samples with the same kernel family whatever its own share.
@@ -368,10 +368,16 @@ class MAGI_v2:
         of "positive", "real", ("lower", lo), ("upper", hi) -- theta = softplus(pre), pre, lo + softplus(pre), hi - softplus(pre).  The
         sampler works on ``pre`` as before; ``thetas_samps`` and ``summary["thetas"]`` are on the natural scale under the supports,
         ``sample_results[2]`` stays ``pre``, and ``results["theta_support"]`` echoes the normalised specification.
+        ``theta_prior`` / ``sigma_sq_prior`` (the reference has a flat prior on every parameter and noise variance, and None keeps that):
+        one entry per parameter / component out of None or "flat", ("normal", m, s), ("lognormal", m, s), ("gamma", k, r),
+        ("invgamma", a, b) -- unnormalised densities on the natural scale (theta under its support, sigma^2), tempered with the posterior --
+        and for a noise variance also ("fixed", c): that sigma^2 is the known constant c, ``sigma_sqs_samps`` and the summaries report c, and
+        its ``pre`` coordinate (started at 0) is an independent standard normal.  lognormal, gamma and invgamma on a parameter need a support
+        inside (0, inf).  ``results["theta_prior"]`` / ``results["sigma_sq_prior"]`` echo the normalised specifications when given.
         Many datasets on one GPU: ``predict_many``."""
         if not keep_samples and not summary:
             raise ValueError("keep_samples=False needs summary=True: the call would return nothing of the posterior")
-        sigma_sqs_LB, sig_pre0, th_pre0 = self._predict_prepare(sigma_sqs_LB, family_chains, theta_support)
+        sigma_sqs_LB, sig_pre0, th_pre0 = self._predict_prepare(sigma_sqs_LB, family_chains, theta_support, theta_prior, sigma_sq_prior)
         eng = self.engine
         if seed is None:                 # the reference calls sample_chain unseeded (magi_v2.py:389-395)
             seed = _fresh_seed()
@@ -412,9 +418,9 @@ class MAGI_v2:
             raise RuntimeError("posterior_summary summarises the samples of the last predict: run predict first")
         return self.engine.sampler_summary(probs=probs, max_lag=max_lag)
 
-    def _predict_prepare(self, sigma_sqs_LB, family_chains=None, theta_support=None):
-        """predict's set-up up to the sampler: matrices on the device, the problem and the parameters' supports set; returns
-        (sigma_sqs_LB, sig_pre0, th_pre0)."""
+    def _predict_prepare(self, sigma_sqs_LB, family_chains=None, theta_support=None, theta_prior=None, sigma_sq_prior=None):
+        """predict's set-up up to the sampler: matrices on the device, the problem, the parameters' supports and then the priors set;
+        returns (sigma_sqs_LB, sig_pre0, th_pre0)."""
         assert ~np.any(np.isnan(self.Xhat_init)), "Please make sure Xhat_init does not have NaNs."
         assert ~np.any(np.isnan(self.sigma_sqs_init)), "Please make sure sigma_sqs_init does not have NaNs."
         assert ~np.any(np.isnan(self.thetas_init)), "Please make sure thetas_init does not have NaNs."
@@ -437,12 +443,21 @@ class MAGI_v2:
             self._theta_support = host.theta_support(theta_support, self.drift.P)
             eng.set_theta_support(theta_support)
             th_pre0 = host.theta_pre_inits(np.asarray(self.thetas_init, dtype=np.float64), *self._theta_support)
+        self._theta_prior = self._sigma_sq_prior = None          # (set_problem has reset the engine's priors to flat)
+        if theta_prior is not None or sigma_sq_prior is not None:
+            if theta_prior is not None:
+                self._theta_prior = host.prior_spec(theta_prior, self.drift.P, "theta", self._theta_support or host.theta_support(None, self.drift.P))
+            if sigma_sq_prior is not None:
+                self._sigma_sq_prior = host.prior_spec(sigma_sq_prior, len(sig_pre0), "sigma_sq")
+                sig_pre0 = np.where(self._sigma_sq_prior[0] == host.PRIOR_FIXED, 0.0, sig_pre0)      # (a fixed variance: pre ~ N(0, 1), started at 0)
+            eng.set_prior(sigma_sq_prior, theta_prior)
         return sigma_sqs_LB, sig_pre0, th_pre0
 
     def _predict_results(self, X_samps, sig_pre, th_pre, diag, sigma_sqs_LB, seed, n_chains, num_burnin_steps, minutes):
         """predict's results dictionary from the chains' samples [n_chains, results, ...] and diagnostics."""
         kept = X_samps is not None                   # (predict(keep_samples=False): no draw was downloaded)
-        sig_samps, th_samps = host.transform_samples(sig_pre, th_pre, sigma_sqs_LB) if kept else (None, None)
+        sig_prior, th_prior = getattr(self, "_sigma_sq_prior", None), getattr(self, "_theta_prior", None)
+        sig_samps, th_samps = host.transform_samples(sig_pre, th_pre, sigma_sqs_LB, sig_prior) if kept else (None, None)
         support = getattr(self, "_theta_support", None)
         if kept and support is not None:
             th_samps = host.transform_thetas(th_pre, *support)
@@ -453,6 +468,10 @@ class MAGI_v2:
                            "reach_max_depth", "is_accepted", "target_log_prob", "energy", "beta_temp")}
         kernel_results["seed"] = seed
         extra = {} if support is None else {"theta_support": host.theta_support_spec(*support)}
+        if th_prior is not None:
+            extra["theta_prior"] = host.prior_spec_echo(*th_prior)
+        if sig_prior is not None:
+            extra["sigma_sq_prior"] = host.prior_spec_echo(*sig_prior)
         return {**extra, "phi1s": self.phi1s, "phi2s": self.phi2s,
                 "Xhat_init": self.Xhat_init,
                 "sigma_sqs_init": self.sigma_sqs_init,
@@ -545,7 +564,7 @@ def partition_for_groups(keys):
 def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_steps: int = 1000, sigma_sqs_LB=None, verbose=False, *,
                  n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[Sequence[int]]] = None,
                  stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
-                 summary: bool = False, keep_samples: bool = True, theta_support=None):
+                 summary: bool = False, keep_samples: bool = True, theta_support=None, theta_prior=None, sigma_sq_prior=None):
     """``predict`` for several models (after their ``initial_fit``) at once.  Models of one library, device and problem shape are sampled
     as one problem group on their GPU -- one captured graph, one kernel pair per leapfrog slot for all their chains -- and the others by
     their own ``predict``.  ``sigma_sqs_LB``: None (each model's default) or one entry per model; ``chain_ids``: None (0 .. n_chains - 1
@@ -553,7 +572,8 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
     ``models[k].predict(<same arguments>, seed=<the seed used>)`` array for array, bit for bit; ``minutes_elapsed`` is the group's.
     ``summary`` / ``keep_samples`` as in ``predict``: a grouped model's summary pools that model's chains alone.  ``theta_support``: None, one
     specification for all models (entries "positive", "real", ("lower", lo), ("upper", hi), as in ``predict``) or one per model (each None
-    or such a specification); the members of one group may differ."""
+    or such a specification); the members of one group may differ.  ``theta_prior`` / ``sigma_sq_prior``: likewise None, one specification
+    for all models (entries None, "flat", ("normal", m, s), ... as in ``predict``) or one per model."""
     if not keep_samples and not summary:
         raise ValueError("keep_samples=False needs summary=True: the call would return nothing of the posterior")
     models = list(models)
@@ -567,18 +587,28 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
         sups = [list(theta_support)] * n
     else:
         sups = list(theta_support)
-    if len(lbs) != n or len(ids) != n or len(sups) != n:
-        raise ValueError("sigma_sqs_LB, chain_ids and per-model theta_support take one entry per model")
+    def per_model(spec):
+        # one prior specification for all models: every entry is None, "flat" or a (name, numbers...) tuple; else one per model
+        is_prior = lambda e: e is None or (isinstance(e, str) and e == "flat") or (
+            isinstance(e, (tuple, list)) and len(e) >= 2 and e[0] in ("normal", "lognormal", "gamma", "invgamma", "fixed"))
+        if spec is None:
+            return [None] * n
+        if len(spec) > 0 and all(is_prior(e) for e in spec) and not all(e is None for e in spec):
+            return [list(spec)] * n
+        return list(spec)
+    tpri, spri = per_model(theta_prior), per_model(sigma_sq_prior)
+    if len(lbs) != n or len(ids) != n or len(sups) != n or len(tpri) != n or len(spri) != n:
+        raise ValueError("sigma_sqs_LB, chain_ids and per-model theta_support, theta_prior and sigma_sq_prior take one entry per model")
     if seed is None:
         seed = _fresh_seed()
     kw = dict(n_chains=n_chains, seed=seed, stale_cache=stale_cache, anneal=anneal, max_tree_depth=max_tree_depth, step_size=step_size)
-    prep = [m._predict_prepare(lb, None, sp) for m, lb, sp in zip(models, lbs, sups)]
+    prep = [m._predict_prepare(lb, None, sp, tp, sq) for m, lb, sp, tp, sq in zip(models, lbs, sups, tpri, spri)]
     out = [None] * n
     for grp in partition_for_groups([group_key(m, n_chains) for m in models]):
         if len(grp) == 1:
             k = grp[0]
             out[k] = models[k].predict(num_results, num_burnin_steps, lbs[k], verbose, chain_ids=ids[k], summary=summary, keep_samples=keep_samples,
-                                        theta_support=sups[k], **kw)
+                                        theta_support=sups[k], theta_prior=tpri[k], sigma_sq_prior=spri[k], **kw)
             continue
         g = MagiGroup([models[k].engine for k in grp])
         try:

@@ -325,6 +325,7 @@ void magi_destroy(magi_handle* h) {
     free_matrices(h);
     free_dev(h->d_members);          // (a group's members are the caller's)
     free_dev(h->dTsup);
+    free_dev(h->dPrior);
     for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     if (h->ev_t0) (void)hipEventDestroy(h->ev_t0);
     if (h->ev_t1) (void)hipEventDestroy(h->ev_t1);
@@ -362,6 +363,8 @@ int magi_group_create(magi_handle* const* members, int n_members, magi_handle** 
     g->pb.tasks = g->pb.stasks = nullptr;
     g->pb.tgrid = nullptr;
     g->pb.tsup = nullptr;                          // (every member brings its own supports)
+    g->pb.prior = nullptr;                         // (and its own priors)
+    g->pb.fixed_mask = 0;
     hipError_t e = hipMalloc(&g->d_members, sizeof(DevProblem) * n_members);
     if (e != hipSuccess) {
         magi_destroy(g);
@@ -554,6 +557,10 @@ int magi_set_problem(magi_handle* h, const double* mu, const double* N_ds, const
     }
     for (int p = 0; p < MAGI_MAX_P; ++p) { h->th_kind[p] = MAGI_THETA_POSITIVE; h->th_bound[p] = 0.0; }      // (a new problem: every parameter positive)
     pb.tsup = nullptr;
+    for (int j = 0; j < MAGI_MAX_D + MAGI_MAX_P; ++j) { h->pr_kind[j] = MAGI_PRIOR_FLAT; h->pr_a[j] = h->pr_b[j] = 0.0; }      // (and every prior flat)
+    pb.prior = nullptr;
+    pb.fixed_mask = 0;
+    for (int d = 0; d < MAGI_MAX_D; ++d) h->lb_orig[d] = pb.LB[d];
     h->have_problem = true;
     free_chains(h);          // dimp may have changed
     drop_graph(h);
@@ -590,6 +597,10 @@ int magi_set_times(magi_handle* h, const double* t, int n) {
     return MAGI_OK;
 }
 
+// priors whose density lives on (0, inf), and the supports that keep a parameter there
+static bool prior_needs_positive(int k) { return k == MAGI_PRIOR_LOGNORMAL || k == MAGI_PRIOR_GAMMA || k == MAGI_PRIOR_INVGAMMA; }
+static bool support_is_positive(int kind, double bound) { return kind == MAGI_THETA_POSITIVE || (kind == MAGI_THETA_LOWER && bound >= 0.0); }
+
 int magi_set_theta_support(magi_handle* h, int P, const int* kind, const double* bound) {
     if (!h) return MAGI_E_BADARG;
     if (h->group_n) return refuse_group(h, "magi_set_theta_support");
@@ -609,6 +620,9 @@ int magi_set_theta_support(magi_handle* h, int P, const int* kind, const double*
             return magi_fail(h, MAGI_E_BADARG, "magi_set_theta_support: the bound of parameter " + std::to_string(p) + " is missing or not finite");
         kd[p] = k;
         bd[p] = bounded ? bound[p] : 0.0;
+        if (prior_needs_positive(h->pr_kind[h->pb.D + p]) && !support_is_positive(k, bd[p]))
+            return magi_fail(h, MAGI_E_BADARG, "magi_set_theta_support: parameter " + std::to_string(p) + " has a lognormal, gamma or inverse-gamma prior (magi_set_prior), "
+                                               "which needs a support inside (0, inf): POSITIVE, or LOWER with a bound >= 0");
         tab[p] = make_double2(k == MAGI_THETA_REAL ? 0.0 : k == MAGI_THETA_UPPER ? -1.0 : 1.0, bd[p]);
         plain = plain && k == MAGI_THETA_POSITIVE;
     }
@@ -633,6 +647,70 @@ int magi_get_theta_support(magi_handle* h, int P, int* kind, double* bound) {
     for (int p = 0; p < P; ++p) {
         if (kind) kind[p] = h->th_kind[p];
         if (bound) bound[p] = h->th_bound[p];
+    }
+    return MAGI_OK;
+}
+
+int magi_set_prior(magi_handle* h, int n, const int* kind, const double* a, const double* b) {
+    if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_set_prior");
+    if (!h->have_problem) return magi_fail(h, MAGI_E_STATE, "magi_set_prior: set the problem first (magi_set_problem resets the priors)");
+    const int D = h->pb.D, P = h->pb.P;
+    if (n != D + P) return magi_fail(h, MAGI_E_BADARG, "magi_set_prior: n = " + std::to_string(n) + ", the problem has D + P = " + std::to_string(D + P) + " parameter entries");
+    constexpr int NT = MAGI_MAX_D + MAGI_MAX_P;
+    int kd[NT] = {};
+    double av[NT] = {}, bv[NT] = {};
+    double4 tab[NT];
+    bool plain = true;
+    for (int j = 0; j < NT; ++j) tab[j] = make_double4(0.0, 0.0, 0.0, 0.0);
+    for (int e = 0; kind && e < n; ++e) {
+        const int k = kind[e];
+        const std::string who = e < D ? "sigma^2 entry " + std::to_string(e) : "theta entry " + std::to_string(e - D);
+        if (k < MAGI_PRIOR_FLAT || k > MAGI_PRIOR_FIXED)
+            return magi_fail(h, MAGI_E_BADARG, "magi_set_prior: kind[" + std::to_string(e) + "] = " + std::to_string(k) + " is none of MAGI_PRIOR_*");
+        if (k == MAGI_PRIOR_FLAT) continue;
+        if (k == MAGI_PRIOR_FIXED && e >= D)
+            return magi_fail(h, MAGI_E_BADARG, "magi_set_prior: " + who + ": FIXED is for sigma^2 entries only (a constant in f_vec states a fixed theta)");
+        if (!a || !std::isfinite(a[e]) || (k != MAGI_PRIOR_FIXED && (!b || !std::isfinite(b[e]))))
+            return magi_fail(h, MAGI_E_BADARG, "magi_set_prior: " + who + ": a parameter is missing or not finite");
+        const bool a_pos = k == MAGI_PRIOR_GAMMA || k == MAGI_PRIOR_INVGAMMA || k == MAGI_PRIOR_FIXED;      // (shape, shape, value; a normal's or lognormal's m is free)
+        if ((a_pos && !(a[e] > 0.0)) || (k != MAGI_PRIOR_FIXED && !(b[e] > 0.0)))
+            return magi_fail(h, MAGI_E_BADARG, "magi_set_prior: " + who + ": sd, shape, rate, scale and a fixed value must be > 0");
+        if (e >= D && prior_needs_positive(k) && !support_is_positive(h->th_kind[e - D], h->th_bound[e - D]))
+            return magi_fail(h, MAGI_E_BADARG, "magi_set_prior: " + who + ": a lognormal, gamma or inverse-gamma prior needs a support inside (0, inf): POSITIVE, or LOWER with a "
+                                               "bound >= 0 (magi_set_theta_support comes first)");
+        kd[e] = k; av[e] = a[e]; bv[e] = k == MAGI_PRIOR_FIXED ? 0.0 : b[e];
+        const bool gauss = k == MAGI_PRIOR_NORMAL || k == MAGI_PRIOR_LOGNORMAL;
+        tab[e < D ? e : MAGI_MAX_D + (e - D)] = make_double4((double)k, av[e], bv[e], gauss ? 1.0 / (bv[e] * bv[e]) : 0.0);
+        plain = false;
+    }
+    (void)hipSetDevice(h->device);
+    if (h->stream) MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // (nothing in flight reads the old table)
+    if (!plain) {
+        if (!h->dPrior) MAGI_HIP_CHECK(h, hipMalloc(&h->dPrior, sizeof(double4) * NT));
+        MAGI_HIP_CHECK(h, hipMemcpy(h->dPrior, tab, sizeof(tab), hipMemcpyHostToDevice));
+    }
+    h->sampler_ready = false;
+    drop_graph(h);                                                           // (the problem, pointer included, is a kernel argument of the captured graph)
+    for (int j = 0; j < NT; ++j) { h->pr_kind[j] = kd[j]; h->pr_a[j] = av[j]; h->pr_b[j] = bv[j]; }
+    h->pb.prior = plain ? nullptr : h->dPrior;                               // all flat: no table, the kernels' default path
+    h->pb.fixed_mask = 0;                                                    // a fixed sigma^2_d: bit d, and its constant in place of LB[d]
+    for (int d = 0; d < D; ++d) {
+        h->pb.LB[d] = kd[d] == MAGI_PRIOR_FIXED ? av[d] : h->lb_orig[d];
+        if (kd[d] == MAGI_PRIOR_FIXED) h->pb.fixed_mask |= 1 << d;
+    }
+    return MAGI_OK;
+}
+
+int magi_get_prior(magi_handle* h, int n, int* kind, double* a, double* b) {
+    if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_get_prior");
+    if (!h->have_problem) return magi_fail(h, MAGI_E_STATE, "magi_get_prior: set the problem first");
+    if (n != h->pb.D + h->pb.P) return magi_fail(h, MAGI_E_BADARG, "magi_get_prior: n = " + std::to_string(n) + ", the problem has D + P = " + std::to_string(h->pb.D + h->pb.P) + " parameter entries");
+    for (int e = 0; e < n; ++e) {
+        if (kind) kind[e] = h->pr_kind[e];
+        if (a) a[e] = h->pr_a[e];
+        if (b) b[e] = h->pr_b[e];
     }
     return MAGI_OK;
 }
@@ -1025,6 +1103,8 @@ static double ckpt_tag(const magi_handle* h, long long chain_id) {
     mix(ints, sizeof(ints)); mix(dbl, sizeof(dbl)); mix(&c.seed, sizeof(c.seed)); mix(&chain_id, sizeof(chain_id));
     // (the parameters' supports, when any is set: without one the tag is what it was before supports existed)
     if (h->pb.tsup) { mix(h->th_kind, sizeof(int) * h->pb.P); mix(h->th_bound, sizeof(double) * h->pb.P); }
+    // (likewise the priors, when any is set)
+    if (h->pb.prior) { const int n = h->pb.D + h->pb.P; mix(h->pr_kind, sizeof(int) * n); mix(h->pr_a, sizeof(double) * n); mix(h->pr_b, sizeof(double) * n); }
     return (double)(x & ((1ull << 52) - 1));
 }
 
@@ -1066,7 +1146,7 @@ int magi_sampler_set_checkpoint(magi_handle* h, const double* scalars) {
             !std::isfinite(o[CKPT_LOG_SHRINK]) || !(o[CKPT_BETA_CACHE] > 0.0) || !(o[CKPT_BETA_CACHE] <= 1.4426950408889636))      // (the schedule starts at 1 / ln 2, magi_v2.py:833-835)
             return magi_fail(h, MAGI_E_BADARG, who + ": non-finite dual-averaging state, step size <= 0 or cached temperature outside (0, 1 / ln 2]");
         if (o[CKPT_TAG] != ckpt_tag(h, ctl[c].chain_id))
-            return magi_fail(h, MAGI_E_BADARG, who + " was taken under another sampler configuration, seed, chain id, problem size or parameter support: a resume continues "
+            return magi_fail(h, MAGI_E_BADARG, who + " was taken under another sampler configuration, seed, chain id, problem size, parameter support or prior: a resume continues "
                                                "the SAME run (magi_hip.h)");
         ctl[c].k = (int)o[CKPT_K]; ctl[c].da_step = (int)o[CKPT_DA_STEP]; ctl[c].da_step_size = o[CKPT_STEP_SIZE];
         ctl[c].da_error_sum = o[CKPT_ERR_SUM]; ctl[c].da_log_avg = o[CKPT_LOG_AVG]; ctl[c].da_log_shrink = o[CKPT_LOG_SHRINK];

@@ -237,7 +237,9 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
             const double qv = lcur ? qv1 : qv0, pv = lcur ? pv1 : pv0;
             const double ex = m_exp(qv);
             const double sg = ThetaSup::dtheta(hsup, se, ex / (1.0 + ex));      // == par[PAR_SGT] of that state (compute_par_entry)
-            const double qnx = next_entry_pre(pv, qv, lhs, leps, theta_entry_grad(pb.beta_inv, tpp, sg), msc);
+            double gj = theta_entry_grad(pb.beta_inv, tpp, sg);
+            if (pb.prior) gj = theta_entry_grad_prior(gj, Prior::load(pb.prior, D, D + li), hsup, se, qv, ex, sg);      // (priors: wave-uniform)
+            const double qnx = next_entry_pre(pv, qv, lhs, leps, gj, msc);
             thp = ThetaSup::theta(hsup, se, qnx, m_log(1.0 + m_exp(qnx)));      // == par'[PAR_TH] (compute_par_entry)
         }
         if (mine) th_s[cg * 8 + li] = thp;

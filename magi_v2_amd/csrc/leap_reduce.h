@@ -40,6 +40,12 @@ __device__ __forceinline__ void part_rows_sum(const double* part, int nwg, int r
 // dth = d theta / d pre (PAR_SGT): sg for a positive or lower-bounded parameter, -sg for an upper-bounded one, 1 for a real one; the
 // log-Jacobian's derivative is 1 - |dth| for all of them (ThetaSup, magi_internal.h), and |sg| is sg bit for bit.
 __device__ __forceinline__ double theta_entry_grad(double beta_inv, double tpp, double dth) { return -0.5 * beta_inv * tpp * dth + (1.0 - fabs(dth)); }
+// the same under a prior table (Prior, magi_internal.h), for the stream kernels that hold pre and e^pre of the entry and not its parameter
+// block: theta as compute_par_entry forms PAR_TH, then Prior::grad as the reduce applies it.  `pe`: entry D + p of the table.
+__device__ __forceinline__ double theta_entry_grad_prior(double g0, const double4& pe, bool hsup, double2 se, double pre, double ex, double dth) {
+    if (Prior::flat(pe)) return g0;
+    return Prior::grad(pe, g0, ThetaSup::theta(hsup, se, pre, m_log(1.0 + ex)), dth);
+}
 // position of a parameter entry after completing this leaf's momentum step and taking the next half step
 // (`s`: the entry's metric scale, 1 under the identity metric -- the momentum is the whitened one, DevChains::scale)
 __device__ __forceinline__ double next_entry_pre(double ph, double q, double hs, double eps, double gj, double s) {
@@ -113,7 +119,7 @@ __device__ __forceinline__ void reduce_prefetch_ops_store(const double (&tmp)[PE
     }
 }
 
-// sh: (21 + 4) * 16 doubles (scratch + a 64-double parking block), shs: >= 16 doubles.  `lp` is the plan the point phase just
+// sh: (21 + 4) * 16 doubles (scratch + a 64-double parking block), shs: >= 16 doubles ([12]: the log prior, when a table is set).  `lp` is the plan the point phase just
 // executed; `pre` the values of leap_reduce_issue; `par_r` the state's parameter block (may be an LDS copy), `par` the global one.
 template <int DRIFT>
 __device__ __forceinline__ ReduceOut leap_reduce(const DevProblem& pb, const DevChains& ch, int chain, double* vb, double* par, const double* par_r,
@@ -186,11 +192,13 @@ __device__ __forceinline__ ReduceOut leap_reduce(const DevProblem& pb, const Dev
             t4 = ssd * (1.0 / sj);
             lj = par_r[PAR_LJS + j];
             gj = -0.5 * (nds / sj - ssd / (sj * sj)) * sg + (1.0 - sg);
+            if (pb.prior) gj = Prior::grad_sigma(Prior::load(pb.prior, D, j), gj, sj, sg);      // (priors: wave-uniform; log p itself: wave 2 below)
         } else if (plane) {
             const double sg = par_r[PAR_SGT + (j - D)];
             const double tpp = select_lane<K0 + 8>(red, 1 + D, P, j - D);
             lj = par_r[PAR_LJT + (j - D)];
             gj = theta_entry_grad(pb.beta_inv, tpp, sg);
+            if (pb.prior) gj = Prior::grad(Prior::load(pb.prior, D, j), gj, par_r[PAR_TH + (j - D)], sg);
         }
         double ppj = 0.0, a[4] = {0.0, 0.0, 0.0, 0.0}, b[4] = {0.0, 0.0, 0.0, 0.0};
         if (plane) {
@@ -235,10 +243,12 @@ __device__ __forceinline__ ReduceOut leap_reduce(const DevProblem& pb, const Dev
                 const double ssd = select_lane<K0 + 8>(red, 1, D, jj);
                 const double nds = cst ? cst[jj] : MAGI_SEL_D(pb.N_ds, jj);
                 gj = -0.5 * (nds / sj - ssd / (sj * sj)) * sg + (1.0 - sg);
+                if (pb.prior) gj = Prior::grad_sigma(Prior::load(pb.prior, D, jj), gj, sj, sg);
             } else {
                 const double sg = par_r[PAR_SGT + (jj - D)];
                 const double tpp = select_lane<K0 + 8>(red, 1 + D, P, jj - D);
                 gj = theta_entry_grad(pb.beta_inv, tpp, sg);
+                if (pb.prior) gj = Prior::grad(Prior::load(pb.prior, D, jj), gj, par_r[PAR_TH + (jj - D)], sg);
             }
             const double phv = ops ? ops[(OPS_P + lp.cur) * OPS_W + jj] : ph[ND + jj], qv = ops ? ops[(OPS_Q + lp.cur) * OPS_W + jj] : q[ND + jj];
             sh[21 * 16 + jj] = next_entry_pre(phv, qv, lp.hs, lp.eps, gj, msc);      // parking block of 64 doubles behind block_sum's scratch: read by leap_next_par
@@ -253,11 +263,19 @@ __device__ __forceinline__ ReduceOut leap_reduce(const DevProblem& pb, const Dev
         }
         t3 = row16_sum(t3);
         if (jd == 0) shs[1] = t3;
+        // priors (wave-uniform): sum_j log p of the evaluated state's D + P entries, here and not in wave 0 -- these lanes hold nothing else
+        if (pb.prior) {
+            double lp = 0.0;
+            if (jd < D + P) lp = Prior::logp(Prior::load(pb.prior, D, jd), par_r[jd < D ? PAR_SIG2 + jd : PAR_TH + (jd - D)]);
+            lp = row16_sum(lp);
+            if (jd == 0) shs[12] = lp;
+        }
     }
     __syncthreads();
     ReduceOut o;
     o.t12 = red[0]; o.t3 = shs[1]; o.t4 = shs[2]; o.pp = shs[3];
     o.L = -0.5 * ((pb.beta_inv * red[0]) + (o.t3 + o.t4)) + shs[0];
+    if (pb.prior) o.L += shs[12];
 #pragma unroll
     for (int k = 0; k < 4; ++k) { o.dA[k] = shs[4 + 2 * k]; o.dB[k] = shs[5 + 2 * k]; }
     __syncthreads();   // shs may be reused by the caller

@@ -94,7 +94,9 @@
             if (lane < P) {
                 const double ex = m_exp(qv);
                 const double sg = ThetaSup::dtheta(hsup, se, ex / (1.0 + ex));      // == par[PAR_SGT] of that state (compute_par_entry)
-                const double qnx = next_entry_pre(pv, qv, lp->hs, lp->eps, theta_entry_grad(pb.beta_inv, tpp, sg), msc);
+                double gj = theta_entry_grad(pb.beta_inv, tpp, sg);
+                if (pb.prior) gj = theta_entry_grad_prior(gj, Prior::load(pb.prior, D, D + lane), hsup, se, qv, ex, sg);      // (priors: wave-uniform)
+                const double qnx = next_entry_pre(pv, qv, lp->hs, lp->eps, gj, msc);
                 thp = ThetaSup::theta(hsup, se, qnx, m_log(1.0 + m_exp(qnx)));      // == par'[PAR_TH] (compute_par_entry)
             }
         } else if (lane < P) {

@@ -75,6 +75,11 @@ struct DevProblem {
                            // drift uses t (DriftT<>::TDEP, point_time below) and by no other; nullptr until they are set
     const double2* tsup;   // [MAGI_MAX_P] support of every parameter (magi_set_theta_support; ThetaSup below): (sign, bound); nullptr: every
                            // parameter is positive, theta = softplus(pre) -- the kernels then run the instructions they ran without supports
+    const double4* prior;  // [MAGI_MAX_D + MAGI_MAX_P] prior of every parameter entry, sigma^2_0.. then theta_0.. at MAGI_MAX_D (magi_set_prior; Prior
+                           // below): (kind, a, b, 1 / b^2); nullptr: every prior is flat -- the kernels then run the instructions they ran without priors
+    int fixed_mask;        // bit j: sigma^2_j is fixed (MAGI_PRIOR_FIXED) at LB[j], which then holds the constant itself; 0 without one.  A scalar of
+                           // the problem and no table look-up: compute_par_entry also runs in the point kernel's boundary pass, where a load
+                           // and a second mask cost the point kernel of a traced drift 48 B of scratch
 };
 
 // Support of one parameter entry, as a table entry (x, y) = (sign, bound):
@@ -92,6 +97,29 @@ struct ThetaSup {
     static __device__ __forceinline__ double logjac(bool has, double2 se, double pre, double sp) { return (has && se.x == 0.0) ? 0.0 : pre - sp; }
     // entry p of the table; (1, 0) without one.  p is clamped by the caller.
     static __device__ __forceinline__ double2 load(const double2* sup, int p) { return sup ? sup[p] : make_double2(1.0, 0.0); }
+};
+
+// Prior of one parameter entry on its NATURAL scale v (sigma^2 = softplus(pre) + LB; theta under its support), DESIGN 4.2d, as a table
+// entry (x, y, z, w) = (kind MAGI_PRIOR_*, a, b, 1 / b^2).  Unnormalised:
+//   flat       0                                        normal (m, s)     -(v - m)^2 / (2 s^2)
+//   lognormal  -log v - (log v - m)^2 / (2 s^2)         gamma (k, r)      (k - 1) log v - r v
+//   invgamma   -(a + 1) log v - b / v                   fixed c           sigma^2 entries only: v = c whatever pre is, see compute_par_entry
+// log p joins the entry's log-Jacobian term where that term is summed into L, and its gradient (d log p / dv)(dv / dpre) is formed where the
+// entry's gradient is -- both from the block's natural value and dv / dpre (leap_reduce, finalize_gradient), the gradient by `grad` below -- the ONE statement of it, so the
+// theta' a stream kernel derives equals the decisions' to the bit (the products are explicit fma's or single operations: nothing left to
+// contract differently from site to site).  The table pointer is null (wave-uniform) while every prior is flat.
+struct Prior {
+    enum { FLAT = 0, NORMAL = 1, LOGNORMAL = 2, GAMMA = 3, INVGAMMA = 4, FIXED = 5 };
+    // entry j of the parameter block (j < D: sigma^2_j; else theta_{j - D}); the caller has tested the pointer
+    static __device__ __forceinline__ double4 load(const double4* tab, int D, int j) { return tab[j < D ? j : min(MAGI_MAX_D + (j - D), MAGI_MAX_D + MAGI_MAX_P - 1)]; }
+    static __device__ __forceinline__ bool flat(const double4& e) { return e.x == (double)FLAT; }
+    static __device__ __forceinline__ bool fixed(const double4& e) { return e.x == (double)FIXED; }
+    static __device__ inline double logp(const double4& e, double v);
+    static __device__ inline double dlogp(const double4& e, double v);
+    // g0: the entry's gradient without a prior; v, dv: its natural value and dv / dpre (PAR_SIG2, PAR_SGS / PAR_TH, PAR_SGT)
+    static __device__ __forceinline__ double grad(const double4& e, double g0, double v, double dv) { return flat(e) ? g0 : fma(dlogp(e, v), dv, g0); }
+    // a sigma^2 entry: under FIXED, PAR_SGS holds pre itself (d sigma^2 / d pre is 0 and needs no slot) and the gradient is that of -pre^2 / 2
+    static __device__ __forceinline__ double grad_sigma(const double4& e, double g0, double s2, double sgs) { return fixed(e) ? -sgs : grad(e, g0, s2, sgs); }
 };
 
 // Member m of a problem group's device table (magi_group_create; leap.hip: k_stream_group).  The index is wave-uniform and the table
@@ -341,6 +369,24 @@ static __device__ __noinline__ double m_exp(double x) { return exp(x); }
 static __device__ __noinline__ double m_log1p(double x) { return log1p(x); }
 
 __device__ inline double softplus_ref(double x) { return m_log(1.0 + m_exp(x)); }   // magi_v2.py:318
+
+__device__ inline double Prior::logp(const double4& e, double v) {
+    const int k = (int)e.x;
+    if (k == NORMAL) { const double d = v - e.y; return -0.5 * (d * d) * e.w; }
+    if (k == FLAT || k == FIXED) return 0.0;
+    const double lv = m_log(v);
+    if (k == LOGNORMAL) { const double d = lv - e.y; return -lv - 0.5 * (d * d) * e.w; }
+    if (k == GAMMA) return (e.y - 1.0) * lv - e.z * v;
+    return -(e.y + 1.0) * lv - e.z / v;
+}
+__device__ inline double Prior::dlogp(const double4& e, double v) {
+    const int k = (int)e.x;
+    if (k == NORMAL) return -((v - e.y) * e.w);
+    if (k == LOGNORMAL) return -fma(m_log(v) - e.y, e.w, 1.0) / v;
+    if (k == GAMMA) return (e.y - 1.0) / v - e.z;
+    if (k == INVGAMMA) return (e.z / v - (e.y + 1.0)) / v;
+    return 0.0;
+}
 __device__ inline double sigmoid(double x) { return 1.0 / (1.0 + m_exp(-x)); }
 
 __device__ inline double logaddexp(double a, double b) {
@@ -394,19 +440,27 @@ __device__ inline void compute_par_entry(const DevProblem& pb, int j, double pre
     const double sg = e / (1.0 + e);           // d softplus / d pre (= 1/(1+exp(-pre)) up to rounding)
     if (j < pb.D) {
         const double lb = lb_tab ? lb_tab[j] : MAGI_SEL_D(pb.LB, j);
-        const double s2 = sp + lb;
+        double s2 = sp + lb, dsg = sg, ljs = pre - sp;
+        if (pb.fixed_mask) {                                       // (wave-uniform) a fixed sigma^2: the constant (held in LB), pre itself in PAR_SGS, -pre^2 / 2
+            const bool fx = (pb.fixed_mask >> j) & 1;
+            s2 = fx ? lb : s2;
+            dsg = fx ? pre : dsg;
+            ljs = fx ? -0.5 * (pre * pre) : ljs;
+        }
         par[PAR_SIG2 + j] = s2;
-        par[PAR_SGS + j] = sg;
-        par[PAR_LJS + j] = pre - sp;
+        par[PAR_SGS + j] = dsg;
+        par[PAR_LJS + j] = ljs;
         if (with_log2pis) par[PAR_LOG2PIS + j] = m_log(2.0 * 3.141592653589793 * s2);      // (leap_reduce evaluates it at the consumer)
     } else {
         // PAR_SGT holds d theta / d pre under the parameter's support (ThetaSup above; sg itself without a table)
         const int p = j - pb.D;
         const bool has = pb.tsup != nullptr;                       // (wave-uniform)
         const double2 se = ThetaSup::load(pb.tsup, min(p, MAGI_MAX_P - 1));
-        par[PAR_TH + p] = ThetaSup::theta(has, se, pre, sp);
+        const double th = ThetaSup::theta(has, se, pre, sp);
+        const double ljt = ThetaSup::logjac(has, se, pre, sp);
+        par[PAR_TH + p] = th;
         par[PAR_SGT + p] = ThetaSup::dtheta(has, se, sg);
-        par[PAR_LJT + p] = ThetaSup::logjac(has, se, pre, sp);
+        par[PAR_LJT + p] = ljt;
     }
 }
 
@@ -904,13 +958,17 @@ __device__ inline FinalizeOut finalize_gradient(const DevProblem& pb, double* vb
             t4 = ssd * (1.0 / s2);
             lj = par[PAR_LJS + j];
             const double dsig = nds / s2 - ssd / (s2 * s2);
-            g[ND + j] = -0.5 * dsig * sg + (1.0 - sg);
+            double gj = -0.5 * dsig * sg + (1.0 - sg);
+            if (pb.prior) { const double4 pe = Prior::load(pb.prior, D, j); gj = Prior::grad_sigma(pe, gj, s2, sg); lj += Prior::logp(pe, s2); }
+            g[ND + j] = gj;
         } else if (j < D + P) {
             const int p = j - D;
             const double sg = par[PAR_SGT + p];                     // d theta / d pre; the log-Jacobian's derivative is 1 - |sg| (ThetaSup)
             const double tpp = select_lane<K>(red, 2 + MAGI_MAX_D, MAGI_MAX_P, p);
             lj = par[PAR_LJT + p];
-            g[ND + D + p] = -0.5 * pb.beta_inv * tpp * sg + (1.0 - fabs(sg));
+            double gj = -0.5 * pb.beta_inv * tpp * sg + (1.0 - fabs(sg));
+            if (pb.prior) { const double4 pe = Prior::load(pb.prior, D, j); gj = Prior::grad(pe, gj, par[PAR_TH + p], sg); lj += Prior::logp(pe, par[PAR_TH + p]); }
+            g[ND + D + p] = gj;
         }
         t3 = wave_sum(t3);
         t4 = wave_sum(t4);
@@ -988,6 +1046,12 @@ struct magi_handle {
     int th_kind[MAGI_MAX_P] = {};
     double th_bound[MAGI_MAX_P] = {};
     double2* dTsup = nullptr;
+    // priors of the D + P parameter entries (magi_set_prior): the host copy, and the device table pb.prior points at while any is not flat
+    // (allocated once, MAGI_MAX_D + MAGI_MAX_P entries, freed with the handle, as dTsup)
+    int pr_kind[MAGI_MAX_D + MAGI_MAX_P] = {};
+    double pr_a[MAGI_MAX_D + MAGI_MAX_P] = {}, pr_b[MAGI_MAX_D + MAGI_MAX_P] = {};
+    double4* dPrior = nullptr;
+    double lb_orig[MAGI_MAX_D] = {};  // LB as magi_set_problem gave it (pb.LB holds the constant of a fixed sigma^2 instead)
     size_t mat_elems = 0;
     // dense C^-1, m, K^-1 ([D][N][N], unmasked) as built or uploaded: authoritative until the caller uploads others; packed
     // (band mask, symmetrised / transposed copies, single-phase operator blocks) by magi_pack_matrices

@@ -33,13 +33,17 @@ struct SumProbs { double p[MAX_Q]; };
 
 __global__ __launch_bounds__(G_TILE * 4) void k_sum_gather(int S, int nc, const double* __restrict__ src /* rows ld apart, nc columns */,
                                                            long long ld, int mode, int lb0, SumLB lb, const double2* __restrict__ tsup /* MODE_THETA: the parameters' supports, or null */,
+                                                           const double4* __restrict__ prior /* MODE_SIGMA: the prior table (a fixed sigma^2 reports its constant), or null */,
                                                            double* __restrict__ chunk /* [nc][S] */) {
     __shared__ double tile[G_TILE][G_TILE + 1];               // (+1: the column reads below fall on 32 different bank pairs)
     const int r0 = blockIdx.x * G_TILE, c0 = blockIdx.y * G_TILE, tx = threadIdx.x, ty = threadIdx.y;
     for (int r = ty; r < G_TILE; r += 4)
         if (r0 + r < S && c0 + tx < nc) {
             double v = src[(size_t)(r0 + r) * (size_t)ld + c0 + tx];
-            if (mode == MODE_SIGMA) v = softplus_ref(v) + lb.v[lb0 + c0 + tx];          // (lb0 + nc <= D: the sigma block has D columns)
+            if (mode == MODE_SIGMA) {
+                v = softplus_ref(v) + lb.v[lb0 + c0 + tx];                              // (lb0 + nc <= D: the sigma block has D columns)
+                if (prior) { const double4 pe = prior[lb0 + c0 + tx]; if (Prior::fixed(pe)) v = pe.y; }
+            }
             else if (mode == MODE_THETA) v = ThetaSup::theta(tsup != nullptr, ThetaSup::load(tsup, lb0 + c0 + tx), v, softplus_ref(v));      // (lb0 + nc <= P)
             tile[r][tx] = v;
         }
@@ -342,7 +346,7 @@ struct SumOut { double *mean, *sd, *quant, *rhat, *ess, *mcse; };
 // one block of K columns of C x R draws: from the device (dsrc: column j of row r at dsrc[r ld + j]) or from the host (hsrc [C R][K]).
 // Adds the block's columns with a non-finite draw to *nonfinite.
 int summarize_block(magi_handle* h, const char* who, const double* dsrc, const double* hsrc, long long ld, int C, int R, long long K, int mode,
-                    int N, int D, const SumLB& lb, const double2* tsup, int n_q, const SumProbs& probs, int max_lag, const SumOut& o, int* nonfinite) {
+                    int N, int D, const SumLB& lb, const double2* tsup, const double4* prior, int n_q, const SumProbs& probs, int max_lag, const SumOut& o, int* nonfinite) {
     const size_t S = (size_t)C * R, M = 2 * (size_t)C;
     size_t cc = std::max<size_t>(1, CHUNK_DOUBLES / S);
     cc = std::min<size_t>({cc, (size_t)K, (size_t)1 << 21});             // (k_sum_gather: at most 2^15 tiles along grid.y)
@@ -369,7 +373,7 @@ int summarize_block(magi_handle* h, const char* who, const double* dsrc, const d
             if (e != hipSuccess) break;
         }
         rc = magi_launch(h, "k_sum_gather: ", k_sum_gather, dim3((unsigned)((S + G_TILE - 1) / G_TILE), (unsigned)((nc + G_TILE - 1) / G_TILE)),
-                         dim3(G_TILE, 4), h->stream, (int)S, nc, src, sld, mode, (int)c0, lb, tsup, chunk);
+                         dim3(G_TILE, 4), h->stream, (int)S, nc, src, sld, mode, (int)c0, lb, tsup, prior, chunk);
         if (rc == MAGI_OK)
             rc = magi_launch(h, "k_sum_moments: ", k_sum_moments, dim3((unsigned)nc), dim3(SUM_WG), h->stream, C, R, (const double*)chunk, yb, col,
                              (long long)c0, mode, N, D, dmean, dsd, drhat, dcount);
@@ -433,7 +437,7 @@ int magi_summarize(magi_handle* h, int C, int R, int K, const double* draws, int
     (void)hipSetDevice(h->device);
     SumLB lb{};
     int count = 0;
-    rc = summarize_block(h, who, nullptr, draws, K, C, R, K, MODE_PLAIN, 1, 1, lb, nullptr, n_q, pr, max_lag, SumOut{mean, sd, quant, rhat, ess, mcse_mean}, &count);
+    rc = summarize_block(h, who, nullptr, draws, K, C, R, K, MODE_PLAIN, 1, 1, lb, nullptr, nullptr, n_q, pr, max_lag, SumOut{mean, sd, quant, rhat, ess, mcse_mean}, &count);
     if (rc == MAGI_OK && n_nonfinite) *n_nonfinite = count;
     return rc;
 }
@@ -470,24 +474,26 @@ int magi_sampler_summarize(magi_handle* h, int chain0, int n_sel, int n_q, const
     const DevProblem& pb = h->pb;
     SumLB lb{};
     const double2* tsup = pb.tsup;                             // the parameters' supports: the handle's, or the member's own on a group
+    const double4* prior = pb.prior;                           // likewise the prior table
     if (member >= 0) {                                         // the member's problem as the sampler read it (magi_sampler_init)
         DevProblem mp;
         MAGI_HIP_CHECK(h, hipMemcpy(&mp, h->d_members + member, sizeof(DevProblem), hipMemcpyDeviceToHost));
         for (int d = 0; d < pb.D; ++d) lb.v[d] = mp.LB[d];
         tsup = mp.tsup;
+        prior = mp.prior;
     } else {
         for (int d = 0; d < pb.D; ++d) lb.v[d] = pb.LB[d];
     }
     const double* base = h->ch.samples + (size_t)chain0 * R * pb.dimp;
     int count = 0;
     if (X_mean || X_sd || X_quant || X_rhat || X_ess || X_mcse_mean || n_nonfinite)
-        rc = summarize_block(h, who, base, nullptr, pb.dimp, n_sel, R, pb.ND, MODE_X, pb.N, pb.D, lb, nullptr, n_q, pr, max_lag,
+        rc = summarize_block(h, who, base, nullptr, pb.dimp, n_sel, R, pb.ND, MODE_X, pb.N, pb.D, lb, nullptr, nullptr, n_q, pr, max_lag,
                              SumOut{X_mean, X_sd, X_quant, X_rhat, X_ess, X_mcse_mean}, &count);
     if (rc == MAGI_OK && (sig_mean || sig_sd || sig_quant || sig_rhat || sig_ess || sig_mcse_mean || n_nonfinite))
-        rc = summarize_block(h, who, base + pb.ND, nullptr, pb.dimp, n_sel, R, pb.D, MODE_SIGMA, pb.N, pb.D, lb, nullptr, n_q, pr, max_lag,
+        rc = summarize_block(h, who, base + pb.ND, nullptr, pb.dimp, n_sel, R, pb.D, MODE_SIGMA, pb.N, pb.D, lb, nullptr, prior, n_q, pr, max_lag,
                              SumOut{sig_mean, sig_sd, sig_quant, sig_rhat, sig_ess, sig_mcse_mean}, &count);
     if (rc == MAGI_OK && (th_mean || th_sd || th_quant || th_rhat || th_ess || th_mcse_mean || n_nonfinite))
-        rc = summarize_block(h, who, base + pb.ND + pb.D, nullptr, pb.dimp, n_sel, R, pb.P, MODE_THETA, pb.N, pb.D, lb, tsup, n_q, pr, max_lag,
+        rc = summarize_block(h, who, base + pb.ND + pb.D, nullptr, pb.dimp, n_sel, R, pb.P, MODE_THETA, pb.N, pb.D, lb, tsup, nullptr, n_q, pr, max_lag,
                              SumOut{th_mean, th_sd, th_quant, th_rhat, th_ess, th_mcse_mean}, &count);
     if (rc == MAGI_OK && n_nonfinite) *n_nonfinite = count;
     return rc;

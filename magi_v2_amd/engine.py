@@ -12,7 +12,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .host import theta_support
+from .host import prior_spec, theta_support
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmagi_hip.so")
@@ -61,6 +61,8 @@ _SYMBOLS = {
     "magi_set_times": (C.c_int, [C.c_void_p, _dp, C.c_int]),
     "magi_set_theta_support": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp]),
     "magi_get_theta_support": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp]),
+    "magi_set_prior": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp]),
+    "magi_get_prior": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp]),
     "magi_logpost_grad": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "magi_logpost_grad_fused": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "magi_sampler_cfg_default": (None, [C.POINTER(SamplerCfg)]),
@@ -461,6 +463,31 @@ class MagiEngine:
         kinds, bounds = np.zeros(self.P, dtype=np.int32), np.zeros(self.P)
         self._check(self._lib.magi_get_theta_support(self._h, int(self.P), kinds.ctypes.data_as(_ip), _ptr(bounds)))
         return kinds, bounds
+
+    def set_prior(self, sigma_sq_prior=None, theta_prior=None):
+        """Priors on the noise variances and the ODE parameters (magi_set_prior), after ``set_problem`` -- which resets them to flat -- and
+        after ``set_theta_support``: each None (flat) or one entry per component / parameter out of None / "flat", ("normal", m, s),
+        ("lognormal", m, s), ("gamma", k, r), ("invgamma", a, b) and, for a noise variance, ("fixed", c) (host.prior_spec).  They act on the
+        natural scale and govern ``logpost_grad``, the next ``sampler_init`` and the sigma^2 block of ``sampler_summary`` (a fixed variance
+        reports its constant)."""
+        if self.P is None:
+            raise MagiHipError(-5, "set_prior: set the problem first (magi_set_problem)")
+        ks, as_, bs = prior_spec(sigma_sq_prior, self.D, "sigma_sq")
+        kt, at, bt = prior_spec(theta_prior, self.P, "theta", self.theta_support())
+        kinds = np.ascontiguousarray(np.concatenate([ks, kt]), dtype=np.int32)
+        a, b = np.ascontiguousarray(np.concatenate([as_, at])), np.ascontiguousarray(np.concatenate([bs, bt]))
+        flat = sigma_sq_prior is None and theta_prior is None
+        self._check(self._lib.magi_set_prior(self._h, int(self.D + self.P), None if flat else kinds.ctypes.data_as(_ip), _ptr(a), _ptr(b)))
+
+    def prior(self):
+        """The priors in force as ((kinds int32[D], a[D], b[D]) of sigma^2, (kinds int32[P], a[P], b[P]) of theta) (magi_get_prior;
+        host.prior_spec_echo names them)."""
+        if self.P is None:
+            raise MagiHipError(-5, "prior: set the problem first (magi_set_problem)")
+        n, D = int(self.D + self.P), int(self.D)
+        kinds, a, b = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n)
+        self._check(self._lib.magi_get_prior(self._h, n, kinds.ctypes.data_as(_ip), _ptr(a), _ptr(b)))
+        return (kinds[:D], a[:D], b[:D]), (kinds[D:], a[D:], b[D:])
 
     def _states(self, X, sig_pre, th_pre):
         X = _f64(X)

@@ -102,9 +102,14 @@ def softplus_inverse_inits(sigma_sqs_init, thetas_init, LB):
     return sig_pre, th_pre
 
 
-def transform_samples(sig_pre, th_pre, LB):
-    """magi_v2.py:418-419."""
-    return np.log(np.exp(sig_pre) + 1.0) + LB, np.log(np.exp(th_pre) + 1.0)
+def transform_samples(sig_pre, th_pre, LB, sigma_sq_prior=None):
+    """magi_v2.py:418-419.  ``sigma_sq_prior``: None or the (kinds, a, b) of ``prior_spec(..., "sigma_sq")`` -- a component whose noise variance is
+    fixed reports that constant, whatever its ``pre`` coordinate is."""
+    sig = np.log(np.exp(sig_pre) + 1.0) + LB
+    if sigma_sq_prior is not None:
+        kinds, a, _ = sigma_sq_prior
+        sig = np.where(np.asarray(kinds) == PRIOR_FIXED, np.asarray(a, dtype=np.float64), sig)
+    return sig, np.log(np.exp(th_pre) + 1.0)
 
 
 # supports of the ODE parameters (include/magi_hip.h: magi_set_theta_support; DESIGN 4.2c).  The codes are the header's MAGI_THETA_*.
@@ -173,6 +178,69 @@ def transform_thetas(th_pre, kinds, bounds):
         sp = np.log(np.exp(th_pre) + 1.0)
     out = np.where(kinds == THETA_LOWER, bounds + sp, np.where(kinds == THETA_UPPER, bounds - sp, sp))
     return np.where(kinds == THETA_REAL, th_pre, out)
+
+
+# priors of the parameter entries (include/magi_hip.h: magi_set_prior).  The codes are the header's MAGI_PRIOR_*.
+PRIOR_FLAT, PRIOR_NORMAL, PRIOR_LOGNORMAL, PRIOR_GAMMA, PRIOR_INVGAMMA, PRIOR_FIXED = 0, 1, 2, 3, 4, 5
+_PRIOR_NAMES = {"normal": PRIOR_NORMAL, "lognormal": PRIOR_LOGNORMAL, "gamma": PRIOR_GAMMA, "invgamma": PRIOR_INVGAMMA}
+_PRIOR_POSITIVE = (PRIOR_LOGNORMAL, PRIOR_GAMMA, PRIOR_INVGAMMA)          # densities on (0, inf)
+
+
+def prior_spec(spec, n: int, which: str, support=None):
+    """Normalises a prior specification for the n entries of one block into (kinds int32[n], a float64[n], b float64[n]).  ``which`` is
+    "sigma_sq" or "theta".  ``spec`` is None (every prior flat, the reference's posterior) or n entries out of None / "flat",
+    ("normal", m, s), ("lognormal", m, s), ("gamma", k, r), ("invgamma", a, b) and, for sigma_sq only, ("fixed", c): all parameters finite;
+    s, k, r, a, b, c > 0.  ``support`` (theta only): the (kinds, bounds) of ``theta_support`` -- lognormal, gamma and invgamma need a
+    support inside (0, inf): positive, or lower with lo >= 0.  Anything else raises ValueError.  b of a fixed entry is 0."""
+    if which not in ("sigma_sq", "theta"):
+        raise ValueError(f"prior_spec: which = {which!r} is neither 'sigma_sq' nor 'theta'")
+    n = int(n)
+    name = which + "_prior"
+    kinds, a, b = np.zeros(n, dtype=np.int32), np.zeros(n, dtype=np.float64), np.zeros(n, dtype=np.float64)
+    if spec is None:
+        return kinds, a, b
+    if isinstance(spec, (str, bytes)) or not hasattr(spec, "__len__"):
+        raise ValueError(f"{name}: expected None or a sequence of {n} entries, got {spec!r}")
+    if len(spec) != n:
+        raise ValueError(f"{name}: {len(spec)} entries for {n} parameters")
+    known = "None, 'flat', ('normal', m, s), ('lognormal', m, s), ('gamma', k, r), ('invgamma', a, b)" + (", ('fixed', c)" if which == "sigma_sq" else "")
+    for j, e in enumerate(spec):
+        if e is None or (isinstance(e, str) and e == "flat"):
+            continue
+        if not isinstance(e, (tuple, list)) or len(e) < 1 or not isinstance(e[0], str):
+            raise ValueError(f"{name}[{j}]: {e!r} is none of {known}")
+        if e[0] == "fixed":
+            if which != "sigma_sq":
+                raise ValueError(f"{name}[{j}]: 'fixed' is for noise variances only (a constant in f_vec states a fixed parameter)")
+            want = 1
+        elif e[0] in _PRIOR_NAMES:
+            want = 2
+        else:
+            raise ValueError(f"{name}[{j}]: {e!r} is none of {known}")
+        if len(e) != 1 + want:
+            raise ValueError(f"{name}[{j}]: {e[0]!r} takes {want} parameter(s), got {len(e) - 1}")
+        try:
+            v = [float(x) for x in e[1:]]
+        except (TypeError, ValueError):
+            raise ValueError(f"{name}[{j}]: the parameters of {e!r} are not numbers") from None
+        if not all(np.isfinite(v)):
+            raise ValueError(f"{name}[{j}]: the parameters of {e!r} are not finite")
+        k = PRIOR_FIXED if e[0] == "fixed" else _PRIOR_NAMES[e[0]]
+        if not v[-1] > 0.0 or (k in (PRIOR_GAMMA, PRIOR_INVGAMMA) and not v[0] > 0.0):
+            raise ValueError(f"{name}[{j}]: sd, shape, rate, scale and a fixed value must be > 0, got {e!r}")
+        if which == "theta" and k in _PRIOR_POSITIVE and support is not None:
+            sk, sb = int(np.asarray(support[0])[j]), float(np.asarray(support[1])[j])
+            if not (sk == THETA_POSITIVE or (sk == THETA_LOWER and sb >= 0.0)):
+                raise ValueError(f"{name}[{j}]: a {e[0]} prior needs a support inside (0, inf): 'positive', or ('lower', lo) with lo >= 0")
+        kinds[j], a[j], b[j] = k, v[0], (0.0 if k == PRIOR_FIXED else v[1])
+    return kinds, a, b
+
+
+def prior_spec_echo(kinds, a, b):
+    """The normalised specification (a list of "flat", ("normal", m, s), ..., ("fixed", c)) of (kinds, a, b)."""
+    names = {v: k for k, v in _PRIOR_NAMES.items()}
+    return ["flat" if int(k) == PRIOR_FLAT else ("fixed", float(x)) if int(k) == PRIOR_FIXED else (names[int(k)], float(x), float(y))
+            for k, x, y in zip(kinds, a, b)]
 
 
 def observation_bookkeeping(X_obs: np.ndarray, X_grid: np.ndarray):
