@@ -191,6 +191,31 @@ enum { MAGI_PRIOR_FLAT = 0, MAGI_PRIOR_NORMAL = 1, MAGI_PRIOR_LOGNORMAL = 2, MAG
 int magi_set_prior(magi_handle* h, int n /* D + P */, const int* kind, const double* a, const double* b);
 int magi_get_prior(magi_handle* h, int n /* D + P */, int* kind, double* a, double* b);
 
+/* Observation model (opt-in; the reference observes every component as y = x + N(0, sigma^2_d) with one variance for all its points, and
+ * that stays the default).  Component d is observed through a link g_d, with Gaussian error on the LINK's scale:
+ *   MAGI_LINK_IDENTITY  g(x) = x                                         (the reference)
+ *   MAGI_LINK_LOG       g(x) = log x     data y > 0                      (multiplicative error)
+ *   MAGI_LINK_SQRT      g(x) = sqrt x    data y >= 0                     (counts, variance-stabilised)
+ * and observation k -- in the order of magi_set_problem's obs_idx -- may carry a known weight w_k > 0 (the mean of n replicates: n):
+ *   t4 = sum_d (1 / sigma^2_d) sum_{k in obs_d} w_k (g_d(x_k) - g_d(y_k))^2,   t3 = sum_d N_d log(2 pi sigma^2_d) as before;
+ * the constant Jacobian of the data transform and sum log w_k are dropped (the density is unnormalised).  sigma^2_d is the variance on the
+ * link's scale; the GP terms, the drift, theta, the samples and every summary see x itself.  The link is evaluated at observed points
+ * only: a state with x <= 0 (log) or x < 0 (sqrt) THERE has a non-finite log posterior -- magi_logpost_grad* return NaN for that state and
+ * leave the others of the batch untouched, the sampler counts the leaf as energy -inf -- as for a state outside a drift's domain.
+ * link = NULL: every link the identity; weight = NULL: every weight 1; both NULL: back to the default.  A handle whose model was never set,
+ * or set to all-IDENTITY without weights, computes bit for bit what it computed without this call (the kernels test one scalar and one
+ * pointer).  The model belongs to the problem: magi_set_problem resets it (and the handle keeps the untransformed data, so the model can be
+ * changed or reset without a new magi_set_problem); it governs magi_logpost_grad*, the next magi_sampler_init (it invalidates the sampler
+ * state and the captured graph), and the handle as a member of a group (each member brings its own).  A fixed sigma^2 (MAGI_PRIOR_FIXED)
+ * composes with it: the constant is then the variance on the link's scale.
+ * Errors, each leaving the handle as it was: MAGI_E_BADARG for D or n_obs other than the problem's, a link out of range, a weight that is
+ * not finite or not > 0, a datum outside its link's domain; MAGI_E_STATE before magi_set_problem and on a group handle.  Checkpoints carry
+ * the model in their tag when one is set.
+ *   magi_get_obs_model   the model in force (weights 1 when none were given); either output may be NULL. */
+enum { MAGI_LINK_IDENTITY = 0, MAGI_LINK_LOG = 1, MAGI_LINK_SQRT = 2 };
+int magi_set_obs_model(magi_handle* h, int D, const int* link /* [D] or NULL */, int64_t n_obs, const double* weight /* [n_obs], aligned with magi_set_problem's obs_idx, or NULL */);
+int magi_get_obs_model(magi_handle* h, int D, int* link, int64_t n_obs, double* weight);
+
 /* unnormalized_log_prob (magi_v2.py:308-348) and its gradient (TF autodiff in the reference,
  * induced by magi_v2.py:360-364) for n_chains independent states.
  * X[n_chains][N][D], sig_pre[n_chains][D], th_pre[n_chains][P] -> logp[n_chains],

@@ -352,7 +352,7 @@ class MAGI_v2:
                 n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[int]] = None,
                 stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
                 family_chains: Optional[int] = None, summary: bool = False, keep_samples: bool = True, adapt_metric: bool = False,
-                theta_support=None, theta_prior=None, sigma_sq_prior=None):
+                theta_support=None, theta_prior=None, sigma_sq_prior=None, obs_link=None, obs_weight=None):
         """magi_v2.py:286-425.  Returns the reference's results dictionary; with n_chains > 1 every
         sample array gains a leading chain axis.  ``family_chains``: in a job sharded over GPUs, the largest per-GPU share
         (shard.family_chains_for) -- every rank then samples with the same kernel family whatever its own share.
@@ -374,10 +374,18 @@ class MAGI_v2:
         and for a noise variance also ("fixed", c): that sigma^2 is the known constant c, ``sigma_sqs_samps`` and the summaries report c, and
         its ``pre`` coordinate (started at 0) is an independent standard normal.  lognormal, gamma and invgamma on a parameter need a support
         inside (0, inf).  ``results["theta_prior"]`` / ``results["sigma_sq_prior"]`` echo the normalised specifications when given.
+        ``obs_link`` / ``obs_weight`` (the reference observes y = x + N(0, sigma^2_d), and None keeps that): ``obs_link`` is one of "identity",
+        "log" (multiplicative error; data > 0), "sqrt" (counts; data >= 0) for all components or one per component -- Gaussian error on
+        g(y), sigma^2 the variance on that scale; ``obs_weight`` is shaped like the observed data on the grid, [n_points, D], a known weight
+        > 0 per observation (the mean of n replicates: n; entries at unobserved positions are ignored).  ``X_samps``, the summaries and
+        ``posterior_trajectories`` stay on the natural scale.  For a linked component the default ``sigma_sqs_LB`` is (0.01 std(g(y_d)))^2 and
+        the chain starts from a sigma^2 on the link's scale (host.link_sigma_defaults); an explicit ``sigma_sqs_LB`` is taken as given.
+        ``Xhat_init`` outside a link's domain at an observed point raises ValueError.  ``results["obs_link"]`` / ``results["obs_weight"]`` echo
+        the normalised specification when given.
         Many datasets on one GPU: ``predict_many``."""
         if not keep_samples and not summary:
             raise ValueError("keep_samples=False needs summary=True: the call would return nothing of the posterior")
-        sigma_sqs_LB, sig_pre0, th_pre0 = self._predict_prepare(sigma_sqs_LB, family_chains, theta_support, theta_prior, sigma_sq_prior)
+        sigma_sqs_LB, sig_pre0, th_pre0 = self._predict_prepare(sigma_sqs_LB, family_chains, theta_support, theta_prior, sigma_sq_prior, obs_link, obs_weight)
         eng = self.engine
         if seed is None:                 # the reference calls sample_chain unseeded (magi_v2.py:389-395)
             seed = _fresh_seed()
@@ -418,16 +426,27 @@ class MAGI_v2:
             raise RuntimeError("posterior_summary summarises the samples of the last predict: run predict first")
         return self.engine.sampler_summary(probs=probs, max_lag=max_lag)
 
-    def _predict_prepare(self, sigma_sqs_LB, family_chains=None, theta_support=None, theta_prior=None, sigma_sq_prior=None):
-        """predict's set-up up to the sampler: matrices on the device, the problem, the parameters' supports and then the priors set;
-        returns (sigma_sqs_LB, sig_pre0, th_pre0)."""
+    def _predict_prepare(self, sigma_sqs_LB, family_chains=None, theta_support=None, theta_prior=None, sigma_sq_prior=None,
+                         obs_link=None, obs_weight=None):
+        """predict's set-up up to the sampler: matrices on the device, the problem, the parameters' supports, the priors and then the
+        observation model set; returns (sigma_sqs_LB, sig_pre0, th_pre0)."""
         assert ~np.any(np.isnan(self.Xhat_init)), "Please make sure Xhat_init does not have NaNs."
         assert ~np.any(np.isnan(self.sigma_sqs_init)), "Please make sure sigma_sqs_init does not have NaNs."
         assert ~np.any(np.isnan(self.thetas_init)), "Please make sure thetas_init does not have NaNs."
 
+        LB_given = sigma_sqs_LB is not None
         if sigma_sqs_LB is None:
             sigma_sqs_LB = host.sigma_sqs_lower_bound(self.Xhat_init)
         sigma_sqs_LB = np.asarray(sigma_sqs_LB, dtype=np.float64)
+        sigma_sqs_start = np.asarray(self.sigma_sqs_init, dtype=np.float64)
+        self._obs_link = self._obs_weight = None
+        if obs_link is not None or obs_weight is not None:          # (checked before the engine is touched)
+            Xg = np.asarray(self.X_obs_discret, dtype=np.float64)
+            self._obs_link = host.obs_model_spec(obs_link, Xg.shape[1])
+            self._obs_weight = host.obs_weight_grid(obs_weight, Xg)
+            host.link_start_check(self._obs_link, Xg, self.Xhat_init)
+            sigma_sqs_LB, sigma_sqs_start = host.link_sigma_defaults(self._obs_link, Xg, self.Xhat_init, self._obs_weight, sigma_sqs_LB,
+                                                                     sigma_sqs_start, LB_given)
         eng = self.engine
         self._sync_matrices()
         if family_chains is not None:
@@ -436,8 +455,7 @@ class MAGI_v2:
             eng.set_times(self.I)
         eng.set_problem(self.mu_ds, self.N_ds.astype(np.float64), np.asarray(self.not_nan_idxs),
                         np.asarray(self.y_tau_ds_observed), float(self.beta), sigma_sqs_LB, self.drift)
-        sig_pre0, th_pre0 = host.softplus_inverse_inits(np.asarray(self.sigma_sqs_init, dtype=np.float64),
-                                                        np.asarray(self.thetas_init, dtype=np.float64), sigma_sqs_LB)
+        sig_pre0, th_pre0 = host.softplus_inverse_inits(sigma_sqs_start, np.asarray(self.thetas_init, dtype=np.float64), sigma_sqs_LB)
         self._theta_support = None                   # (set_problem has reset the engine's supports to all-positive)
         if theta_support is not None:
             self._theta_support = host.theta_support(theta_support, self.drift.P)
@@ -451,6 +469,9 @@ class MAGI_v2:
                 self._sigma_sq_prior = host.prior_spec(sigma_sq_prior, len(sig_pre0), "sigma_sq")
                 sig_pre0 = np.where(self._sigma_sq_prior[0] == host.PRIOR_FIXED, 0.0, sig_pre0)      # (a fixed variance: pre ~ N(0, 1), started at 0)
             eng.set_prior(sigma_sq_prior, theta_prior)
+        if self._obs_link is not None:               # (set_problem has reset the engine's observation model to the reference's)
+            w = None if self._obs_weight is None else self._obs_weight.reshape(-1)[np.asarray(self.not_nan_idxs)]
+            eng.set_obs_model(None if obs_link is None else self._obs_link, w)
         return sigma_sqs_LB, sig_pre0, th_pre0
 
     def _predict_results(self, X_samps, sig_pre, th_pre, diag, sigma_sqs_LB, seed, n_chains, num_burnin_steps, minutes):
@@ -472,6 +493,10 @@ class MAGI_v2:
             extra["theta_prior"] = host.prior_spec_echo(*th_prior)
         if sig_prior is not None:
             extra["sigma_sq_prior"] = host.prior_spec_echo(*sig_prior)
+        if getattr(self, "_obs_link", None) is not None:
+            extra["obs_link"] = host.obs_model_spec_echo(self._obs_link)
+            if self._obs_weight is not None:
+                extra["obs_weight"] = self._obs_weight
         return {**extra, "phi1s": self.phi1s, "phi2s": self.phi2s,
                 "Xhat_init": self.Xhat_init,
                 "sigma_sqs_init": self.sigma_sqs_init,
@@ -564,7 +589,8 @@ def partition_for_groups(keys):
 def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_steps: int = 1000, sigma_sqs_LB=None, verbose=False, *,
                  n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[Sequence[int]]] = None,
                  stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
-                 summary: bool = False, keep_samples: bool = True, theta_support=None, theta_prior=None, sigma_sq_prior=None):
+                 summary: bool = False, keep_samples: bool = True, theta_support=None, theta_prior=None, sigma_sq_prior=None,
+                 obs_link=None, obs_weight=None):
     """``predict`` for several models (after their ``initial_fit``) at once.  Models of one library, device and problem shape are sampled
     as one problem group on their GPU -- one captured graph, one kernel pair per leapfrog slot for all their chains -- and the others by
     their own ``predict``.  ``sigma_sqs_LB``: None (each model's default) or one entry per model; ``chain_ids``: None (0 .. n_chains - 1
@@ -573,7 +599,9 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
     ``summary`` / ``keep_samples`` as in ``predict``: a grouped model's summary pools that model's chains alone.  ``theta_support``: None, one
     specification for all models (entries "positive", "real", ("lower", lo), ("upper", hi), as in ``predict``) or one per model (each None
     or such a specification); the members of one group may differ.  ``theta_prior`` / ``sigma_sq_prior``: likewise None, one specification
-    for all models (entries None, "flat", ("normal", m, s), ... as in ``predict``) or one per model."""
+    for all models (entries None, "flat", ("normal", m, s), ... as in ``predict``) or one per model.  ``obs_link`` / ``obs_weight``: likewise
+    None, one specification for all models (a link name, or one name per component; one weight array) or one per model (a list of such
+    specifications / of arrays or None); the members of one group may differ."""
     if not keep_samples and not summary:
         raise ValueError("keep_samples=False needs summary=True: the call would return nothing of the posterior")
     models = list(models)
@@ -597,18 +625,25 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
             return [list(spec)] * n
         return list(spec)
     tpri, spri = per_model(theta_prior), per_model(sigma_sq_prior)
-    if len(lbs) != n or len(ids) != n or len(sups) != n or len(tpri) != n or len(spri) != n:
-        raise ValueError("sigma_sqs_LB, chain_ids and per-model theta_support, theta_prior and sigma_sq_prior take one entry per model")
+    # one link specification for all models: a name, or a sequence of names / None / codes; one per model: a list whose entries are such specifications
+    one_link = lambda e: e is None or isinstance(e, (str, int, np.integer))
+    if obs_link is None or isinstance(obs_link, str) or (len(obs_link) > 0 and all(one_link(e) for e in obs_link) and not all(e is None for e in obs_link)):
+        olnk = [obs_link] * n
+    else:
+        olnk = list(obs_link)
+    owts = [obs_weight] * n if obs_weight is None or isinstance(obs_weight, np.ndarray) else list(obs_weight)      # (one array for all, or a list with one array or None per model)
+    if len(lbs) != n or len(ids) != n or len(sups) != n or len(tpri) != n or len(spri) != n or len(olnk) != n or len(owts) != n:
+        raise ValueError("sigma_sqs_LB, chain_ids and per-model theta_support, theta_prior, sigma_sq_prior, obs_link and obs_weight take one entry per model")
     if seed is None:
         seed = _fresh_seed()
     kw = dict(n_chains=n_chains, seed=seed, stale_cache=stale_cache, anneal=anneal, max_tree_depth=max_tree_depth, step_size=step_size)
-    prep = [m._predict_prepare(lb, None, sp, tp, sq) for m, lb, sp, tp, sq in zip(models, lbs, sups, tpri, spri)]
+    prep = [m._predict_prepare(lb, None, sp, tp, sq, ol, ow) for m, lb, sp, tp, sq, ol, ow in zip(models, lbs, sups, tpri, spri, olnk, owts)]
     out = [None] * n
     for grp in partition_for_groups([group_key(m, n_chains) for m in models]):
         if len(grp) == 1:
             k = grp[0]
             out[k] = models[k].predict(num_results, num_burnin_steps, lbs[k], verbose, chain_ids=ids[k], summary=summary, keep_samples=keep_samples,
-                                        theta_support=sups[k], theta_prior=tpri[k], sigma_sq_prior=spri[k], **kw)
+                                        theta_support=sups[k], theta_prior=tpri[k], sigma_sq_prior=spri[k], obs_link=olnk[k], obs_weight=owts[k], **kw)
             continue
         g = MagiGroup([models[k].engine for k in grp])
         try:

@@ -34,6 +34,8 @@ void free_dev(void* p) { if (p) (void)hipFree(p); }
 
 void free_matrices(magi_handle* h) {
     free_dev(h->dCsym); free_dev(h->dM); free_dev(h->dMt); free_dev(h->dKsym); free_dev(h->dYobs);
+    free_dev(h->dObsw);
+    h->dObsw = nullptr; h->pb.obsw = nullptr; h->pb.obs_links = 0;
     free_dev(h->dTimes);
     h->dTimes = nullptr; h->times_N = 0; h->times_cap = 0; h->pb.tgrid = nullptr;
     free_dev(h->dTiles); free_dev(h->dTasks);
@@ -365,6 +367,8 @@ int magi_group_create(magi_handle* const* members, int n_members, magi_handle** 
     g->pb.tsup = nullptr;                          // (every member brings its own supports)
     g->pb.prior = nullptr;                         // (and its own priors)
     g->pb.fixed_mask = 0;
+    g->pb.obs_links = 0;                           // (and its own observation model)
+    g->pb.obsw = nullptr;
     hipError_t e = hipMalloc(&g->d_members, sizeof(DevProblem) * n_members);
     if (e != hipSuccess) {
         magi_destroy(g);
@@ -534,14 +538,24 @@ int magi_set_problem(magi_handle* h, const double* mu, const double* N_ds, const
     (void)hipSetDevice(h->device);
     const int N = pb.N, D = pb.D;
     std::vector<double> yobs((size_t)N * D, std::nan(""));
+    std::vector<int64_t> obs_e((size_t)n_obs);
     for (int64_t k = 0; k < n_obs; ++k) {
         const int64_t idx = obs_idx[k];
         if (idx < 0 || idx >= (int64_t)N * D) return magi_fail(h, MAGI_E_BADARG, "obs_idx out of range");
         const int i = (int)(idx / D), d = (int)(idx % D);          // flat row-major index into X[N][D]
         yobs[(size_t)d * N + i] = y[k];
+        obs_e[(size_t)k] = (int64_t)d * N + i;
     }
     free_dev(h->dYobs);
     h->dYobs = nullptr;
+    free_dev(h->dObsw);                                            // (a new problem: identity links, no weights; the data kept for magi_set_obs_model)
+    h->dObsw = nullptr;
+    pb.obsw = nullptr;
+    pb.obs_links = 0;
+    for (int d = 0; d < MAGI_MAX_D; ++d) h->ob_link[d] = MAGI_LINK_IDENTITY;
+    h->obs_w.clear();
+    h->obs_e.swap(obs_e);
+    h->obs_y.assign(y, y + n_obs);
     MAGI_HIP_CHECK(h, hipMalloc(&h->dYobs, sizeof(double) * N * D));
     MAGI_HIP_CHECK(h, hipMemcpy(h->dYobs, yobs.data(), sizeof(double) * N * D, hipMemcpyHostToDevice));
     pb.yobs = h->dYobs;
@@ -712,6 +726,63 @@ int magi_get_prior(magi_handle* h, int n, int* kind, double* a, double* b) {
         if (a) a[e] = h->pr_a[e];
         if (b) b[e] = h->pr_b[e];
     }
+    return MAGI_OK;
+}
+
+int magi_set_obs_model(magi_handle* h, int D, const int* link, int64_t n_obs, const double* weight) {
+    if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_set_obs_model");
+    if (!h->have_problem) return magi_fail(h, MAGI_E_STATE, "magi_set_obs_model: set the problem first (magi_set_problem resets the observation model)");
+    const int N = h->pb.N;
+    if (D != h->pb.D) return magi_fail(h, MAGI_E_BADARG, "magi_set_obs_model: D = " + std::to_string(D) + ", the problem has " + std::to_string(h->pb.D) + " components");
+    if (n_obs != (int64_t)h->obs_e.size())
+        return magi_fail(h, MAGI_E_BADARG, "magi_set_obs_model: n_obs = " + std::to_string(n_obs) + ", magi_set_problem was given " + std::to_string(h->obs_e.size()) + " observations");
+    int lk[MAGI_MAX_D] = {};
+    int links = 0;
+    for (int d = 0; link && d < D; ++d) {
+        if (link[d] < MAGI_LINK_IDENTITY || link[d] > MAGI_LINK_SQRT)
+            return magi_fail(h, MAGI_E_BADARG, "magi_set_obs_model: link[" + std::to_string(d) + "] = " + std::to_string(link[d]) + " is none of MAGI_LINK_*");
+        lk[d] = link[d];
+        links |= link[d] << (2 * d);
+    }
+    for (int64_t k = 0; weight && k < n_obs; ++k)
+        if (!std::isfinite(weight[k]) || !(weight[k] > 0.0))
+            return magi_fail(h, MAGI_E_BADARG, "magi_set_obs_model: weight[" + std::to_string(k) + "] is not a finite number > 0");
+    // g_d(y) laid out like yobs; observations given twice: the last one counts, as in magi_set_problem
+    std::vector<double> gy((size_t)N * D, std::nan("")), w;
+    if (weight) w.assign((size_t)N * D, 1.0);
+    for (int64_t k = 0; k < n_obs; ++k) {
+        const int64_t e = h->obs_e[(size_t)k];
+        const int d = (int)(e / N);
+        const double y = h->obs_y[(size_t)k];
+        if (!std::isnan(y) && ((lk[d] == MAGI_LINK_LOG && !(y > 0.0)) || (lk[d] == MAGI_LINK_SQRT && !(y >= 0.0))))
+            return magi_fail(h, MAGI_E_BADARG, "magi_set_obs_model: observation " + std::to_string(k) + " of component " + std::to_string(d) + " is outside the domain of its link (log: y > 0, sqrt: y >= 0)");
+        gy[(size_t)e] = lk[d] == MAGI_LINK_LOG ? std::log(y) : lk[d] == MAGI_LINK_SQRT ? std::sqrt(y) : y;
+        if (weight) w[(size_t)e] = weight[k];
+    }
+    (void)hipSetDevice(h->device);
+    if (h->stream) MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // (nothing in flight reads the old data)
+    if (weight && !h->dObsw) MAGI_HIP_CHECK(h, hipMalloc(&h->dObsw, sizeof(double) * N * D));
+    if (weight) MAGI_HIP_CHECK(h, hipMemcpy(h->dObsw, w.data(), sizeof(double) * N * D, hipMemcpyHostToDevice));
+    MAGI_HIP_CHECK(h, hipMemcpy(h->dYobs, gy.data(), sizeof(double) * N * D, hipMemcpyHostToDevice));
+    h->sampler_ready = false;
+    drop_graph(h);                                                           // (the problem is a kernel argument of the captured graph)
+    for (int d = 0; d < MAGI_MAX_D; ++d) h->ob_link[d] = lk[d];
+    if (weight) h->obs_w.assign(weight, weight + n_obs); else h->obs_w.clear();
+    h->pb.obs_links = links;                                                 // all identity and no weights: the kernels' default path
+    h->pb.obsw = weight ? h->dObsw : nullptr;
+    return MAGI_OK;
+}
+
+int magi_get_obs_model(magi_handle* h, int D, int* link, int64_t n_obs, double* weight) {
+    if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_get_obs_model");
+    if (!h->have_problem) return magi_fail(h, MAGI_E_STATE, "magi_get_obs_model: set the problem first");
+    if (D != h->pb.D) return magi_fail(h, MAGI_E_BADARG, "magi_get_obs_model: D = " + std::to_string(D) + ", the problem has " + std::to_string(h->pb.D) + " components");
+    if (n_obs != (int64_t)h->obs_e.size())
+        return magi_fail(h, MAGI_E_BADARG, "magi_get_obs_model: n_obs = " + std::to_string(n_obs) + ", magi_set_problem was given " + std::to_string(h->obs_e.size()) + " observations");
+    for (int d = 0; link && d < D; ++d) link[d] = h->ob_link[d];
+    for (int64_t k = 0; weight && k < n_obs; ++k) weight[k] = h->obs_w.empty() ? 1.0 : h->obs_w[(size_t)k];
     return MAGI_OK;
 }
 
@@ -1105,6 +1176,11 @@ static double ckpt_tag(const magi_handle* h, long long chain_id) {
     if (h->pb.tsup) { mix(h->th_kind, sizeof(int) * h->pb.P); mix(h->th_bound, sizeof(double) * h->pb.P); }
     // (likewise the priors, when any is set)
     if (h->pb.prior) { const int n = h->pb.D + h->pb.P; mix(h->pr_kind, sizeof(int) * n); mix(h->pr_a, sizeof(double) * n); mix(h->pr_b, sizeof(double) * n); }
+    // (and the observation model, when one is set)
+    if (h->pb.obs_links || h->pb.obsw) {
+        mix(h->ob_link, sizeof(int) * h->pb.D);
+        if (!h->obs_w.empty()) mix(h->obs_w.data(), sizeof(double) * h->obs_w.size());
+    }
     return (double)(x & ((1ull << 52) - 1));
 }
 
@@ -1146,7 +1222,7 @@ int magi_sampler_set_checkpoint(magi_handle* h, const double* scalars) {
             !std::isfinite(o[CKPT_LOG_SHRINK]) || !(o[CKPT_BETA_CACHE] > 0.0) || !(o[CKPT_BETA_CACHE] <= 1.4426950408889636))      // (the schedule starts at 1 / ln 2, magi_v2.py:833-835)
             return magi_fail(h, MAGI_E_BADARG, who + ": non-finite dual-averaging state, step size <= 0 or cached temperature outside (0, 1 / ln 2]");
         if (o[CKPT_TAG] != ckpt_tag(h, ctl[c].chain_id))
-            return magi_fail(h, MAGI_E_BADARG, who + " was taken under another sampler configuration, seed, chain id, problem size, parameter support or prior: a resume continues "
+            return magi_fail(h, MAGI_E_BADARG, who + " was taken under another sampler configuration, seed, chain id, problem size, parameter support, prior or observation model: a resume continues "
                                                "the SAME run (magi_hip.h)");
         ctl[c].k = (int)o[CKPT_K]; ctl[c].da_step = (int)o[CKPT_DA_STEP]; ctl[c].da_step_size = o[CKPT_STEP_SIZE];
         ctl[c].da_error_sum = o[CKPT_ERR_SUM]; ctl[c].da_log_avg = o[CKPT_LOG_AVG]; ctl[c].da_log_shrink = o[CKPT_LOG_SHRINK];

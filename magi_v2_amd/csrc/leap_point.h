@@ -85,9 +85,15 @@ struct GridPoint {     // component d of grid index i of one chain (one lane)
         }
         double d4 = 0.0;
         if (!isnan(o.y)) {
-            const double df = xd - o.y;
-            pk[PK_SS + d] = df * df;
-            d4 = 2.0 * df / o.sig2;
+            if (ObsModel::set(pb)) {      // (observation model: wave-uniform; the weight is loaded here, on the opt-in path alone)
+                double dss;
+                pk[PK_SS + d] = ObsModel::resid(pb, d, (size_t)e, xd, o.y, dss);
+                d4 = dss / o.sig2;
+            } else {
+                const double df = xd - o.y;
+                pk[PK_SS + d] = df * df;
+                d4 = 2.0 * df / o.sig2;
+            }
         }
         const double gx = -0.5 * (pb.beta_inv * (2.0 * hx - 2.0 * etf + jtd) + d4);
         *(vb + (size_t)V_G * dimp + e) = gx;
@@ -295,9 +301,15 @@ __device__ __forceinline__ void point_block_sep(const DevProblem& pb, const DevC
             }
             double d4 = 0.0;
             if (!isnan(ops.y)) {
-                const double df = xd - ops.y;
-                pk[PK_SS + d] = df * df;
-                d4 = 2.0 * df / ops.sig2;
+                if (ObsModel::set(pb)) {      // (observation model, as GridPoint::finish)
+                    double dss;
+                    pk[PK_SS + d] = ObsModel::resid(pb, d, (size_t)e, xd, ops.y, dss);
+                    d4 = dss / ops.sig2;
+                } else {
+                    const double df = xd - ops.y;
+                    pk[PK_SS + d] = df * df;
+                    d4 = 2.0 * df / ops.sig2;
+                }
             }
             const double gx = -0.5 * (pb.beta_inv * (2.0 * hx - 2.0 * etf + jtd) + d4);
             *(vb + (size_t)V_G * dimp + e) = gx;

@@ -52,7 +52,8 @@ __device__ inline void row_epilogue(const DevProblem& pb, double* vb, const doub
         const double y = pb.yobs[e];
         double d4 = 0.0;
         if (!isnan(y)) {
-            d4 = 2.0 * (q[e] - y) / par[PAR_SIG2 + d];
+            if (ObsModel::set(pb)) { double dss; (void)ObsModel::resid(pb, d, e, q[e], y, dss); d4 = dss / par[PAR_SIG2 + d]; }      // (observation model: wave-uniform)
+            else d4 = 2.0 * (q[e] - y) / par[PAR_SIG2 + d];
         }
         vb[(size_t)V_G * dimp + e] = -0.5 * (pb.beta_inv * d12 + d4);
     }

@@ -80,6 +80,11 @@ struct DevProblem {
     int fixed_mask;        // bit j: sigma^2_j is fixed (MAGI_PRIOR_FIXED) at LB[j], which then holds the constant itself; 0 without one.  A scalar of
                            // the problem and no table look-up: compute_par_entry also runs in the point kernel's boundary pass, where a load
                            // and a second mask cost the point kernel of a traced drift 48 B of scratch
+    int obs_links;         // link g_d of component d's observations in bits 2d, 2d + 1 (magi_set_obs_model; ObsModel below): 0 identity, 1 log, 2 sqrt.
+                           // A packed scalar for the reason fixed_mask is one: a per-lane d selects by a shift, not from a kernel-argument array
+    const double* obsw;    // [D][N] known weight of every observation, laid out like yobs (1 where none was given, and at unobserved entries);
+                           // nullptr: every weight is 1.  With obs_links == 0 and no weights the kernels run the instructions they ran without a model;
+                           // otherwise yobs holds g_d(y)
 };
 
 // Support of one parameter entry, as a table entry (x, y) = (sign, bound):
@@ -388,6 +393,30 @@ __device__ inline double Prior::dlogp(const double4& e, double v) {
     return 0.0;
 }
 __device__ inline double sigmoid(double x) { return 1.0 / (1.0 + m_exp(-x)); }
+
+// Observation model: component d is observed through a link g_d -- identity, log or sqrt -- with Gaussian error of variance
+// sigma^2_d on the LINK's scale, and observation k may carry a known weight w_k (a mean of n replicates counts n times):
+//     t4 = sum_d (1 / sigma^2_d) sum_{k in obs_d} w_k (g_d(x_k) - g_d(y_k))^2
+// The component still contributes ONE sum ss_d, so t3, t4, the sigma^2 gradient and the reduce are what they were; only the four places that
+// form a point's squared residual and its x-derivative change (GridPoint::finish, point_block_sep, row_epilogue<3>, finalize_gradient), and
+// they share this one statement of it.  yobs holds g_d(y) (transformed once, by magi_set_obs_model).  The link is evaluated at OBSERVED
+// points only: outside its domain there (x <= 0 under log, x < 0 under sqrt) the residual is not finite, and so is the log posterior of
+// that state -- the rule of a state outside a drift's domain.  `set` is wave-uniform; while it is false the callers run their old instructions.
+struct ObsModel {
+    enum { IDENTITY = 0, LOG = 1, SQRT = 2 };
+    static __device__ __forceinline__ bool set(const DevProblem& pb) { return (pb.obs_links != 0) | (pb.obsw != nullptr); }
+    // w (g(x) - gy)^2 of the observed entry e = d N + i, and `dss` = its x-derivative 2 w (g(x) - gy) g'(x); gy = g_d(y) as yobs holds it
+    static __device__ __forceinline__ double resid(const DevProblem& pb, int d, size_t e, double x, double gy, double& dss) {
+        const int link = (pb.obs_links >> (2 * d)) & 3;
+        double gx = x, dg = 1.0;
+        if (link == LOG) { gx = m_log(x); dg = 1.0 / x; }
+        else if (link == SQRT) { gx = sqrt(x); dg = 0.5 / gx; }
+        const double w = pb.obsw ? pb.obsw[e] : 1.0;
+        const double df = gx - gy, wdf = w * df;
+        dss = (2.0 * wdf) * dg;
+        return wdf * df;
+    }
+};
 
 __device__ inline double logaddexp(double a, double b) {
     if (a == -INFINITY && b == -INFINITY) return -INFINITY;
@@ -932,7 +961,10 @@ __device__ inline FinalizeOut finalize_gradient(const DevProblem& pb, double* vb
                 t2s = fma(r[idx], kr, t2s);
                 g2[d] = 2.0 * kr;
                 const double y = pb.yobs[idx];
-                if (!isnan(y)) { const double df = xv - y; ss[d] = fma(df, df, ss[d]); }
+                if (!isnan(y)) {
+                    if (ObsModel::set(pb)) { double dss; ss[d] += ObsModel::resid(pb, d, (size_t)idx, xv, y, dss); }      // (observation model: wave-uniform)
+                    else { const double df = xv - y; ss[d] = fma(df, df, ss[d]); }
+                }
             } else { x[d] = 0.0; g2[d] = 0.0; }
         }
         drift_tt_g_acc(pb.drift, x, th, g2, tp, point_time_rt(pb, i));
@@ -1052,6 +1084,13 @@ struct magi_handle {
     double pr_a[MAGI_MAX_D + MAGI_MAX_P] = {}, pr_b[MAGI_MAX_D + MAGI_MAX_P] = {};
     double4* dPrior = nullptr;
     double lb_orig[MAGI_MAX_D] = {};  // LB as magi_set_problem gave it (pb.LB holds the constant of a fixed sigma^2 instead)
+    // observation model (magi_set_obs_model): the data as magi_set_problem gave them -- entry d N + i and UNtransformed value of observation k,
+    // so that the model can be changed or reset without a new magi_set_problem -- the links, the weights (empty: none given) and the device
+    // copy of the weights pb.obsw points at while any was given ([D][N] like dYobs; allocated on first use, freed with dYobs)
+    std::vector<int64_t> obs_e;
+    std::vector<double> obs_y, obs_w;
+    int ob_link[MAGI_MAX_D] = {};
+    double* dObsw = nullptr;
     size_t mat_elems = 0;
     // dense C^-1, m, K^-1 ([D][N][N], unmasked) as built or uploaded: authoritative until the caller uploads others; packed
     // (band mask, symmetrised / transposed copies, single-phase operator blocks) by magi_pack_matrices

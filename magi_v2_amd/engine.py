@@ -12,7 +12,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .host import prior_spec, theta_support
+from .host import obs_model_spec, prior_spec, theta_support
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmagi_hip.so")
@@ -63,6 +63,8 @@ _SYMBOLS = {
     "magi_get_theta_support": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp]),
     "magi_set_prior": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp]),
     "magi_get_prior": (C.c_int, [C.c_void_p, C.c_int, _ip, _dp, _dp]),
+    "magi_set_obs_model": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_int64, _dp]),
+    "magi_get_obs_model": (C.c_int, [C.c_void_p, C.c_int, _ip, C.c_int64, _dp]),
     "magi_logpost_grad": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "magi_logpost_grad_fused": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, C.c_double, _dp, _dp, _dp, _dp, _dp]),
     "magi_sampler_cfg_default": (None, [C.POINTER(SamplerCfg)]),
@@ -185,6 +187,7 @@ class MagiEngine:
         self.n_chains = 0
         self._cfg = None
         self._problem_drift = None
+        self._n_obs = 0
 
     # -- plumbing -------------------------------------------------------------------------------
     def close(self):
@@ -444,6 +447,7 @@ class MagiEngine:
         self._check(self._lib.magi_set_problem(self._h, _ptr(mu), _ptr(N_ds), obs_idx.ctypes.data_as(_lp), _ptr(y),
                                                obs_idx.shape[0], float(beta), _ptr(LB), drift_id, P))
         self.P = P
+        self._n_obs = int(obs_idx.shape[0])
         self._problem_drift = drift
 
     def set_theta_support(self, spec):
@@ -488,6 +492,28 @@ class MagiEngine:
         kinds, a, b = np.zeros(n, dtype=np.int32), np.zeros(n), np.zeros(n)
         self._check(self._lib.magi_get_prior(self._h, n, kinds.ctypes.data_as(_ip), _ptr(a), _ptr(b)))
         return (kinds[:D], a[:D], b[:D]), (kinds[D:], a[D:], b[D:])
+
+    def set_obs_model(self, link=None, weight=None):
+        """The observation model (magi_set_obs_model), after ``set_problem`` -- which resets it to the reference's: ``link`` None, one of
+        "identity", "log", "sqrt" for all components or one per component (host.obs_model_spec); ``weight`` None or one known weight > 0 per
+        observation, in the order of ``set_problem``'s ``obs_idx``.  Gaussian error on the link's scale, sigma^2 the variance there:
+        t4 = sum_d (1 / sigma^2_d) sum_k w_k (g_d(x_k) - g_d(y_k))^2.  It governs ``logpost_grad`` and the next ``sampler_init``; samples and
+        summaries stay on the natural scale.  Both None: back to the default."""
+        if self.P is None:
+            raise MagiHipError(-5, "set_obs_model: set the problem first (magi_set_problem)")
+        links = np.ascontiguousarray(obs_model_spec(link, self.D), dtype=np.int32)
+        w = None if weight is None else _f64(np.asarray(weight, dtype=np.float64).reshape(-1))
+        n_obs = self._n_obs if w is None else int(w.shape[0])
+        self._check(self._lib.magi_set_obs_model(self._h, int(self.D), None if link is None else links.ctypes.data_as(_ip), n_obs, None if w is None else _ptr(w)))
+
+    def obs_model(self):
+        """The observation model in force as (links int32[D], weights float64[n_obs]) (magi_get_obs_model; host.obs_model_spec_echo names
+        the links; the weights are 1 when none were given)."""
+        if self.P is None:
+            raise MagiHipError(-5, "obs_model: set the problem first (magi_set_problem)")
+        links, w = np.zeros(self.D, dtype=np.int32), np.ones(self._n_obs)
+        self._check(self._lib.magi_get_obs_model(self._h, int(self.D), links.ctypes.data_as(_ip), self._n_obs, _ptr(w)))
+        return links, w
 
     def _states(self, X, sig_pre, th_pre):
         X = _f64(X)
@@ -733,5 +759,6 @@ class MagiGroup(MagiEngine):
             raise MagiHipError(rc, lib.magi_last_error(None).decode())
         self._h = out.value
         self.N, self.D, self.P = engines[0].N, engines[0].D, engines[0].P
+        self._n_obs = engines[0]._n_obs
         self.n_chains = 0
         self._cfg = None

@@ -243,6 +243,108 @@ def prior_spec_echo(kinds, a, b):
             for k, x, y in zip(kinds, a, b)]
 
 
+# observation model (include/magi_hip.h: magi_set_obs_model).  The codes are the header's MAGI_LINK_*.
+LINK_IDENTITY, LINK_LOG, LINK_SQRT = 0, 1, 2
+_LINK_NAMES = {"identity": LINK_IDENTITY, "log": LINK_LOG, "sqrt": LINK_SQRT}
+
+
+def obs_model_spec(link, D: int):
+    """Normalises a link specification into codes int32[D]: None (every link the identity, the reference's model), one of "identity",
+    "log", "sqrt" for all D components, or one such name (or None, or a LINK_* code) per component.  Anything else raises ValueError."""
+    D = int(D)
+    links = np.zeros(D, dtype=np.int32)
+    if link is None:
+        return links
+    if isinstance(link, str):
+        link = [link] * D
+    if isinstance(link, bytes) or not hasattr(link, "__len__"):
+        raise ValueError(f"obs_link: expected None, a link name or a sequence of {D} entries, got {link!r}")
+    if len(link) != D:
+        raise ValueError(f"obs_link: {len(link)} entries for {D} components")
+    for d, e in enumerate(link):
+        if e is None:
+            continue
+        if isinstance(e, str) and e in _LINK_NAMES:
+            links[d] = _LINK_NAMES[e]
+        elif isinstance(e, (int, np.integer)) and not isinstance(e, bool) and int(e) in _LINK_NAMES.values():
+            links[d] = int(e)
+        else:
+            raise ValueError(f"obs_link[{d}]: {e!r} is none of None, 'identity', 'log', 'sqrt'")
+    return links
+
+
+def obs_model_spec_echo(links):
+    """The normalised specification (a list of "identity" / "log" / "sqrt") of link codes."""
+    names = {v: k for k, v in _LINK_NAMES.items()}
+    return [names[int(k)] for k in links]
+
+
+def link_apply(link: int, v):
+    """g(v) of one link code, elementwise (NaN outside the link's domain; -inf for log 0)."""
+    v = np.asarray(v, dtype=np.float64)
+    with np.errstate(invalid="ignore", divide="ignore"):
+        return np.log(v) if int(link) == LINK_LOG else np.sqrt(v) if int(link) == LINK_SQRT else v.copy()
+
+
+def link_domain(link: int, v):
+    """Whether v lies in the domain of the link: log v > 0, sqrt v >= 0, identity anything finite or not."""
+    v = np.asarray(v, dtype=np.float64)
+    return v > 0.0 if int(link) == LINK_LOG else v >= 0.0 if int(link) == LINK_SQRT else np.ones(v.shape, dtype=bool)
+
+
+def obs_weight_grid(obs_weight, X_grid: np.ndarray):
+    """``obs_weight`` (shaped like the observed data on the grid, [n_points, D]) as float64 with 1 at unobserved positions, whose entries
+    are ignored; every weight at an observed position must be finite and > 0.  None stays None."""
+    if obs_weight is None:
+        return None
+    w = np.asarray(obs_weight, dtype=np.float64)
+    if w.shape != X_grid.shape:
+        raise ValueError(f"obs_weight: shape {w.shape}, the observed data on the grid have shape {X_grid.shape}")
+    seen = ~np.isnan(X_grid)
+    if not np.all(np.isfinite(w[seen]) & (w[seen] > 0.0)):
+        raise ValueError("obs_weight: every weight of an observed point must be a finite number > 0")
+    return np.where(seen, w, 1.0)
+
+
+def link_start_check(links, X_grid: np.ndarray, Xhat_init: np.ndarray):
+    """Raises ValueError when the data or the start state leave a link's domain at an observed point: a chain started there starts at NaN."""
+    for d, k in enumerate(links):
+        seen = ~np.isnan(X_grid[:, d])
+        bad_y = int((~link_domain(k, X_grid[seen, d])).sum())
+        if bad_y:
+            raise ValueError(f"obs_link: component {d} has {bad_y} observation(s) outside the domain of its {obs_model_spec_echo([k])[0]} link")
+        bad = int((~link_domain(k, np.asarray(Xhat_init)[seen, d])).sum())
+        if bad:
+            raise ValueError(f"obs_link: Xhat_init of component {d} is outside the domain of its {obs_model_spec_echo([k])[0]} link at {bad} observed point(s): "
+                             "the chain would start at a non-finite log posterior")
+
+
+def link_sigma_defaults(links, X_grid: np.ndarray, Xhat_init: np.ndarray, weight_grid, LB, sigma_sqs_init, LB_given: bool):
+    """sigma^2 lives on the link's scale, where the natural-scale defaults are wrong by orders of magnitude.  For every component with a link
+    other than the identity: the lower bound becomes (0.01 std(g(y_d)))^2 unless ``LB_given``, and the starting value the weighted mean square
+    of g(Xhat_init) - g(y) over the observed points where Xhat_init lies in the link's domain -- or (0.1 std(g(y_d)))^2 when fewer than two
+    such points exist or the mean square is not above the bound.  Identity components keep ``LB`` and ``sigma_sqs_init``.
+    Returns (LB, sigma_sqs_start)."""
+    LB = np.array(LB, dtype=np.float64)
+    start = np.array(sigma_sqs_init, dtype=np.float64)
+    for d, k in enumerate(links):
+        if int(k) == LINK_IDENTITY:
+            continue
+        seen = ~np.isnan(X_grid[:, d])
+        gy = link_apply(k, X_grid[seen, d])
+        sd = gy.std() if gy.size else 0.0
+        if not LB_given:
+            LB[d] = (0.01 * sd) ** 2
+        xs = np.asarray(Xhat_init, dtype=np.float64)[seen, d]
+        ok = link_domain(k, xs) & np.isfinite(link_apply(k, xs))
+        w = np.ones(gy.shape) if weight_grid is None else np.asarray(weight_grid)[seen, d]
+        ms = -1.0
+        if int(ok.sum()) >= 2:
+            ms = float(np.sum(w[ok] * (link_apply(k, xs[ok]) - gy[ok]) ** 2) / np.sum(w[ok]))
+        start[d] = ms if ms > LB[d] else (0.1 * sd) ** 2
+    return LB, start
+
+
 def observation_bookkeeping(X_obs: np.ndarray, X_grid: np.ndarray):
     """magi_v2.py:53, 89, 96-100: N_ds, beta, flat indices and values of the non-NaN grid entries."""
     N_ds = (~np.isnan(X_obs)).sum(axis=0)
