@@ -10,6 +10,7 @@ import numpy as np
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
 import magi_v2  # noqa: E402  (the drop-in module)
+from magi_v2_amd.host import compare_elpd  # noqa: E402
 
 
 def f_vec(t, X, thetas):
@@ -50,12 +51,22 @@ def main():
     sigma_fit = model.sigma_sqs_init.copy()
     model.thetas_init = np.ones(3)
     print("fitted on the observed rows: phi2", np.round(model.phi2s, 3), "sigma", np.round(np.sqrt(sigma_fit), 4))
-    report("fit on observed rows", model.predict(num_results=500, num_burnin_steps=500, n_chains=4, seed=1), model)
+    fitted_phi = model.predict(num_results=500, num_burnin_steps=500, n_chains=4, seed=1, elpd=True)
+    report("fit on observed rows", fitted_phi, model)
 
     # 3. user-supplied hyper-parameters (the reference lets users overwrite them, magi_v2.py:77-80)
     model.initial_fit(discretization=1, hparams={"phi2s": [0.5, 0.5, 0.5], "sigma_sqs": sigma_fit})
     model.thetas_init = np.ones(3)
-    report("phi2 = 0.5, fitted noise", model.predict(num_results=500, num_burnin_steps=500, n_chains=4, seed=1), model)
+    fixed_phi = model.predict(num_results=500, num_burnin_steps=500, n_chains=4, seed=1, elpd=True)
+    report("phi2 = 0.5, fitted noise", fixed_phi, model)
+
+    # 4. which of the two do the data prefer?  PSIS-LOO of the observations under the hyper-parameters of step 2 against those of step 3,
+    #    computed on the GPU from the samples each run left there.  Both runs see the same observations through the same (identity) link,
+    #    so their pointwise values pair up.  An elpd_diff within a couple of se_diff decides nothing; observations with khat > 0.7 are
+    #    those the posterior cannot predict without them, and their elpd_loo is not reliable.
+    for row in compare_elpd({"fitted phi2": fitted_phi["elpd"], "phi2 = 0.5": fixed_phi["elpd"]}):
+        print(f"[model comparison] {row['name']}: elpd_loo {row['elpd']:.1f} (se {row['se']:.1f}), p_loo {row['p']:.1f}, "
+              f"elpd_diff {row['elpd_diff']:.1f} (se {row['se_diff']:.1f}), {row['n_khat_bad']} observation(s) with khat > 0.7")
 
 
 if __name__ == "__main__":

@@ -461,6 +461,51 @@ int magi_sampler_summarize(magi_handle* h, int chain0, int n_sel, int n_q, const
                            double* th_mean, double* th_sd, double* th_quant, double* th_rhat, double* th_ess, double* th_mcse_mean,
                            int* n_nonfinite);
 
+/* ---- pointwise log-likelihood, WAIC and PSIS-LOO ----------------------------------------------- */
+
+/* Which of two models of the same data predicts them better (unit csrc/elpd.hip).  Per column k of a log-likelihood
+ * array loglik, host [C][R][K] -- l_s, s = c R + r, the log density of observation k under draw s -- with S = C R pooled draws:
+ *   lpd           logsumexp_s l_s - log S: the log pointwise predictive density.
+ *   p_waic        var_s l_s (ddof = 1, two passes; NaN when S < 2).
+ *   elpd_waic     lpd - p_waic.
+ *   khat, elpd_loo, p_loo   Pareto-smoothed importance sampling (Vehtari, Gelman, Gabry 2017, r_eff = 1).  Log ratios r_s = -l_s - max_s(-l_s)
+ *                 (a -0.0 counts as +0.0).  Tail length M = min(floor(S / 5), ceil(3 sqrt(S))).  The draws are ordered ascending by (r, s);
+ *                 the tail is the last M of them and the cutoff c is the r of the draw just below it.  If M < 5 or the tail's largest and
+ *                 smallest r are equal there is no smoothing and khat = +inf.  Otherwise x_j = exp(r_tail,j) - exp(c), ascending, and the
+ *                 fit is Zhang and Stephens': m = 30 + floor(sqrt(M)); theta_j = 1 / x_M + (1 - sqrt(m / (j - 1/2))) / (3 x_[floor(M/4 + 1/2)]),
+ *                 j = 1 .. m; k_j = mean_i log1p(-theta_j x_i); l_j = M (log(-theta_j / k_j) - k_j - 1); w_j = 1 / sum_i exp(l_i - l_j);
+ *                 theta = sum_j theta_j w_j; k = mean_i log1p(-theta x_i); sigma = -k / theta; khat = (k M + 5) / (M + 10).  If khat is
+ *                 finite the tail draw of rank j (1-based) gets the log weight log(exp(c) + sigma / khat expm1(-khat log1p(-(j - 1/2) / M)))
+ *                 (khat = 0: log(exp(c) - sigma log1p(-(j - 1/2) / M))); every other draw keeps lw_s = r_s.  All log weights are capped at 0.
+ *                 elpd_loo = logsumexp_s(l_s + lw_s) - logsumexp_s(lw_s);  p_loo = lpd - elpd_loo.
+ * A column with a non-finite l has NaN in every output and counts in *n_nonfinite.  Every sum runs in one fixed order: the results are
+ * bit-identical from run to run and do not depend on the chunking (summary_chunk_cols).
+ * lpd, p_waic, elpd_waic, elpd_loo, p_loo, khat [K], n_nonfinite: each optional (NULL: not copied).
+ * MAGI_E_BADARG (handle stays usable): C, R, C R as magi_summarize; K outside [1, 2^24]; loglik NULL; elpd_loo, p_loo or khat asked
+ * for with C R > 466033 -- the tail is sorted in LDS, 2048 (key, index) pairs, and M = ceil(3 sqrt(C R)) must fit; lpd, p_waic and
+ * elpd_waic are served for every C R when the three are NULL.  Needs a handle only for its device and stream, as magi_summarize; device
+ * memory of a call: the 64 MiB chunk, its staging buffer and 6 K doubles + K ints of results. */
+int magi_elpd(magi_handle* h, int C, int R, int K, const double* loglik,
+              double* lpd, double* p_waic, double* elpd_waic, double* elpd_loo, double* p_loo, double* khat,
+              int* n_nonfinite);
+
+/* The same six outputs for the observations of the finished sampler run, from its device-resident samples pooled over the chains
+ * [chain0, chain0 + n_sel): no draw crosses to the host.  One column per observed entry e = d N + i (yobs[e] not NaN), in ascending e;
+ * obs_index [n_obs] returns e, *n_obs_out their number n_obs (<= N D: arrays of N D entries always suffice, and a call with every other
+ * output NULL returns the number alone).  The log-likelihood of entry e under draw s, with x = X_s[e] and sigma^2_d(s) =
+ * softplus(sig_pre_d) + LB[d], or the constant of a MAGI_PRIOR_FIXED entry (the sigma^2 block of magi_sampler_summarize), is the
+ * untempered observation density of magi_set_obs_model:
+ *   l = -1/2 [ log(2 pi sigma^2_d / w_e) + w_e (g_d(x) - g_d(y_e))^2 / sigma^2_d ]
+ * with the link g_d and the weight w_e of the handle's -- on a group handle the member's own -- observation model (identity and 1
+ * without one).  A state outside a link's domain at an observed point gives a non-finite l, hence a NaN column.  The density is on the
+ * LINK's scale: to compare models with different links add log|g_d'(y_e)| per observation (MAGI_v2.posterior_elpd(scale="data")).
+ * loglik_out, optional: host [n_sel num_results][n_obs], the l themselves.  Every output is optional.
+ * MAGI_E_STATE / MAGI_E_BADARG as magi_sampler_summarize (sampler initialised, every selected chain finished, the chain range inside
+ * the sampler's chains and inside one member of a group), and the C R bound of elpd_loo, p_loo, khat above. */
+int magi_sampler_elpd(magi_handle* h, int chain0, int n_sel,
+                      double* lpd, double* p_waic, double* elpd_waic, double* elpd_loo, double* p_loo, double* khat,
+                      int* obs_index, int* n_obs_out, double* loglik_out, int* n_nonfinite);
+
 /* ---- multi-GPU ---------------------------------------------------------------------------------
  * There is deliberately NO magi_gather in this ABI (SURVEY 8b had listed one).  The path shards by independent (dataset, chain) units with
  * no exchange while sampling (one handle per GPU, one process per GPU); its only collective is ONE gather of the post-burn-in samples at
@@ -522,7 +567,8 @@ int magi_stream_kernel_name(magi_handle* h, int n_chains, char* buf, int cap);
  *   "build_serial"        MAGI_BUILD_SERIAL         flag
  *   "slot_budget_graphs"  (none: a test hook)       cap on the graph launches of one magi_sampler_run; 0 = the computed bound
  * Beside the options, one test switch of the summaries (no environment variable, no effect on any result): summary_chunk_cols, 0..2^24;
- * > 0: magi_summarize / magi_sampler_summarize gather at most this many columns per chunk (0 = what the work space allows). */
+ * > 0: magi_summarize / magi_sampler_summarize and magi_elpd / magi_sampler_elpd gather at most this many columns per chunk (0 = what the
+ * work space allows). */
 int magi_set_option(magi_handle* h, const char* name, int64_t value);
 
 /* Diagnostics: per-class device time of the last magi_build_matrices run with option "build_profile" set

@@ -352,7 +352,7 @@ class MAGI_v2:
                 n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[int]] = None,
                 stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
                 family_chains: Optional[int] = None, summary: bool = False, keep_samples: bool = True, adapt_metric: bool = False,
-                theta_support=None, theta_prior=None, sigma_sq_prior=None, obs_link=None, obs_weight=None):
+                theta_support=None, theta_prior=None, sigma_sq_prior=None, obs_link=None, obs_weight=None, elpd: bool = False):
         """magi_v2.py:286-425.  Returns the reference's results dictionary; with n_chains > 1 every
         sample array gains a leading chain axis.  ``family_chains``: in a job sharded over GPUs, the largest per-GPU share
         (shard.family_chains_for) -- every rank then samples with the same kernel family whatever its own share.
@@ -382,9 +382,12 @@ class MAGI_v2:
         the chain starts from a sigma^2 on the link's scale (host.link_sigma_defaults); an explicit ``sigma_sqs_LB`` is taken as given.
         ``Xhat_init`` outside a link's domain at an observed point raises ValueError.  ``results["obs_link"]`` / ``results["obs_weight"]`` echo
         the normalised specification when given.
+        ``elpd=True`` adds ``results["elpd"]``: the pointwise log predictive density of the observations, WAIC and PSIS-LOO with the
+        Pareto-khat diagnostic, computed on the GPU from the device-resident samples (``posterior_elpd``, on the scale of the data) -- what
+        ``host.compare_elpd`` compares two models of the same data by.  Legal with ``keep_samples=False``.
         Many datasets on one GPU: ``predict_many``."""
-        if not keep_samples and not summary:
-            raise ValueError("keep_samples=False needs summary=True: the call would return nothing of the posterior")
+        if not keep_samples and not (summary or elpd):
+            raise ValueError("keep_samples=False needs summary=True or elpd=True: the call would return nothing of the posterior")
         sigma_sqs_LB, sig_pre0, th_pre0 = self._predict_prepare(sigma_sqs_LB, family_chains, theta_support, theta_prior, sigma_sq_prior, obs_link, obs_weight)
         eng = self.engine
         if seed is None:                 # the reference calls sample_chain unseeded (magi_v2.py:389-395)
@@ -415,6 +418,8 @@ class MAGI_v2:
             results["metric"] = {"inv_mass_X": sq(mX), "inv_mass_sigma_pre": sq(ms), "inv_mass_theta_pre": sq(mt), "windows": windows}
         if summary:
             results["summary"] = _warn_if_stuck(self.posterior_summary())
+        if elpd:
+            results["elpd"] = self.posterior_elpd()
         return results
 
     def posterior_summary(self, probs=DEFAULT_PROBS, max_lag: int = 0):
@@ -425,6 +430,34 @@ class MAGI_v2:
         if not getattr(self, "_predicted", False):
             raise RuntimeError("posterior_summary summarises the samples of the last predict: run predict first")
         return self.engine.sampler_summary(probs=probs, max_lag=max_lag)
+
+    def posterior_elpd(self, scale: str = "data", loglik: bool = False, loo: Optional[bool] = None):
+        """Pointwise log predictive density, WAIC and PSIS-LOO of the last ``predict``, all its chains pooled, computed on the GPU from the
+        samples the sampler left there (MagiEngine.sampler_elpd; definitions in include/magi_hip.h).  The likelihood of an observation is
+        Gaussian on its link's scale; ``scale="data"`` (default) adds the constant log|g_d'(y)| per observation -- -log y under a log
+        link, -log(2 sqrt(y)) under sqrt, 0 under the identity -- to lpd, elpd_waic and elpd_loo, so that models with different links
+        compare on the scale of the data (a datum 0 under a sqrt link: ValueError); ``scale="link"`` adds nothing.  Returns the dictionary
+        of ``host.elpd_result``: ``pointwise`` (lpd, p_waic, elpd_waic, elpd_loo, p_loo, khat), ``obs_index`` [(grid point, component)],
+        the totals elpd_waic, elpd_loo, p_waic, p_loo with ``se_<name>``, ``n_khat_bad`` (khat > 0.7), ``n_nonfinite``; ``loglik=True`` adds
+        the log-likelihood [chains, draws, n_obs] (on the link's scale).  ``loo``: None computes PSIS-LOO whenever the device serves it -- up
+        to 466033 pooled draws -- and past that warns and returns lpd and WAIC alone (``host.elpd_wants_loo``); False skips it; True insists
+        (MagiHipError past the bound)."""
+        if not getattr(self, "_predicted", False):
+            raise RuntimeError("posterior_elpd works on the samples of the last predict: run predict first")
+        if scale not in ("data", "link"):
+            raise ValueError(f"scale: 'data' or 'link', got {scale!r}")
+        eng = self.engine
+        want = host.elpd_wants_loo(eng.n_chains * eng._cfg.num_results, loo)
+        return self._elpd_on_scale(eng.sampler_elpd(loglik=loglik, loo=want), scale)
+
+    def _elpd_on_scale(self, res, scale):
+        """``res`` (MagiEngine.sampler_elpd: the link's scale) on ``scale``, under the links of the last ``_predict_prepare``."""
+        if scale not in ("data", "link"):
+            raise ValueError(f"scale: 'data' or 'link', got {scale!r}")
+        shift = None
+        if scale == "data":
+            shift = host.elpd_jacobian(getattr(self, "_obs_link", None), np.asarray(self.X_obs_discret, dtype=np.float64), res["obs_index"])
+        return host.elpd_result(res["pointwise"], res["obs_index"], res["n_nonfinite"], loglik=res.get("loglik"), shift=shift, scale=scale)
 
     def _predict_prepare(self, sigma_sqs_LB, family_chains=None, theta_support=None, theta_prior=None, sigma_sq_prior=None,
                          obs_link=None, obs_weight=None):
@@ -590,7 +623,7 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
                  n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[Sequence[int]]] = None,
                  stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
                  summary: bool = False, keep_samples: bool = True, theta_support=None, theta_prior=None, sigma_sq_prior=None,
-                 obs_link=None, obs_weight=None):
+                 obs_link=None, obs_weight=None, elpd: bool = False):
     """``predict`` for several models (after their ``initial_fit``) at once.  Models of one library, device and problem shape are sampled
     as one problem group on their GPU -- one captured graph, one kernel pair per leapfrog slot for all their chains -- and the others by
     their own ``predict``.  ``sigma_sqs_LB``: None (each model's default) or one entry per model; ``chain_ids``: None (0 .. n_chains - 1
@@ -601,9 +634,10 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
     or such a specification); the members of one group may differ.  ``theta_prior`` / ``sigma_sq_prior``: likewise None, one specification
     for all models (entries None, "flat", ("normal", m, s), ... as in ``predict``) or one per model.  ``obs_link`` / ``obs_weight``: likewise
     None, one specification for all models (a link name, or one name per component; one weight array) or one per model (a list of such
-    specifications / of arrays or None); the members of one group may differ."""
-    if not keep_samples and not summary:
-        raise ValueError("keep_samples=False needs summary=True: the call would return nothing of the posterior")
+    specifications / of arrays or None); the members of one group may differ.  ``elpd`` as in ``predict``: one ``results["elpd"]`` per
+    model, a grouped model's from its own chains and observation model."""
+    if not keep_samples and not (summary or elpd):
+        raise ValueError("keep_samples=False needs summary=True or elpd=True: the call would return nothing of the posterior")
     models = list(models)
     n = len(models)
     lbs = [None] * n if sigma_sqs_LB is None else list(sigma_sqs_LB)
@@ -643,7 +677,7 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
         if len(grp) == 1:
             k = grp[0]
             out[k] = models[k].predict(num_results, num_burnin_steps, lbs[k], verbose, chain_ids=ids[k], summary=summary, keep_samples=keep_samples,
-                                        theta_support=sups[k], theta_prior=tpri[k], sigma_sq_prior=spri[k], obs_link=olnk[k], obs_weight=owts[k], **kw)
+                                        theta_support=sups[k], theta_prior=tpri[k], sigma_sq_prior=spri[k], obs_link=olnk[k], obs_weight=owts[k], elpd=elpd, **kw)
             continue
         g = MagiGroup([models[k].engine for k in grp])
         try:
@@ -665,6 +699,8 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
                 print(f"Finished sampling in {minutes} minutes.")
             diag = g.sampler_diag()
             summaries = [g.sampler_summary(member=j) for j in range(len(grp))] if summary else None
+            elpds = [g.sampler_elpd(member=j, loo=host.elpd_wants_loo(n_chains * num_results))
+                     for j in range(len(grp))] if elpd else None
         finally:
             g.close()
         for j, k in enumerate(grp):
@@ -674,4 +710,6 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
             out[k] = models[k]._predict_results(*part, dk, prep[k][0], seed, n_chains, num_burnin_steps, minutes)
             if summary:
                 out[k]["summary"] = _warn_if_stuck(summaries[j])
+            if elpd:
+                out[k]["elpd"] = models[k]._elpd_on_scale(elpds[j], "data")
     return out

@@ -1,0 +1,101 @@
+// What the per-column statistics units share (summary.hip, elpd.hip): one 256-thread workgroup per column of C R draws gathered to
+// chunk[column][C R]; the fixed-order reductions over that workgroup; the order-preserving key of a double and the radix select on it;
+// the limits of C and R.  Every sum runs in one fixed order (lane-strided partials, a butterfly, the four waves added as
+// (w0 + w1) + (w2 + w3)) and the only atomics are integer ones: results are bit-identical from run to run.
+#pragma once
+#include "magi_internal.h"
+
+#include <algorithm>
+#include <string>
+
+namespace colstat {
+
+constexpr int SUM_WG = 256;
+constexpr int G_TILE = 64;            // the gathers: 64 x 64 doubles per workgroup of 64 x 4 threads
+constexpr int SUM_LDS = 2048;         // doubles of LDS a statistics kernel sorts / stages (16 KiB: four workgroups per CU and more)
+constexpr size_t CHUNK_DOUBLES = (size_t)1 << 23;
+
+struct SumLB { double v[MAGI_MAX_D]; };
+
+// the reductions over the workgroup, each in one fixed order; every thread receives the result
+__device__ __forceinline__ double wg_sum(double v, double* red /* LDS [4] */) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    __syncthreads();                                           // (the previous use of red is over)
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ double wg_min(double v, double* red) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v = fmin(v, __shfl_xor(v, m, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmin(fmin(red[0], red[1]), fmin(red[2], red[3]));
+}
+// (the butterfly: not the DPP wave_sum of magi_internal.h, whose order differs)
+__device__ __forceinline__ double wave_bsum(double v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+// order-preserving key of a finite double and its inverse
+__device__ __forceinline__ unsigned long long to_key(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : b | 0x8000000000000000ull;
+}
+__device__ __forceinline__ double from_key(unsigned long long k) {
+    const unsigned long long b = (k >> 63) ? k ^ 0x8000000000000000ull : ~k;
+    return __longlong_as_double((long long)b);
+}
+
+// key of rank `rank` (0-based) among the S keys key_of(0 .. S - 1), `bits` wide (a multiple of 8); every thread returns it
+template <class KeyOf>
+__device__ __forceinline__ unsigned long long radix_select_keys(KeyOf key_of, int S, int rank, int bits, int* hist /* LDS [256] */) {
+    unsigned long long prefix = 0, mask = 0;
+    for (int shift = bits - 8; shift >= 0; shift -= 8) {
+        hist[threadIdx.x] = 0;                                 // (SUM_WG == 256 bins)
+        __syncthreads();
+        for (int e = threadIdx.x; e < S; e += SUM_WG) {
+            const unsigned long long key = key_of(e);
+            if ((key & mask) == prefix) atomicAdd(&hist[(int)((key >> shift) & 255)], 1);
+        }
+        __syncthreads();
+        int cum = 0, b = 0;
+        for (; b < 255; ++b) {                                 // (the rank lies in one of the bins: b stops at 255 at the latest)
+            const int c = hist[b];
+            if (cum + c > rank) break;
+            cum += c;
+        }
+        rank -= cum;
+        prefix |= (unsigned long long)b << shift;
+        mask |= 0xFFull << shift;
+        __syncthreads();                                       // (every thread has read hist before it is cleared again)
+    }
+    return prefix;
+}
+
+// key of the order statistic of rank `rank` (0-based) among the S finite values of row; every thread returns it
+__device__ inline unsigned long long radix_select(const double* __restrict__ row, int S, int rank, int* hist /* LDS [256] */) {
+    return radix_select_keys([row](int e) { return to_key(row[e]); }, S, rank, 64, hist);
+}
+
+// the limits of a column's draws the entry points share
+inline int check_draws(magi_handle* h, const char* who, long long C, long long R) {
+    if (C < 1 || C > 4096) return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": 1 <= C <= 4096 chains");
+    if (R < 1 || R > (1 << 20)) return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": 1 <= R <= 2^20 draws per chain");
+    if (C * R > (1 << 22)) return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": C R exceeds 2^22 draws per column");
+    return MAGI_OK;
+}
+
+// columns per chunk of a block of K columns of S draws (at most 2^23 doubles; the test switch summary_chunk_cols forces small chunks)
+inline size_t chunk_cols(const magi_handle* h, size_t S, size_t K) {
+    size_t cc = std::max<size_t>(1, CHUNK_DOUBLES / S);
+    cc = std::min<size_t>({cc, K, (size_t)1 << 21});                     // (the gathers: at most 2^15 tiles along grid.y)
+    if (h->opt.summary_chunk_cols > 0) cc = std::min<size_t>(cc, (size_t)h->opt.summary_chunk_cols);
+    return cc;
+}
+
+}  // namespace colstat

@@ -13,22 +13,18 @@
 //                   of 8 bits, LDS histogram) on the order-preserving 64-bit key, then one pass for the next-larger order statistic.
 // Every sum runs in one fixed order (lane-strided partials, a butterfly, the four waves added as (w0 + w1) + (w2 + w3)); the only atomics
 // are integer ones: the results are bit-identical from run to run.  Does not depend on the drift (jit._DRIFT_FREE).
-#include "magi_internal.h"
+#include "colstat.h"
 
 #include <cmath>
 #include <vector>
 
 namespace {
 
-constexpr int SUM_WG = 256;
-constexpr int G_TILE = 64;            // k_sum_gather: 64 x 64 doubles per workgroup of 64 x 4 threads
-constexpr int SUM_LDS = 2048;         // doubles of LDS a statistics kernel sorts / stages (16 KiB: four workgroups per CU and more)
-constexpr size_t CHUNK_DOUBLES = (size_t)1 << 23;
+using namespace colstat;              // SUM_WG, G_TILE, SUM_LDS, the workgroup reductions, to_key / radix_select, check_draws (shared with elpd.hip)
 constexpr int MAX_Q = 16;
 
 enum { MODE_PLAIN = 0, MODE_X = 1, MODE_SIGMA = 2, MODE_THETA = 3 };
 
-struct SumLB { double v[MAGI_MAX_D]; };
 struct SumProbs { double p[MAX_Q]; };
 
 __global__ __launch_bounds__(G_TILE * 4) void k_sum_gather(int S, int nc, const double* __restrict__ src /* rows ld apart, nc columns */,
@@ -50,29 +46,6 @@ __global__ __launch_bounds__(G_TILE * 4) void k_sum_gather(int S, int nc, const 
     __syncthreads();
     for (int c = ty; c < G_TILE; c += 4)
         if (c0 + c < nc && r0 + tx < S) chunk[(size_t)(c0 + c) * S + r0 + tx] = tile[tx][c];
-}
-
-// the three reductions over the workgroup, each in one fixed order; every thread receives the result
-__device__ __forceinline__ double wg_sum(double v, double* red /* LDS [4] */) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    __syncthreads();                                           // (the previous use of red is over)
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return (red[0] + red[1]) + (red[2] + red[3]);
-}
-__device__ __forceinline__ double wg_min(double v, double* red) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v = fmin(v, __shfl_xor(v, m, 64));
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return fmin(fmin(red[0], red[1]), fmin(red[2], red[3]));
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
-    return v;
 }
 
 // where column j of a block goes in the caller's arrays: the X block is walked in the samples' order [D][N] and reported in the host
@@ -139,13 +112,13 @@ __global__ __launch_bounds__(SUM_WG) void k_sum_moments(int C, int R, const doub
         const double* y = row + split_start(m, R, n);
         double a = 0.0;
         for (int i = lane; i < n; i += 64) a += y[i];
-        const double ym = wave_sum(a) / (double)n;
+        const double ym = wave_bsum(a) / (double)n;
         double q = 0.0;
         for (int i = lane; i < n; i += 64) {
             const double dv = y[i] - ym;
             q += dv * dv;
         }
-        wacc += wave_sum(q) / (double)(n - 1);
+        wacc += wave_bsum(q) / (double)(n - 1);
         if (lane == 0) yb[m] = ym;
     }
     __syncthreads();                                           // (yb is read below by other waves of this workgroup)
@@ -235,41 +208,6 @@ __global__ __launch_bounds__(SUM_WG) void k_sum_ess(int C, int R, int max_lag, c
     }
 }
 
-// order-preserving key of a finite double and its inverse
-__device__ __forceinline__ unsigned long long to_key(double v) {
-    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
-    return (b >> 63) ? ~b : b | 0x8000000000000000ull;
-}
-__device__ __forceinline__ double from_key(unsigned long long k) {
-    const unsigned long long b = (k >> 63) ? k ^ 0x8000000000000000ull : ~k;
-    return __longlong_as_double((long long)b);
-}
-
-// key of the order statistic of rank `rank` (0-based) among the S finite values of row; every thread returns it
-__device__ unsigned long long radix_select(const double* __restrict__ row, int S, int rank, int* hist /* LDS [256] */) {
-    unsigned long long prefix = 0, mask = 0;
-    for (int shift = 56; shift >= 0; shift -= 8) {
-        hist[threadIdx.x] = 0;                                 // (SUM_WG == 256 bins)
-        __syncthreads();
-        for (int e = threadIdx.x; e < S; e += SUM_WG) {
-            const unsigned long long key = to_key(row[e]);
-            if ((key & mask) == prefix) atomicAdd(&hist[(int)((key >> shift) & 255)], 1);
-        }
-        __syncthreads();
-        int cum = 0, b = 0;
-        for (; b < 255; ++b) {                                 // (the rank lies in one of the bins: b stops at 255 at the latest)
-            const int c = hist[b];
-            if (cum + c > rank) break;
-            cum += c;
-        }
-        rank -= cum;
-        prefix |= (unsigned long long)b << shift;
-        mask |= 0xFFull << shift;
-        __syncthreads();                                       // (every thread has read hist before it is cleared again)
-    }
-    return prefix;
-}
-
 __global__ __launch_bounds__(SUM_WG) void k_sum_order(int S, const double* __restrict__ chunk, const double* __restrict__ col, long long k0,
                                                       int mode, int N, int D, long long K, int n_q, SumProbs probs,
                                                       double* __restrict__ quant /* [n_q][K] */) {
@@ -348,9 +286,7 @@ struct SumOut { double *mean, *sd, *quant, *rhat, *ess, *mcse; };
 int summarize_block(magi_handle* h, const char* who, const double* dsrc, const double* hsrc, long long ld, int C, int R, long long K, int mode,
                     int N, int D, const SumLB& lb, const double2* tsup, const double4* prior, int n_q, const SumProbs& probs, int max_lag, const SumOut& o, int* nonfinite) {
     const size_t S = (size_t)C * R, M = 2 * (size_t)C;
-    size_t cc = std::max<size_t>(1, CHUNK_DOUBLES / S);
-    cc = std::min<size_t>({cc, (size_t)K, (size_t)1 << 21});             // (k_sum_gather: at most 2^15 tiles along grid.y)
-    if (h->opt.summary_chunk_cols > 0) cc = std::min<size_t>(cc, (size_t)h->opt.summary_chunk_cols);
+    const size_t cc = chunk_cols(h, S, (size_t)K);
     const bool diag = R >= 4, want_ess = o.ess || o.mcse, want_q = n_q > 0 && o.quant;
     // one device buffer: chunk (cc S) | staging of the host route (cc S) | ybar (cc M) | col (cc 4) | mean, sd, rhat, ess, mcse (K each) |
     // quant (n_q K) | the counter (1 int)
@@ -412,13 +348,6 @@ int check_probs(magi_handle* h, const char* who, int n_q, const double* probs, S
             return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": probs[" + std::to_string(q) + "] is not a finite number in [0, 1]");
         pr.p[q] = probs[q];
     }
-    return MAGI_OK;
-}
-
-int check_draws(magi_handle* h, const char* who, long long C, long long R) {
-    if (C < 1 || C > 4096) return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": 1 <= C <= 4096 chains");
-    if (R < 1 || R > (1 << 20)) return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": 1 <= R <= 2^20 draws per chain");
-    if (C * R > (1 << 22)) return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": C R exceeds 2^22 draws per column");
     return MAGI_OK;
 }
 

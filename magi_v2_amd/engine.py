@@ -12,7 +12,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .host import obs_model_spec, prior_spec, theta_support
+from .host import ELPD_POINTWISE, elpd_result, obs_model_spec, prior_spec, theta_support
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmagi_hip.so")
@@ -94,6 +94,8 @@ _SYMBOLS = {
     "magi_ode_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _ip, _ip]),
     "magi_summarize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int] + [_dp] * 6 + [_ip]),
     "magi_sampler_summarize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int] + [_dp] * 18 + [_ip]),
+    "magi_elpd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp] + [_dp] * 6 + [_ip]),
+    "magi_sampler_elpd": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [_dp] * 6 + [_ip, _ip, _dp, _ip]),
 }
 
 SUMMARY_STATS = ("mean", "sd", "quantiles", "rhat", "ess", "mcse_mean")       # the order of the six outputs in include/magi_hip.h
@@ -294,13 +296,8 @@ class MagiEngine:
         out.update(probs=probs, n_nonfinite=int(nf.value))
         return out
 
-    def sampler_summary(self, chains=None, probs=DEFAULT_PROBS, max_lag=0, member=None):
-        """Summaries of the finished sampler run, computed on the device-resident samples (magi_sampler_summarize): no draw is copied to the
-        host.  Returns dict(X, sigma_sqs, thetas, probs, n_nonfinite); X, sigma_sqs (= softplus(sig_pre) + LB) and thetas
-        (= softplus(th_pre); under ``set_theta_support`` the natural scale of each parameter's support, a group member's own) each a dict as
-        ``summarize`` returns, of shapes [N, D], [D] and [P].  ``chains``: None (all) or a contiguous
-        run of chain indices (a range, or (first, count) as a slice) pooled into one summary.  ``member`` (a MagiGroup): the chains of
-        that member -- a group's members sample different posteriors and are never pooled."""
+    def _chain_range(self, chains, member):
+        """(chain0, n_sel) of ``chains`` (None: all; a contiguous run of chain indices, or a slice) or of ``member`` of a MagiGroup."""
         if member is not None:
             if chains is not None:
                 raise ValueError("give chains or member, not both")
@@ -315,6 +312,16 @@ class MagiEngine:
             if idx.size == 0 or np.any(np.diff(idx) != 1):
                 raise ValueError("chains must be a contiguous, increasing run of chain indices")
             chain0, n_sel = int(idx[0]), int(idx.size)
+        return chain0, n_sel
+
+    def sampler_summary(self, chains=None, probs=DEFAULT_PROBS, max_lag=0, member=None):
+        """Summaries of the finished sampler run, computed on the device-resident samples (magi_sampler_summarize): no draw is copied to the
+        host.  Returns dict(X, sigma_sqs, thetas, probs, n_nonfinite); X, sigma_sqs (= softplus(sig_pre) + LB) and thetas
+        (= softplus(th_pre); under ``set_theta_support`` the natural scale of each parameter's support, a group member's own) each a dict as
+        ``summarize`` returns, of shapes [N, D], [D] and [P].  ``chains``: None (all) or a contiguous
+        run of chain indices (a range, or (first, count) as a slice) pooled into one summary.  ``member`` (a MagiGroup): the chains of
+        that member -- a group's members sample different posteriors and are never pooled."""
+        chain0, n_sel = self._chain_range(chains, member)
         probs, n_q = self._probs(probs)
         blocks = {"X": _summary_arrays((self.N, self.D), n_q), "sigma_sqs": _summary_arrays((self.D,), n_q),
                   "thetas": _summary_arrays((self.P,), n_q)}
@@ -324,6 +331,47 @@ class MagiEngine:
         out = {b: dict(zip(SUMMARY_STATS, arrs)) for b, arrs in blocks.items()}
         out.update(probs=probs, n_nonfinite=int(nf.value))
         return out
+
+    def _elpd_outputs(self, n, loo):
+        return {s: (np.empty(n) if (loo or s in ("lpd", "p_waic", "elpd_waic")) else None) for s in ELPD_POINTWISE}
+
+    def elpd(self, loglik, loo=True):
+        """WAIC and PSIS-LOO of a log-likelihood array ``loglik`` [C chains, R draws, K observations] on the device (magi_elpd; the
+        definitions are in include/magi_hip.h): a sharded job's gathered log-likelihoods, or any other model's.  Returns the dictionary
+        of ``host.elpd_result``: ``pointwise`` (lpd, p_waic, elpd_waic, elpd_loo, p_loo, khat, each [K]), the totals with their standard
+        errors, ``n_khat_bad``, ``n_nonfinite`` (columns with a non-finite entry: all their outputs are NaN).  ``loo=False`` leaves the
+        three PSIS outputs out (None) -- the only way past C R = 466033, the bound of the device's tail sort."""
+        loglik = _f64(loglik)
+        if loglik.ndim != 3:
+            raise ValueError(f"expected loglik of shape (chains, draws, observations), got {loglik.shape}")
+        n_c, n_r, K = loglik.shape
+        outs = self._elpd_outputs(K, loo)
+        nf = C.c_int32(0)
+        self._check(self._lib.magi_elpd(self._h, n_c, n_r, K, _ptr(loglik), *[_ptr(outs[s]) for s in ELPD_POINTWISE], C.byref(nf)))
+        return elpd_result(outs, None, nf.value)
+
+    def sampler_elpd(self, chains=None, member=None, loglik=False, loo=True):
+        """Pointwise log-likelihood, WAIC and PSIS-LOO of the finished sampler run, computed on the device-resident samples
+        (magi_sampler_elpd): no draw is copied to the host.  One entry per observation, in the order of ``obs_index`` [n_obs, 2] = (grid
+        point i, component d), ascending in d N + i; the log-likelihood is the untempered observation density under the handle's (a
+        group member's own) links, weights, LB and fixed variances, on the LINK's scale.  ``chains`` / ``member`` as in
+        ``sampler_summary``.  ``loglik=True`` adds ``loglik`` [chains, draws, n_obs], the log-likelihood itself.  ``loo`` as in ``elpd``.
+        Returns the dictionary of ``host.elpd_result``."""
+        chain0, n_sel = self._chain_range(chains, member)
+        group = getattr(self, "members", None)
+        cap = (group[chain0 // (self.n_chains // len(group))] if group else self)._n_obs      # observations given to set_problem: n_obs is at most that
+        outs = self._elpd_outputs(cap, loo)
+        idx = np.zeros(max(cap, 1), dtype=np.int32)
+        ll = np.empty(n_sel * self._cfg.num_results * cap) if loglik and self._cfg is not None else None
+        n_obs, nf = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.magi_sampler_elpd(self._h, chain0, n_sel, *[_ptr(outs[s]) for s in ELPD_POINTWISE], idx.ctypes.data_as(_ip),
+                                                C.byref(n_obs), _ptr(ll), C.byref(nf)))
+        n = int(n_obs.value)
+        outs = {s: (None if v is None else v[:n].copy()) for s, v in outs.items()}
+        if ll is not None:
+            ll = ll[:n_sel * self._cfg.num_results * n].reshape(n_sel, self._cfg.num_results, n)
+        e = idx[:n].astype(np.int64)
+        return elpd_result(outs, np.stack([e % self.N, e // self.N], axis=1), nf.value, loglik=ll)
 
     def selftest(self, drift=None, force=False):
         """Self-test of the library this engine runs (magi_v2_amd.selftest.ensure: cached verdict, or a run on handles of its own);

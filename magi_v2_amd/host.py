@@ -7,6 +7,7 @@ kernel matrices or samples -- those exist only as HIP kernels (magi_v2_amd/csrc)
 """
 from __future__ import annotations
 
+import warnings
 from typing import Callable, Dict, Optional, Tuple
 
 import numpy as np
@@ -352,6 +353,117 @@ def observation_bookkeeping(X_obs: np.ndarray, X_grid: np.ndarray):
     beta = (D * n_grid) / N_ds.sum()
     idx = np.where(~np.isnan(X_grid).flatten())[0]
     return N_ds, beta, idx, X_grid.reshape(-1)[idx]
+
+
+# --------------------------------------------------------------------------------------------
+# pointwise log-likelihood, WAIC, PSIS-LOO: the host side (the statistics themselves are the device's, csrc/elpd.hip)
+# --------------------------------------------------------------------------------------------
+
+ELPD_POINTWISE = ("lpd", "p_waic", "elpd_waic", "elpd_loo", "p_loo", "khat")       # the order of the six outputs in include/magi_hip.h
+ELPD_TOTALS = ("elpd_waic", "elpd_loo", "p_waic", "p_loo")
+KHAT_BAD = 0.7
+ELPD_LOO_MAX_DRAWS = 466033          # pooled draws per observation up to which the device serves PSIS-LOO (include/magi_hip.h: magi_elpd)
+
+
+def elpd_result(pointwise, obs_index=None, n_nonfinite=0, loglik=None, shift=None, scale="link"):
+    """The dictionary ``MagiEngine.elpd`` / ``sampler_elpd`` / ``MAGI_v2.posterior_elpd`` return, from the device's pointwise arrays
+    (``pointwise``: name -> [n] for the names of ELPD_POINTWISE; an entry may be None when it was not asked for).  ``shift`` [n]: a
+    per-observation constant added to lpd, elpd_waic and elpd_loo (``elpd_jacobian``).  Holds ``pointwise`` (the arrays), ``obs_index``
+    ([n, 2] pairs (i, d): grid point, component; None for a plain log-likelihood array), ``n_obs``, ``n_nonfinite``, ``scale``, the totals
+    ``elpd_waic``, ``elpd_loo``, ``p_waic``, ``p_loo`` -- sums over the observations -- each with its standard error ``se_<name>`` =
+    sqrt(n var_i) (ddof = 1), ``n_khat_bad`` (observations with khat > 0.7: their elpd_loo is not reliable) and, when given, ``loglik``."""
+    point = {}
+    for s in ELPD_POINTWISE:
+        v = pointwise.get(s)
+        if v is None:
+            point[s] = None
+            continue
+        v = np.array(v, dtype=np.float64)
+        if shift is not None and s in ("lpd", "elpd_waic", "elpd_loo"):
+            v = v + np.asarray(shift, dtype=np.float64)
+        point[s] = v
+    n = int(next(v.shape[0] for v in point.values() if v is not None))
+    out = {"pointwise": point, "obs_index": None if obs_index is None else np.asarray(obs_index, dtype=np.int64).reshape(-1, 2),
+           "n_obs": n, "n_nonfinite": int(n_nonfinite), "scale": scale}
+    for s in ELPD_TOTALS:
+        v = point[s]
+        if v is None:
+            out[s] = out["se_" + s] = None
+            continue
+        out[s] = float(v.sum())
+        out["se_" + s] = float(np.sqrt(n * v.var(ddof=1))) if n >= 2 else float("nan")
+    out["n_khat_bad"] = None if point["khat"] is None else int((point["khat"] > KHAT_BAD).sum())
+    if loglik is not None:
+        out["loglik"] = loglik
+    return out
+
+
+def elpd_wants_loo(n_draws: int, loo=None) -> bool:
+    """Whether PSIS-LOO is computed beside WAIC for ``n_draws`` pooled draws per observation: ``loo`` as given, or -- None -- whenever the
+    device serves it (n_draws <= ELPD_LOO_MAX_DRAWS); past that bound one warning says that lpd and WAIC alone are returned, so that a
+    finished sampling run is not lost to the refusal."""
+    if loo is not None:
+        return bool(loo)
+    if int(n_draws) <= ELPD_LOO_MAX_DRAWS:
+        return True
+    warnings.warn(f"elpd: {int(n_draws)} pooled draws per observation exceed the {ELPD_LOO_MAX_DRAWS} up to which PSIS-LOO is computed on the device; "
+                  "returning lpd and WAIC only (elpd_loo, p_loo and khat are None)", stacklevel=3)
+    return False
+
+
+def elpd_jacobian(links, X_grid: np.ndarray, obs_index):
+    """log|g_d'(y)| of every observation (i, d) of ``obs_index`` [n, 2], y = X_grid[i, d]: what carries a log density on the link's scale
+    to the scale of the data -- 0 for the identity, -log y for log, -log(2 sqrt(y)) for sqrt.  A datum 0 under a sqrt link has no finite
+    constant: ValueError naming the component and the count."""
+    X_grid = np.asarray(X_grid, dtype=np.float64)
+    obs_index = np.asarray(obs_index, dtype=np.int64).reshape(-1, 2)
+    out = np.zeros(obs_index.shape[0])
+    for d, k in enumerate(np.zeros(X_grid.shape[1], dtype=np.int32) if links is None else links):
+        sel = obs_index[:, 1] == d
+        y = X_grid[obs_index[sel, 0], d]
+        if int(k) == LINK_LOG:
+            out[sel] = -np.log(y)
+        elif int(k) == LINK_SQRT:
+            zeros = int((y == 0.0).sum())
+            if zeros:
+                raise ValueError(f"scale='data': component {d} has {zeros} observation(s) equal to 0 under its sqrt link, where log|g'(y)| is not finite; "
+                                 "use scale='link'")
+            out[sel] = -np.log(2.0 * np.sqrt(y))
+    return out
+
+
+def compare_elpd(models, kind="loo"):
+    """Models of the SAME observations compared by their expected log predictive density: ``models`` {name: the dictionary of
+    ``posterior_elpd`` / ``sampler_elpd`` / ``elpd``}, ``kind`` "loo" or "waic".  Returns one row per model, best first: dict(name, elpd, se,
+    p, elpd_diff (to the best model, <= 0), se_diff = sqrt(n var_i(pointwise difference)) (ddof = 1; 0 for the best), n_khat_bad).  Raises
+    ValueError when the models' ``obs_index`` (or numbers of observations) or scales differ: sums over different data do not compare."""
+    if kind not in ("loo", "waic"):
+        raise ValueError(f"kind: 'loo' or 'waic', got {kind!r}")
+    if not models:
+        raise ValueError("compare_elpd: no model")
+    key, pkey = "elpd_" + kind, "p_" + kind
+    names = list(models)
+    first = models[names[0]]
+    for nm in names:
+        r = models[nm]
+        if r["pointwise"][key] is None:
+            raise ValueError(f"compare_elpd: model {nm!r} holds no {key}")
+        a, b = r["obs_index"], first["obs_index"]
+        if r["n_obs"] != first["n_obs"] or (a is None) != (b is None) or (a is not None and not np.array_equal(a, b)):
+            raise ValueError(f"compare_elpd: model {nm!r} and model {names[0]!r} differ in obs_index: they were not fitted to the same observations")
+        if r.get("scale") != first.get("scale"):
+            raise ValueError(f"compare_elpd: model {nm!r} is on scale {r.get('scale')!r}, model {names[0]!r} on {first.get('scale')!r}")
+    order = sorted(names, key=lambda nm: -models[nm][key] if np.isfinite(models[nm][key]) else np.inf)
+    best = models[order[0]]
+    n = best["n_obs"]
+    rows = []
+    for nm in order:
+        r = models[nm]
+        diff = r["pointwise"][key] - best["pointwise"][key]
+        se_diff = 0.0 if r is best else (float(np.sqrt(n * diff.var(ddof=1))) if n >= 2 else float("nan"))
+        rows.append({"name": nm, "elpd": r[key], "se": r["se_" + key], "p": r[pkey], "elpd_diff": 0.0 if r is best else float(diff.sum()),
+                     "se_diff": se_diff, "n_khat_bad": r["n_khat_bad"] if kind == "loo" else None})
+    return rows
 
 
 # --------------------------------------------------------------------------------------------
