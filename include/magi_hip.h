@@ -418,6 +418,39 @@ int magi_ode_solve(magi_handle* h, int drift_id, int P, int S,
                    int T, const double* t_out, int substeps,
                    double* traj, double* mean, double* sd, int* status, int* n_failed);
 
+/* The same draws integrated with error control (unit csrc/ode_adaptive.hip, one lane per draw like magi_ode_solve), for when no fixed `substeps`
+ * is right: a stated tolerance, and stiff systems.  x0, theta, T, t_out, traj, mean, sd, status and n_failed mean what they mean in
+ * magi_ode_solve.
+ * method  MAGI_ODE_DOPRI5: Dormand-Prince 5(4), seven stages with the first the last of the step before (FSAL), advancing with the
+ *           5th-order weights b; err = h sum (b_i - b*_i) k_i; q = 5.
+ *         MAGI_ODE_ROS23: the Shampine-Reichelt modified Rosenbrock 2(3) pair (ode23s), for stiff draws.  d = 1 / (2 + sqrt 2),
+ *           e32 = 6 + sqrt 2, J = df/dx and T = df/dt at (t, y) (T = 0 unless the traced drift uses t), W = I - h d J factored once per
+ *           trial step by LU with partial pivoting;
+ *             k1 = W^-1 (F0 + h d T),  F1 = f(t + h/2, y + h/2 k1),  k2 = W^-1 (F1 - k1) + k1,  y+ = y + h k2,  F2 = f(t + h, y+),
+ *             k3 = W^-1 [F2 - e32 (k2 - F1) - 2 (k1 - F0) + h d T],  err = h/6 (k1 - 2 k2 + k3);  q = 3;  F2 is the next step's F0.
+ * Controller (both methods).  h: the proposed step, first h0 if h0 > 0, else t_out[1] - t_out[0].  In interval j the trial step is
+ *   h_trial = min(h, t_out[j+1] - t); a clipped step ends at t_out[j+1] itself: steps land exactly on every output time, there is no
+ *   dense output.  A step is also clipped (stretched by less than 16 ulp) when h would leave less than 16 ulp(t_out[j+1]) of the
+ *   interval: on a uniform grid h is often the interval's width up to rounding, and the remainder would be a step that underflows.
+ *   errn = max_d |err_d| / (atol + rtol max(|y_d|, |y+_d|));  fac = clamp(0.9 errn^(-1/q), 0.2, 5), 5 when errn = 0.
+ *   A trial with a non-finite |err_d| / (...) or y+_d, or a W with a pivot that is 0 or not finite, is rejected with fac = 0.2.
+ *   errn <= 1: accepted; the step accepted right after a rejection does not grow (fac <- min(fac, 1)); h <- h_trial fac, and after a
+ *     clipped step h <- max(h, h_trial fac), so that a dense output grid does not ratchet the step down.
+ *   errn > 1: rejected, h <- h_trial min(fac, 1).
+ *   Before every trial: accepted + rejected >= max_steps ends the draw with reason 2; h_trial < 16 ulp(t) ends it with reason 3.
+ * reason[s]: 0 none, 1 non-finite state (x0), 2 step budget, 3 step underflow.  For reasons 2 and 3 status[s] is j + 1 of the interval
+ *   that was not completed (1 for reason 1), and the outputs from there on are NaN: status keeps its meaning.  n_accepted[s],
+ *   n_rejected[s]: the steps of draw s.  reason, n_accepted, n_rejected [S]: optional like the other outputs.
+ * MAGI_E_BADARG (handle stays usable): the cases of magi_ode_solve (substeps aside); an unknown method; rtol outside [1e-13, 1e-1]; atol
+ * < 0; rtol or atol not finite; h0 < 0 or not finite; max_steps outside [1, 2^24]. */
+enum { MAGI_ODE_DOPRI5 = 1, MAGI_ODE_ROS23 = 2 };
+int magi_ode_solve_adaptive(magi_handle* h, int drift_id, int P, int S,
+                            const double* x0, const double* theta,
+                            int T, const double* t_out, int method,
+                            double rtol, double atol, double h0, int max_steps,
+                            double* traj, double* mean, double* sd, int* status, int* reason,
+                            int* n_accepted, int* n_rejected, int* n_failed);
+
 /* ---- posterior summaries and convergence diagnostics ----------------------------------------- */
 
 /* Summaries of K scalar columns of C chains x R draws (unit csrc/summary.hip; what the reference's notebooks do on the host with

@@ -543,14 +543,17 @@ class MAGI_v2:
                 "minutes_elapsed": minutes}
 
     # ------------------------------------------------------------------------------------------
-    def posterior_trajectories(self, results, t_out=None, start_index: int = 0, substeps: int = 4, thin: int = 1, return_draws: bool = True):
+    def posterior_trajectories(self, results, t_out=None, start_index: int = 0, substeps: int = 4, thin: int = 1, return_draws: bool = True,
+                               method: str = "rk4", rtol: float = 1e-6, atol: float = 1e-9, h0: float = 0.0, max_steps: int = 100000):
         """The ODE solved on the GPU with every kept posterior draw (MagiEngine.ode_solve: classical RK4, ``substeps`` steps per output
         interval, the device's own drift code): draw k starts at ``results["X_samps"][..., k, start_index, :]`` with
         ``results["thetas_samps"][..., k, :]``; ``thin`` keeps every thin-th draw.  ``t_out``: the output times, default
         ``I[start_index:]``; any increasing grid whose first entry is ``I[start_index]`` will do, and one that runs past ``I[-1]``
         forecasts.  Returns dict(t [T], trajectories [draws, T, D] or None without ``return_draws``, mean [T, D], sd [T, D] (ddof = 1,
         over the draws whose trajectory stayed finite), status [draws] (0, or the index of the first non-finite output), n_failed).  With
-        a leading chain axis in ``results`` (n_chains > 1) trajectories and status keep it; mean and sd are over all chains' draws."""
+        a leading chain axis in ``results`` (n_chains > 1) trajectories and status keep it; mean and sd are over all chains' draws.
+        ``method="dopri5"`` or ``"ros23"`` (stiff systems) integrates with error control instead, to ``rtol`` and ``atol`` (``h0``,
+        ``max_steps``: MagiEngine.ode_solve); the result then also has reason, n_accepted and n_rejected per draw, shaped like status."""
         if results.get("X_samps") is None or results.get("thetas_samps") is None:
             raise ValueError("posterior_trajectories needs the draws: predict with keep_samples=True")
         I = np.asarray(results["I"], dtype=np.float64).reshape(-1)
@@ -560,15 +563,23 @@ class MAGI_v2:
         kept = X0.shape[:-1]                                  # lead + (draws,)
         t = I[start_index:] if t_out is None else np.asarray(t_out, dtype=np.float64).reshape(-1)
         assert t[0] == I[start_index], "t_out must start at I[start_index]"
+        adaptive = {} if method == "rk4" else dict(method=method, rtol=rtol, atol=atol, h0=h0, max_steps=max_steps)
         out = self.engine.ode_solve(X0.reshape(-1, self.D), th.reshape(-1, self.D_thetas), t, substeps=substeps, return_draws=return_draws,
-                                    drift=self.drift)
+                                    drift=self.drift, **adaptive)
         if out["n_failed"] > 0:
             import warnings
+            why = ""
+            if adaptive:
+                counts = np.bincount(out["reason"], minlength=4)
+                why = ": " + ", ".join(f"{int(counts[r])} {self.engine.ODE_REASONS[r]}" for r in (1, 2, 3) if counts[r])
             warnings.warn(f"posterior_trajectories: {out['n_failed']} of {out['status'].shape[0]} trajectories left the finite range "
-                          "(status > 0); mean and sd are over the others")
+                          f"(status > 0{why}); mean and sd are over the others")
         traj = out["trajectories"]
-        return {"t": t, "trajectories": None if traj is None else traj.reshape(kept + traj.shape[1:]), "mean": out["mean"], "sd": out["sd"],
-                "status": out["status"].reshape(kept), "n_failed": out["n_failed"]}
+        res = {"t": t, "trajectories": None if traj is None else traj.reshape(kept + traj.shape[1:]), "mean": out["mean"], "sd": out["sd"],
+               "status": out["status"].reshape(kept), "n_failed": out["n_failed"]}
+        for key in ("reason", "n_accepted", "n_rejected") if adaptive else ():
+            res[key] = out[key].reshape(kept)
+        return res
 
     def update_kernel_matrices(self, I_new, phi1s_new, phi2s_new):
         """magi_v2.py:433-462: new grid + hyper-parameters -> rebuild every component's matrices."""

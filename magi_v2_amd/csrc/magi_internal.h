@@ -771,7 +771,7 @@ template <> struct DriftT<MAGI_DRIFT_SIRW> {
 
 // ------------------------------------------------------------------------------------------
 // Time-dependent drifts (a traced f_vec that uses t: DriftT<>::TDEP).  The time of grid point i is pb.tgrid[i] (i < Np: the padding
-// holds the last time, no load needs a bounds test).  Every drift evaluation of every kernel goes through the five functions below; with
+// holds the last time, no load needs a bounds test).  Every drift evaluation of every kernel goes through the functions below; with
 // TDEP false the time is the constant 0.0 that nothing reads -- no load, no instruction -- and the members are called with the
 // signatures they have always had.
 // ------------------------------------------------------------------------------------------
@@ -804,6 +804,16 @@ __device__ __forceinline__ void drift_jt_at(const double (&x)[DR::D], const doub
                                             double (&t)[DR::P]) {
     if constexpr (DR::TDEP) DR::jt(x, th, tm, g, c, t);
     else DR::jt(x, th, g, c, t);
+}
+// o[d] = d f_d / d t at (x, tm): the emitted DriftT<>::ft of a time-dependent traced drift; every other drift has none and gets the
+// constant 0 that the optimiser drops
+template <class DR>
+__device__ __forceinline__ void drift_ft_at(const double (&x)[DR::D], const double (&th)[DR::P], double tm, double (&o)[DR::D]) {
+    if constexpr (DR::TDEP) DR::ft(x, th, tm, o);
+    else {
+#pragma unroll
+        for (int d = 0; d < DR::D; ++d) o[d] = 0.0;
+    }
 }
 template <class DR>
 __device__ __forceinline__ void drift_basis_at(const double (&x)[DR::D], double tm, double (&ph)[DR::D][DR::NBMAX]) {
@@ -1179,6 +1189,12 @@ int magi_launch(magi_handle* h, const char* what, void (*k)(P...), dim3 grid, di
     if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string(what) + hipGetErrorString(e));
     return MAGI_OK;
 }
+
+// ode.hip, for ode_adaptive.hip: both integrate into trj[T D][S_pad] with S_pad = roundup(S, MAGI_ODE_PAD) and status[S_pad]; R = T D.
+// magi_ode_stats: mean, sd [R] and n_failed over the draws with status 0 (k_ode_stats); magi_ode_transpose: out[S][R] (k_ode_transpose).
+constexpr int MAGI_ODE_PAD = 64;
+int magi_ode_stats(magi_handle* h, int S, int S_pad, int R, const double* trj, const int* status, double* mean, double* sd, int* n_failed);
+int magi_ode_transpose(magi_handle* h, int S, int S_pad, int R, const double* trj, double* out);
 
 // launchers implemented in logpost.hip / sampler.hip ---------------------------------------------
 int magi_launch_gradient(magi_handle* h, int n_chains, hipStream_t s);        // phases 1-3

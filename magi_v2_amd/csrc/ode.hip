@@ -9,6 +9,8 @@
 //                     then a butterfly -- one fixed summation order, bit-identical from run to run.
 //   k_ode_transpose   trj[T D][S_pad] -> the host layout [S][T D] through an LDS tile; launched only when the caller wants the draws.
 // Depends on the drift: a build for a traced drift compiles this unit again (it is not in jit._DRIFT_FREE).
+// The error-controlled integrators of csrc/ode_adaptive.hip share the layout and launch k_ode_stats / k_ode_transpose through
+// magi_ode_stats / magi_ode_transpose at the end of this file.
 #include "magi_internal.h"
 
 #include <cmath>
@@ -165,6 +167,17 @@ int solve(magi_handle* h, int P, int S, const double* x0, const double* theta, i
 }
 
 }  // namespace
+
+static_assert(ODE_WG == MAGI_ODE_PAD && TR_TILE == MAGI_ODE_PAD, "S_pad = roundup(S, MAGI_ODE_PAD) is what both kernels and the transpose's tiles assume");
+
+int magi_ode_stats(magi_handle* h, int S, int S_pad, int R, const double* trj, const int* status, double* mean, double* sd, int* n_failed) {
+    return magi_launch(h, "k_ode_stats: ", k_ode_stats, dim3((unsigned)R), dim3(STATS_WG), h->stream, S, S_pad, trj, status, mean, sd, n_failed);
+}
+
+int magi_ode_transpose(magi_handle* h, int S, int S_pad, int R, const double* trj, double* out) {
+    return magi_launch(h, "k_ode_transpose: ", k_ode_transpose, dim3((unsigned)(S_pad / TR_TILE), (unsigned)((R + TR_TILE - 1) / TR_TILE)), dim3(TR_TILE, 4),
+                       h->stream, S, S_pad, R, trj, out);
+}
 
 int magi_ode_solve(magi_handle* h, int drift_id, int P, int S, const double* x0, const double* theta, int T, const double* t_out, int substeps,
                    double* traj, double* mean, double* sd, int* status, int* n_failed) {

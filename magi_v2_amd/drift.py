@@ -49,6 +49,7 @@ class Drift:
     header: Optional[str] = None
     exprs: List = field(default_factory=list, repr=False)
     time_dependent: bool = False      # some component uses t: the device evaluates it at the handle's times (MagiEngine.set_times)
+    ft_np: Optional[Callable] = None  # (t[N,1] or [N], X[N,D], th[P]) -> d f / d t [N,D]; None unless time_dependent (it is zero)
 
     @property
     def is_builtin(self) -> bool:
@@ -248,6 +249,23 @@ def _header(sp, xs, ths, exprs, D: int, P: int, tag: str, tsym=None) -> str:
     cJ = [sum(ga[d] * J[d][k] for d in range(D)) for k in range(D)]          # (J^T g)_k
     cT = [sum(ga[d] * T[d][p] for d in range(D)) for p in range(P)]          # (T^T g)_p
     f_body = _emit_block(sp, pr, [(f"o[{d}] =", exprs[d]) for d in range(D)], subs)
+    # d f / d t, differentiated like J (the Rosenbrock integrator of csrc/ode_adaptive.hip needs it); a drift that does not use t has none
+    ft_member = ft_entry = ""
+    if tdep:
+        ft_body = _emit_block(sp, pr, [(f"o[{d}] =", sp.diff(exprs[d], tsym)) for d in range(D)], subs)
+        ft_member = f"""
+    // o[d] = df_d/dt
+    static __device__ __forceinline__ void ft(const double (&x)[{D}], const double (&th)[{P}], const double t_magi, double (&o)[{D}]) {{
+{ft_body}
+    }}"""
+        ft_entry = f"""__device__ __forceinline__ void user_drift_ft(const double* xp, const double* thp, const double t_magi, double* out) {{
+    double x[{D}], th[{P}], o[{D}];
+    for (int k = 0; k < {D}; ++k) x[k] = xp[k];
+    for (int k = 0; k < {P}; ++k) th[k] = thp[k];
+    DriftT<MAGI_DRIFT_USER>::ft(x, th, t_magi, o);
+    for (int k = 0; k < {D}; ++k) out[k] = o[k];
+}}
+"""
     jt_body = _emit_block(sp, pr, [(f"c[{k}] =", cJ[k]) for k in range(D)] + [(f"t[{p}] +=", cT[p]) for p in range(P)], subs)
     sel = " : ".join([f"d == {d} ? o[{d}]" for d in range(D - 1)] + [f"o[{D - 1}]"]) if D > 1 else "o[0]"
     sep_members = _sep_members(sp, pr, xs, ths, exprs, D, P, subs, tsym)
@@ -269,7 +287,7 @@ template <> struct DriftT<MAGI_DRIFT_USER> {{
     // c[k] = sum_d g[d] df_d/dx_k ; t[p] += sum_d g[d] df_d/dtheta_p
     static __device__ __forceinline__ void jt(const double (&x)[{D}], const double (&th)[{P}], {targ}const double (&g)[{D}], double (&c)[{D}], double (&t)[{P}]) {{
 {jt_body}
-    }}
+    }}{ft_member}
 {sep_members}
 }};
 // runtime-switch entry points of the reference-order (three-phase) kernels; t_magi: the time of the grid point
@@ -287,7 +305,7 @@ __device__ __forceinline__ void user_drift_jt(const double* xp, const double* th
     if (cout) for (int k = 0; k < {D}; ++k) cout[k] = c[k];
     if (tacc) for (int k = 0; k < {P}; ++k) tacc[k] += t[k];
 }}
-"""
+{ft_entry}"""
 
 
 def _numpy_evaluators(sp, xs, ths, exprs, D: int, P: int, tsym=None):
@@ -305,6 +323,7 @@ def _numpy_evaluators(sp, xs, ths, exprs, D: int, P: int, tsym=None):
     f_l = sp.lambdify(args, exprs, modules="numpy", cse=True, printer=pr)
     j_l = sp.lambdify(args, [J[d][k] for d in range(D) for k in range(D)], modules="numpy", cse=True, printer=pr)
     t_l = sp.lambdify(args, [T[d][p] for d in range(D) for p in range(P)], modules="numpy", cse=True, printer=pr)
+    ft_l = sp.lambdify(args, [sp.diff(e, tsym) for e in exprs], modules="numpy", cse=True, printer=pr) if tsym is not None else None
 
     def cols(X, th, t):
         X = np.asarray(X, dtype=np.float64)
@@ -330,7 +349,12 @@ def _numpy_evaluators(sp, xs, ths, exprs, D: int, P: int, tsym=None):
         Tv = np.stack([np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)) for v in t_l(*a)], axis=1).reshape(n, D, P)
         return Jv, Tv
 
-    return f_np, jac_np
+    def ft_np(t, X, th):
+        a = cols(X, th, t)
+        n = np.asarray(X).shape[0]
+        return np.stack([np.broadcast_to(np.asarray(v, dtype=np.float64), (n,)) for v in ft_l(*a)], axis=1)
+
+    return f_np, jac_np, (ft_np if tsym is not None else None)
 
 
 def trace_drift(f_vec: Callable, D: int, P: int, name: Optional[str] = None, allow_time: bool = False) -> Drift:
@@ -344,9 +368,9 @@ def trace_drift(f_vec: Callable, D: int, P: int, name: Optional[str] = None, all
     key = hashlib.sha256(("|".join(sp.srepr(e) for e in exprs) + f"|{D}|{P}").encode()).hexdigest()[:16]
     tag = name or f"user_{key}"
     tuse = tsym if tdep else None
-    f_np, jac_np = _numpy_evaluators(sp, xs, ths, exprs, D, P, tuse)
+    f_np, jac_np, ft_np = _numpy_evaluators(sp, xs, ths, exprs, D, P, tuse)
     return Drift(name=tag, D=D, P=P, device_id=USER_ID, f_np=f_np, jac_np=jac_np,
-                 header=_header(sp, xs, ths, exprs, D, P, tag, tuse), exprs=exprs, time_dependent=tdep)
+                 header=_header(sp, xs, ths, exprs, D, P, tag, tuse), exprs=exprs, time_dependent=tdep, ft_np=ft_np)
 
 
 def builtin_drift(name: str) -> Drift:
@@ -355,7 +379,7 @@ def builtin_drift(name: str) -> Drift:
     from .engine import DRIFT_SHAPES
     D, P = DRIFT_SHAPES[name]
     sp, xs, ths, _, exprs = _trace(host.NUMPY_DRIFTS[name], D, P)
-    _, jac_np = _numpy_evaluators(sp, xs, ths, exprs, D, P)
+    _, jac_np, _ = _numpy_evaluators(sp, xs, ths, exprs, D, P)
     return Drift(name=name, D=D, P=P, device_id=BUILTIN_IDS[name], f_np=host.NUMPY_DRIFTS[name], jac_np=jac_np, exprs=exprs)
 
 

@@ -161,6 +161,32 @@ def linear_oscillator(t, X, thetas):
 SIGNED_EXAMPLES = {"linear_oscillator": (linear_oscillator, 2, 3)}
 
 
+def robertson(t, X, thetas):
+    """Robertson's chemical kinetics: a' = -k1 a + k3 b c,  b' = k1 a - k3 b c - k2 b^2,  c' = k2 b^2;  theta = (k1, k2, k3), classically
+    (0.04, 3e7, 1e4) from (1, 0, 0).  Stiff: rates nine orders of magnitude apart."""
+    a, b, c = X[:, 0:1], X[:, 1:2], X[:, 2:3]
+    k1, k2, k3 = thetas[0], thetas[1], thetas[2]
+    return np.concatenate([-k1 * a + k3 * b * c, k1 * a - k3 * b * c - k2 * b ** 2, k2 * b ** 2], axis=1)
+
+
+def van_der_pol(t, X, thetas):
+    """Van der Pol oscillator: x' = y,  y' = mu (1 - x^2) y - x;  theta = (mu,).  A relaxation oscillator, stiff for large mu."""
+    x, y = X[:, 0:1], X[:, 1:2]
+    return np.concatenate([y, thetas[0] * (1.0 - x ** 2) * y - x], axis=1)
+
+
+def forced_relaxation(t, X, thetas):
+    """Fast relaxation onto a slow forcing, with the forcing's phase as a second component: x' = -k (x - cos(w t)),  p' = w;
+    theta = (k, w).  Time-dependent; stiff for large k."""
+    x = X[:, 0:1]
+    k, w = thetas[0], thetas[1]
+    return np.concatenate([-k * (x - np.cos(w * t)), w + 0.0 * x], axis=1)
+
+
+# stiff systems (adaptive integrators of csrc/ode_adaptive.hip: MagiEngine.ode_solve(method="ros23" / "dopri5"); tests/test_ode_adaptive_*.py)
+STIFF_EXAMPLES = {"robertson": (robertson, 3, 3), "van_der_pol": (van_der_pol, 2, 1), "forced_relaxation": (forced_relaxation, 2, 2)}
+
+
 def rk4(f_vec, x0, thetas, T, n, substeps=20, grid=None):
     """Reference trajectory on a uniform grid of n points over [0, T], or on ``grid`` (increasing times, its first the start): test data
     only.  The drift is given the current time."""

@@ -92,6 +92,8 @@ _SYMBOLS = {
     "magi_drift_probe": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp]),
     "magi_drift_probe_at": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "magi_ode_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _ip, _ip]),
+    "magi_ode_solve_adaptive": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_double,
+                                          C.c_int, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip]),
     "magi_summarize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int] + [_dp] * 6 + [_ip]),
     "magi_sampler_summarize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int] + [_dp] * 18 + [_ip]),
     "magi_elpd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp] + [_dp] * 6 + [_ip]),
@@ -243,13 +245,24 @@ class MagiEngine:
             self._check(self._lib.magi_drift_probe_at(self._h, drift_id, P, int(path), n, _ptr(X), _ptr(th), _ptr(g), _ptr(f), _ptr(c), _ptr(tt), _ptr(times)))
         return f, c, tt
 
-    def ode_solve(self, x0, theta, t_out, substeps=4, return_draws=True, drift=None):
+    ODE_METHODS = {"rk4": 0, "dopri5": 1, "ros23": 2}          # (1, 2: MAGI_ODE_DOPRI5, MAGI_ODE_ROS23 of include/magi_hip.h)
+    ODE_REASONS = ("none", "non-finite state", "step budget", "step underflow")
+
+    def ode_solve(self, x0, theta, t_out, substeps=4, return_draws=True, drift=None, method="rk4", rtol=1e-6, atol=1e-9, h0=0.0, max_steps=100000):
         """This library's drift integrated on the device for S draws at once (magi_ode_solve): draw s starts at x0[s] ([S, D]) with the
         parameters theta[s] ([S, P], natural scale) and is reported at the increasing times t_out[T] (output 0 is x0).  Classical RK4,
         ``substeps`` steps per output interval: the scheme of drift_examples.rk4.  Returns dict(trajectories [S, T, D] or None without
         ``return_draws``, mean [T, D], sd [T, D] (ddof = 1) over the draws with status 0, status [S] (0, or the index of the first
         non-finite output; 1 for a non-finite x0), n_failed).  ``drift``: built-in name or Drift; None: the Drift this engine was created for, else the drift
-        of the last set_problem."""
+        of the last set_problem.
+        ``method``: "rk4" (the above; the arguments behind it are not used), or an error-controlled integrator (magi_ode_solve_adaptive,
+        the controller is stated in include/magi_hip.h): "dopri5", Dormand-Prince 5(4), or "ros23", the Rosenbrock 2(3) pair of ode23s for
+        stiff systems, with relative and absolute tolerances ``rtol``, ``atol``, first step ``h0`` (0: the first output interval) and at
+        most ``max_steps`` accepted + rejected steps per draw (``substeps`` is not used).  The result then also holds reason [S]
+        (index into ODE_REASONS: a draw that ran out of steps or whose step underflowed has status j + 1 of the interval it did not
+        complete and NaN from there on), n_accepted [S] and n_rejected [S]."""
+        if method not in self.ODE_METHODS:
+            raise ValueError(f"unknown method {method!r}; one of {sorted(self.ODE_METHODS)}")
         if drift is None:
             drift = self.user_drift if self.user_drift is not None else getattr(self, "_problem_drift", None)
             if drift is None:
@@ -269,6 +282,14 @@ class MagiEngine:
         traj = np.empty((S, T, D)) if return_draws else None
         mean, sd = np.empty((T, D)), np.empty((T, D))
         status, nf = np.zeros(max(S, 1), dtype=np.int32), C.c_int32(0)
+        if method != "rk4":
+            reason, n_acc, n_rej = (np.zeros(max(S, 1), dtype=np.int32) for _ in range(3))
+            self._check(self._lib.magi_ode_solve_adaptive(self._h, drift_id, P, S, _ptr(x0), _ptr(theta), T, _ptr(t_out), self.ODE_METHODS[method],
+                                                          float(rtol), float(atol), float(h0), int(max_steps), _ptr(traj), _ptr(mean), _ptr(sd),
+                                                          status.ctypes.data_as(_ip), reason.ctypes.data_as(_ip), n_acc.ctypes.data_as(_ip),
+                                                          n_rej.ctypes.data_as(_ip), C.byref(nf)))
+            return {"trajectories": traj, "mean": mean, "sd": sd, "status": status[:S], "n_failed": int(nf.value), "reason": reason[:S],
+                    "n_accepted": n_acc[:S], "n_rejected": n_rej[:S]}
         self._check(self._lib.magi_ode_solve(self._h, drift_id, P, S, _ptr(x0), _ptr(theta), T, _ptr(t_out), int(substeps), _ptr(traj),
                                              _ptr(mean), _ptr(sd), status.ctypes.data_as(_ip), C.byref(nf)))
         return {"trajectories": traj, "mean": mean, "sd": sd, "status": status[:S], "n_failed": int(nf.value)}

@@ -1,6 +1,7 @@
 """Dev: kernel resource usage of csrc/leap.hip (hipcc -Rpass-analysis=kernel-resource-usage) + where in the ISA the scratch accesses sit.
     python tools/resource_usage.py > profiles/r03_kernel_resource_usage.txt
-    python tools/resource_usage.py selftest.hip          (another unit of csrc/: the table alone)"""
+    python tools/resource_usage.py selftest.hip          (another unit of csrc/: the table alone)
+    python tools/resource_usage.py ode.hip chain8        (the unit compiled for a traced drift of magi_v2_amd.drift_examples)"""
 import re, subprocess, sys, os, tempfile
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 WORK = tempfile.mkdtemp(prefix="magi_ru_")          # (hipcc --save-temps writes into the working directory)
@@ -9,13 +10,21 @@ sys.path.insert(0, ROOT)
 from magi_v2_amd import build
 unit = sys.argv[1] if len(sys.argv) > 1 else "leap.hip"
 src = os.path.join(build.CSRC, unit)
-r = subprocess.run(build.compile_command(src, ["-Rpass-analysis=kernel-resource-usage"]) + ["-c", src, "-o", os.path.join(WORK, unit[:-4] + "_ru.o"), "--save-temps"],
+extra = []
+if len(sys.argv) > 2:
+    from magi_v2_amd import drift, drift_examples, jit
+    ex = {k: v for name in dir(drift_examples) if name.endswith("EXAMPLES") for k, v in getattr(drift_examples, name).items()}
+    d = drift.resolve(*ex[sys.argv[2]])
+    with open(os.path.join(WORK, "user_drift.h"), "w") as fh:
+        fh.write(d.header)
+    extra = jit.drift_flags(d, os.path.join(WORK, "user_drift.h"))
+r = subprocess.run(build.compile_command(src, extra + ["-Rpass-analysis=kernel-resource-usage"]) + ["-c", src, "-o", os.path.join(WORK, unit[:-4] + "_ru.o"), "--save-temps"],
                    capture_output=True, text=True)
 if r.returncode != 0:
     sys.exit(r.stderr[-4000:])
 txt = r.stderr
 blocks = re.split(r"remark: [^\n]*Function Name: ", txt)[1:]
-print("# hipcc -O3 --offload-arch=gfx950 -ffp-contract=on -Rpass-analysis=kernel-resource-usage magi_v2_amd/csrc/%s  (ROCm 7.2)" % unit)
+print("# hipcc -O3 --offload-arch=gfx950 -ffp-contract=on -Rpass-analysis=kernel-resource-usage magi_v2_amd/csrc/%s%s  (ROCm 7.2)" % (unit, " for the traced drift " + sys.argv[2] if extra else ""))
 print("# kernel | VGPRs | VGPR spills | SGPR spills | scratch B/lane | occupancy waves/SIMD | LDS B/block")
 KEYS = ["    VGPRs", "VGPRs Spill", "SGPRs Spill", r"ScratchSize \[bytes/lane\]", r"Occupancy \[waves/SIMD\]", r"LDS Size \[bytes/block\]"]
 for b in blocks:
