@@ -539,6 +539,64 @@ int magi_sampler_elpd(magi_handle* h, int chain0, int n_sel,
                       double* lpd, double* p_waic, double* elpd_waic, double* elpd_loo, double* p_loo, double* khat,
                       int* obs_index, int* n_obs_out, double* loglik_out, int* n_nonfinite);
 
+/* ---- posterior trajectories at any time: GP conditioning ---------------------------------------- */
+
+/* Matern cross blocks (unit csrc/build.hip: k_matern_cross, the rectangular sibling of the kernel behind magi_matern_blocks).  Row times
+ * t_new[T] against column times I[N]: Ks[m][j] = k(t_new[m], I[j]) and pKs[m][j] = d k / d t* at (t_new[m], I[j]), the derivative in the
+ * FIRST argument (the sign convention of p_Kappa).  Same Bessel routine, recurrences and exponent forms as magi_matern_blocks, entry by
+ * entry: with t_new = I the two outputs equal its Kappa and p_Kappa bit for bit.  The coincident-time values (phi1, 0) are taken where
+ * t_new[m] == I[j] EXACTLY, not by index.  Ks, pKs: host [T][N], either may be NULL.  Needs a handle only for its device and stream.
+ * MAGI_E_BADARG (handle stays usable): T outside [1, 2^16], N outside [1, 2^20], T N > 2^28, t_new or I NULL or not finite, phi1, phi2
+ * not positive, nu <= 1. */
+int magi_matern_cross(magi_handle* h, const double* t_new, int T, const double* I, int N,
+                      double phi1, double phi2, double nu, double* Ks, double* pKs);
+
+/* The draws of the trajectory at times t_new that need not be grid points (unit csrc/gp.hip).  Under MAGI's model, given a
+ * draw's x_d(I), x_d(t*) is Gaussian.  Per component d, with C^-1_d the handle's resident dense stack AS STORED, UNTRANSPOSED and not
+ * symmetrised (an uploaded matrix need not be symmetric), Ks_d and pKs_d the cross blocks of magi_matern_cross with (phi1[d], phi2[d], nu):
+ *   W_d = Ks_d C^-1_d,  Wd_d = pKs_d C^-1_d         [T][N]: rows of Ks times columns of C^-1, W_d[m][k] = sum_j Ks_d[m][j] C^-1_d[j][k]
+ *   x_new[s][m][d]  = mu_d + sum_k W_d[m][k] (X_s[k][d] - mu_d)        the conditional mean of x_d(t_new[m]) given draw s
+ *   dx_new[s][m][d] =        sum_k Wd_d[m][k] (X_s[k][d] - mu_d)       the conditional mean of its derivative (at a grid time: m_d (x_d - mu_d))
+ *   cond_var[m][d]  = max(0, phi1_d - sum_k W_d[m][k] Ks_d[m][k])      the conditional variance, the same for every draw
+ *   dcond_var[m][d] = max(0, nu phi1_d / (phi2_d^2 (nu - 1)) - sum_k Wd_d[m][k] pKs_d[m][k])
+ * The variances are clamped at 0: in floating point the difference reaches about -1e-11 at grid times, where it is 0.
+ * Arithmetic: x_new = g + mu_d (1 - r) and dx_new = gd - mu_d rd, with g = sum_k W_d[m][k] X_s[k][d] and gd its twin accumulated by the fp64
+ * matrix-core GEMM, k ascending, and r = sum_k W_d[m][k], rd = sum_k Wd_d[m][k] summed in one fixed order from the same W, Wd: mu is never
+ * subtracted from a draw.  Results are bit-identical from run to run and do not depend on the chunking (gp_chunk_rows).
+ * x_new and dx_new are CONDITIONAL MEANS: a draw of x(t*) itself is x_new + sqrt(cond_var) z with z ~ N(0, 1) per (s, m, d), and the
+ * predictive sd of x(t*) is sqrt(x_sd^2 + cond_var) with x_sd the sd of x_new over the draws.  Outside [min I, max I] the mean reverts to mu
+ * and the variance to phi1.  t_new need not be sorted or distinct and may coincide with grid times; I need not be sorted.
+ * X: host [S][N][D].  x_new, dx_new: host [S][T][D]; cond_var, dcond_var: host [T][D]; every output is optional.
+ * MAGI_E_STATE without resident dense matrices of this N, D (magi_build_matrices, magi_build_dense, magi_set_matrices).  MAGI_E_BADARG
+ * (handle stays usable): T outside [1, 2^16], S outside [1, 2^20], x_new or dx_new asked for with S T D > 2^28, N < 2, D outside
+ * [1, MAGI_MAX_D], a NULL input, a non-finite t_new, I or mu, phi1 or phi2 not positive, nu <= 1.  Device memory of a call: the rows of
+ * t_new go in chunks so that none of the buffers (cross blocks, weights, the two chunks of draws, their staging) exceeds 64 MiB unless a
+ * single row needs more; the draws X themselves are uploaded whole. */
+int magi_gp_predict(magi_handle* h, const double* I, int N, int D, const double* phi1, const double* phi2, double nu,
+                    const double* mu, int T, const double* t_new, int S, const double* X,
+                    double* x_new, double* dx_new, double* cond_var, double* dcond_var);
+
+/* The same for the finished sampler run, from its device-resident samples of the chains [chain0, chain0 + n_sel) read in place (no draw
+ * is copied, transposed or downloaded), with mu the problem's and N, D the problem's; I, phi1, phi2, nu are the caller's: the grid and the
+ * hyper-parameters the resident matrices were built with (an uploaded C^-1 is used as it is).  x_new, dx_new: host
+ * [n_sel num_results][T][D] -- bit for bit what magi_gp_predict returns for the downloaded samples.  The twelve summaries, [T][D] and
+ * quant [n_q][T][D], are the statistics of magi_summarize over x_new and over dx_new as [n_sel][num_results][T D] draws, bit for bit, computed
+ * on the device; *n_nonfinite counts the columns of x_new with a non-finite draw, and those of dx_new when a dx statistic is asked for.
+ * Every output is optional.  MAGI_E_STATE / MAGI_E_BADARG as magi_sampler_summarize (sampler initialised, every selected chain finished,
+ * the chain range inside the sampler's chains and inside one member of a group: the matrices and mu are that member's) and as
+ * magi_gp_predict (S = n_sel num_results); MAGI_E_STATE also when the resident dense matrices are not the problem's N, D. */
+int magi_sampler_gp_predict(magi_handle* h, int chain0, int n_sel, const double* I, const double* phi1, const double* phi2, double nu,
+                            int T, const double* t_new, int n_q, const double* probs, int max_lag,
+                            double* x_new, double* dx_new, double* cond_var, double* dcond_var,
+                            double* x_mean, double* x_sd, double* x_quant, double* x_rhat, double* x_ess, double* x_mcse_mean,
+                            double* dx_mean, double* dx_sd, double* dx_quant, double* dx_rhat, double* dx_ess, double* dx_mcse_mean,
+                            int* n_nonfinite);
+
+/* Diagnostics: device time (ms, HIP events) of the stages of the last magi_gp_predict / magi_sampler_gp_predict made while the switch
+ * gp_profile was set -- cross blocks; weights and variances; the application GEMM; its mu epilogue; statistics -- zeros otherwise (the
+ * transposes and downloads of x_new / dx_new are not among them).  ms: 5 entries. */
+int magi_gp_profile(magi_handle* h, double* ms);
+
 /* ---- multi-GPU ---------------------------------------------------------------------------------
  * There is deliberately NO magi_gather in this ABI (SURVEY 8b had listed one).  The path shards by independent (dataset, chain) units with
  * no exchange while sampling (one handle per GPU, one process per GPU); its only collective is ONE gather of the post-burn-in samples at
@@ -601,7 +659,9 @@ int magi_stream_kernel_name(magi_handle* h, int n_chains, char* buf, int cap);
  *   "slot_budget_graphs"  (none: a test hook)       cap on the graph launches of one magi_sampler_run; 0 = the computed bound
  * Beside the options, one test switch of the summaries (no environment variable, no effect on any result): summary_chunk_cols, 0..2^24;
  * > 0: magi_summarize / magi_sampler_summarize and magi_elpd / magi_sampler_elpd gather at most this many columns per chunk (0 = what the
- * work space allows). */
+ * work space allows).  Likewise the two of the GP conditioning: gp_chunk_rows, 0..2^16; > 0: magi_gp_predict / magi_sampler_gp_predict work on
+ * at most this many rows of t_new per chunk (no effect on any result); gp_profile, a flag: they time their stages (magi_gp_profile; a
+ * synchronisation per stage). */
 int magi_set_option(magi_handle* h, const char* name, int64_t value);
 
 /* Diagnostics: per-class device time of the last magi_build_matrices run with option "build_profile" set

@@ -431,6 +431,39 @@ class MAGI_v2:
             raise RuntimeError("posterior_summary summarises the samples of the last predict: run predict first")
         return self.engine.sampler_summary(probs=probs, max_lag=max_lag)
 
+    @staticmethod
+    def _posterior_at_result(r, derivative, return_draws):
+        """The dictionary ``posterior_at`` returns, from MagiEngine.sampler_gp_predict's."""
+        out = {"t": r["t"], "X": r["X"], "cond_sd": np.sqrt(r["cond_var"]), "pred_sd": np.sqrt(r["X"]["sd"] ** 2 + r["cond_var"]),
+               "probs": r["probs"], "n_nonfinite": r["n_nonfinite"]}
+        if derivative:
+            out.update(dX=r["dX"], dcond_sd=np.sqrt(r["dcond_var"]))
+        if return_draws:
+            out["X_draws"] = r["X_draws"]
+            if derivative:
+                out["dX_draws"] = r["dX_draws"]
+        return out
+
+    def posterior_at(self, t_new, probs=DEFAULT_PROBS, max_lag: int = 0, derivative: bool = True, return_draws: bool = False):
+        """The inferred trajectory of the last ``predict`` at the times ``t_new`` [T], which need not be grid points: a smooth band between
+        them, the state at a held-out measurement's time, the derivative x'(t) that MAGI matches to f(x, theta), a short extrapolation
+        under the GP alone.  Under MAGI's model x_d(t*) given a draw's x_d(I) is Gaussian with mean mu_d + k_d(t*, I) C_d^-1 (x_d(I) - mu_d)
+        and a variance that does not depend on the draw (include/magi_hip.h: magi_sampler_gp_predict); the call conditions every
+        device-resident draw on the GPU, all chains pooled, and nothing but the results crosses to the host -- legal after
+        ``keep_samples=False``.  It uses the model's current grid ``I`` and the ``phi1s`` / ``phi2s`` the resident matrices were built
+        with; a user who overwrote ``C_d_invs`` gets their own matrix (as stored, neither symmetrised nor transposed), with phi as the
+        model holds them in the cross blocks and the prior variances.
+        Returns dict(t [T]; X: mean, sd, rhat, ess, mcse_mean [T, D] and quantiles [len(probs), T, D] of the CONDITIONAL MEANS over the
+        draws; cond_sd [T, D], the sd of x(t*) about its conditional mean; pred_sd = sqrt(sd^2 + cond_sd^2), the predictive sd of x(t*);
+        probs; n_nonfinite; with ``derivative`` dX and dcond_sd, the same for x'(t*); with ``return_draws`` X_draws (and dX_draws)
+        [chains, draws, T, D], the conditional means per draw: a draw of x(t*) itself is X_draws + cond_sd * z, z ~ N(0, 1)).  Outside
+        [min I, max I] the mean reverts to ``mu_ds`` and cond_sd to sqrt(phi1)."""
+        if not getattr(self, "_predicted", False):
+            raise RuntimeError("posterior_at conditions the samples of the last predict: run predict first")
+        r = self.engine.sampler_gp_predict(self.I, self.phi1s, self.phi2s, t_new, nu=2.01, probs=probs, max_lag=max_lag, derivative=derivative,
+                                           return_draws=return_draws)
+        return self._posterior_at_result(r, derivative, return_draws)
+
     def posterior_elpd(self, scale: str = "data", loglik: bool = False, loo: Optional[bool] = None):
         """Pointwise log predictive density, WAIC and PSIS-LOO of the last ``predict``, all its chains pooled, computed on the GPU from the
         samples the sampler left there (MagiEngine.sampler_elpd; definitions in include/magi_hip.h).  The likelihood of an observation is
@@ -634,7 +667,7 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
                  n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[Sequence[int]]] = None,
                  stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
                  summary: bool = False, keep_samples: bool = True, theta_support=None, theta_prior=None, sigma_sq_prior=None,
-                 obs_link=None, obs_weight=None, elpd: bool = False):
+                 obs_link=None, obs_weight=None, elpd: bool = False, posterior_at=None):
     """``predict`` for several models (after their ``initial_fit``) at once.  Models of one library, device and problem shape are sampled
     as one problem group on their GPU -- one captured graph, one kernel pair per leapfrog slot for all their chains -- and the others by
     their own ``predict``.  ``sigma_sqs_LB``: None (each model's default) or one entry per model; ``chain_ids``: None (0 .. n_chains - 1
@@ -646,9 +679,11 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
     for all models (entries None, "flat", ("normal", m, s), ... as in ``predict``) or one per model.  ``obs_link`` / ``obs_weight``: likewise
     None, one specification for all models (a link name, or one name per component; one weight array) or one per model (a list of such
     specifications / of arrays or None); the members of one group may differ.  ``elpd`` as in ``predict``: one ``results["elpd"]`` per
-    model, a grouped model's from its own chains and observation model."""
-    if not keep_samples and not (summary or elpd):
-        raise ValueError("keep_samples=False needs summary=True or elpd=True: the call would return nothing of the posterior")
+    model, a grouped model's from its own chains and observation model.  ``posterior_at``: None, or times t_new [T]: adds
+    ``results["posterior_at"]`` = that model's ``MAGI_v2.posterior_at(t_new)`` (a grouped model's through the group's handle and its
+    member index, from its own chains, matrices and mu); legal with ``keep_samples=False``."""
+    if not keep_samples and not (summary or elpd or posterior_at is not None):
+        raise ValueError("keep_samples=False needs summary=True, elpd=True or posterior_at: the call would return nothing of the posterior")
     models = list(models)
     n = len(models)
     lbs = [None] * n if sigma_sqs_LB is None else list(sigma_sqs_LB)
@@ -687,8 +722,13 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
     for grp in partition_for_groups([group_key(m, n_chains) for m in models]):
         if len(grp) == 1:
             k = grp[0]
-            out[k] = models[k].predict(num_results, num_burnin_steps, lbs[k], verbose, chain_ids=ids[k], summary=summary, keep_samples=keep_samples,
+            only_at = not (keep_samples or summary or elpd)          # (predict wants a reason of its own to drop the draws)
+            out[k] = models[k].predict(num_results, num_burnin_steps, lbs[k], verbose, chain_ids=ids[k], summary=summary or only_at, keep_samples=keep_samples,
                                         theta_support=sups[k], theta_prior=tpri[k], sigma_sq_prior=spri[k], obs_link=olnk[k], obs_weight=owts[k], elpd=elpd, **kw)
+            if only_at:
+                del out[k]["summary"]
+            if posterior_at is not None:
+                out[k]["posterior_at"] = models[k].posterior_at(posterior_at)
             continue
         g = MagiGroup([models[k].engine for k in grp])
         try:
@@ -712,6 +752,8 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
             summaries = [g.sampler_summary(member=j) for j in range(len(grp))] if summary else None
             elpds = [g.sampler_elpd(member=j, loo=host.elpd_wants_loo(n_chains * num_results))
                      for j in range(len(grp))] if elpd else None
+            ats = [g.sampler_gp_predict(models[k].I, models[k].phi1s, models[k].phi2s, posterior_at, member=j)
+                   for j, k in enumerate(grp)] if posterior_at is not None else None
         finally:
             g.close()
         for j, k in enumerate(grp):
@@ -723,4 +765,6 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
                 out[k]["summary"] = _warn_if_stuck(summaries[j])
             if elpd:
                 out[k]["elpd"] = models[k]._elpd_on_scale(elpds[j], "data")
+            if posterior_at is not None:
+                out[k]["posterior_at"] = MAGI_v2._posterior_at_result(ats[j], True, False)
     return out

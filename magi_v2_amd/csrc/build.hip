@@ -171,6 +171,66 @@ __global__ __launch_bounds__(256) void k_matern(MaternArgs a) {
     }
 }
 
+// The rectangular sibling of k_matern: Ks[m][j] = k(t*_m, I_j) and pKs[m][j] = d k / d t* (the derivative in the FIRST argument, the sign
+// convention of p_Kappa) for T row times against the N grid times -- the cross blocks of GP conditioning (gp.hip).  Same Bessel
+// routine, recurrences and f = exp(logA + nu log u - u) forms, entry by entry, so that t* = I reproduces Kappa / p_Kappa bit for bit.
+// The coincident-time branch is taken on EQUAL TIMES (a row time need not be a grid point, and a grid may repeat no time but a row may
+// repeat a grid time); Kappa_pp is not formed: conditioning needs only its coincident value diag_pp.  Either output may be null.
+struct MaternCrossArgs {
+    const double *tnew, *I;
+    double *Ks, *pKs;
+    int T, N;
+    double phi1, nu, c, logA;
+    BesselConsts bc;
+    int rows;                  // row times per workgroup (64, fewer on small problems: as MaternArgs::rows)
+};
+
+__global__ __launch_bounds__(256) void k_matern_cross(MaternCrossArgs a) {
+    __shared__ double ts[64], tt[64];
+    const int i0 = blockIdx.y * a.rows, j0 = blockIdx.x * 64;
+    if (threadIdx.x < 64) {
+        const int i = i0 + threadIdx.x;
+        ts[threadIdx.x] = (i < a.T) ? a.tnew[i] : 0.0;
+    } else if (threadIdx.x < 128) {
+        const int j = j0 + threadIdx.x - 64;
+        tt[threadIdx.x - 64] = (j < a.N) ? a.I[j] : 0.0;
+    }
+    __syncthreads();
+    const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+    for (int r = ty; r < a.rows; r += 4) {
+        const int i = i0 + r, j = j0 + tx;
+        if (i >= a.T || j >= a.N) continue;
+        double kap, pk;
+        if (ts[r] == tt[tx]) {
+            kap = a.phi1; pk = 0.0;
+        } else {
+            const double dt = ts[r] - tt[tx];
+            const double u = a.c * fabs(dt);
+            double k0, k1;                       // scaled K_mu, K_{mu+1}
+            bessel_k_scaled(u, a.bc, k0, k1);
+            double km2, km1, kn;                 // recur to K_{nu-1}, K_nu as k_matern does
+            if (a.bc.n == 1) {
+                km1 = k0; kn = k1;
+            } else {
+                km2 = k0; km1 = k1;
+                double ord = a.bc.mu + 1.0;
+                kn = km2 + 2.0 * ord / u * km1;
+                for (int t = 2; t < a.bc.n; ++t) {
+                    km2 = km1; km1 = kn; ord += 1.0;
+                    kn = km2 + 2.0 * ord / u * km1;
+                }
+            }
+            const double lu = log(u);
+            const double f = exp(a.logA + a.nu * lu - u);              // A u^nu e^-u
+            kap = f * kn;
+            pk = -(dt > 0.0 ? 1.0 : -1.0) * a.c * f * km1;
+        }
+        const size_t o = (size_t)i * a.N + j;
+        if (a.Ks) a.Ks[o] = kap;
+        if (a.pKs) a.pKs[o] = pk;
+    }
+}
+
 // =============================================================================================
 // fp64 MFMA GEMM:  C(m,n) = alpha * sum_k A(m,k) B(n,k) + beta * C(m,n)
 //   A(m,k) = A[m*sAm + k*sAk],  B(n,k) = B[n*sBn + k*sBk]  (arbitrary strides -> NN / NT / TN)
@@ -1459,6 +1519,35 @@ int magi_matern_blocks_device(magi_handle* h, const double* I, int N, double phi
     if (p_Kappa) MAGI_HIP_CHECK(h, hipMemcpy(p_Kappa, dP.p, nn * sizeof(double), hipMemcpyDeviceToHost));
     if (Kappa_pp) MAGI_HIP_CHECK(h, hipMemcpy(Kappa_pp, dPP.p, nn * sizeof(double), hipMemcpyDeviceToHost));
     return MAGI_OK;
+}
+
+int magi_matern_cross_launch(magi_handle* h, hipStream_t s, const double* dT, int T, const double* dI, int N, double phi1, double phi2, double nu,
+                             double* dKs, double* dPKs) {
+    MaternCrossArgs a{};
+    a.tnew = dT; a.I = dI; a.Ks = dKs; a.pKs = dPKs; a.T = T; a.N = N;
+    a.phi1 = phi1; a.nu = nu; a.c = std::sqrt(2.0 * nu) / phi2;                 // (the scalars exactly as launch_matern forms them)
+    a.logA = std::log(phi1) + (1.0 - nu) * std::log(2.0) - std::lgamma(nu);
+    a.bc = bessel_consts(nu);
+    a.rows = 64;
+    while (a.rows > 4 && (long)((N + 63) / 64) * ((T + a.rows - 1) / a.rows) < 1024) a.rows /= 2;
+    dim3 grid((N + 63) / 64, (T + a.rows - 1) / a.rows);
+    hipLaunchKernelGGL(k_matern_cross, grid, dim3(256), 0, s, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("matern cross launch: ") + hipGetErrorString(e));
+    return MAGI_OK;
+}
+
+double magi_matern_diag_pp(double phi1, double phi2, double nu) { return nu * phi1 / ((phi2 * phi2) * (nu - 1.0)); }
+
+int magi_gemm_strided(magi_handle* h, hipStream_t s, const MagiGemm& d) {
+    GemmArgs g{};
+    g.A = d.A; g.sAm = d.sAm; g.sAk = d.sAk;
+    g.B = d.B; g.sBn = d.sBn; g.sBk = d.sBk;
+    g.C = d.C; g.ldc = d.ldc; g.M = d.M; g.N = d.N; g.K = d.K; g.alpha = 1.0; g.beta = 0.0;
+    g.zinner = d.inner;
+    g.batchA = d.batchA; g.batchB = d.batchB; g.batchC = d.batchC;
+    g.batchA2 = d.batchA2; g.batchB2 = d.batchB2; g.batchC2 = d.batchC2;
+    return launch_gemm(h, s, g, d.inner * d.outer);
 }
 
 int magi_build_profile_get(const magi_handle* h, double* flops, double* ms, long* calls) {

@@ -1415,6 +1415,16 @@ int magi_set_option(magi_handle* h, const char* name, int64_t value) {
         h->opt.summary_chunk_cols = (int)value;
         return MAGI_OK;
     }
+    // likewise the two of csrc/gp.hip: its chunk size (no result depends on it) and its per-stage timing (magi_gp_profile)
+    if (std::strcmp(name, "gp_chunk_rows") == 0) {
+        if (value < 0 || value > (1 << 16)) return magi_fail(h, MAGI_E_BADARG, "gp_chunk_rows in [0, 65536]");
+        h->opt.gp_chunk_rows = (int)value;
+        return MAGI_OK;
+    }
+    if (std::strcmp(name, "gp_profile") == 0) {
+        h->opt.gp_profile = value != 0;
+        return MAGI_OK;
+    }
     for (const OptRow& r : kOptions) {
         if (std::strcmp(r.name, name) != 0) continue;
         if (set_option(h->opt, r, value)) return MAGI_OK;

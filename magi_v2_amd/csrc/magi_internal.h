@@ -1050,6 +1050,8 @@ struct MagiOptions {
     int potrf_lookahead_min = 4096;     // build.hip: grids from this size on factorise with look-ahead (0: never), see potrf
     long long slot_budget_graphs = 0;   // TEST HOOK: cap on the graph launches of one magi_sampler_run (0 = the computed bound)
     int summary_chunk_cols = 0;         // TEST HOOK: summary.hip gathers at most this many columns per chunk (0 = what the work space allows)
+    int gp_chunk_rows = 0;              // TEST HOOK: gp.hip works on at most this many rows of t_new per chunk (0 = what the work space allows)
+    int gp_profile = 0;                 // gp.hip: per-stage device times (HIP events, a synchronisation per stage; read by magi_gp_profile)
     int no_graph = 0;                   // launch the leapfrog slots directly (debugging, long rocprofv3 kernel traces)
     int fit_host_loop = 0;              // build.hip: the hyper-parameter fit with its scalar tail on the host (the tests' reference)
     int build_profile = 0, build_serial = 0;           // build.hip: per-class device times (serialises), one component per group
@@ -1155,6 +1157,7 @@ struct magi_handle {
     hipEvent_t ev_pw[4] = {nullptr, nullptr, nullptr, nullptr};      // begin / end of the two factorisations of a dense build
     double potrf_wall_ms = 0.0, potrf_wall_flops = 0.0;              // of the last dense build (whole factorisations, not serialised)
     BuildProfile prof;                                               // of the last profiled dense build of THIS handle (build.hip)
+    double gp_ms[5] = {};            // gp.hip: cross blocks, weights, application GEMM, its mu epilogue, statistics of the last call under the option gp_profile
     size_t apply_pin_cap = 0;
     // problem group (magi_group_create): group_n > 0 members whose chains this handle samples; it has no matrices of its own
     int group_n = 0;
@@ -1241,5 +1244,29 @@ int magi_ensure_dense(magi_handle* h, int N, int D);
 int magi_dense_apply_device(magi_handle* h, int which, int trans, int nv, const double* dV, double* dY);
 // thetainit.hip: Adam x iters on the theta objective of magi_v2.py:148-158 with the resident UNbanded stacks, one captured graph per step
 int magi_theta_init_device(magi_handle* h, int drift, int P, const double* Xhat, const double* mu, int iters, double lr, double* theta, double* loss_trace);
+// build.hip, for gp.hip: Ks, pKs (device [T][N], either may be null) = k, dk/dt* of the row times dT[T] against the grid times dI[N]
+// (k_matern_cross: k_matern's arithmetic entry by entry, the coincident branch on equal times); the coincident value of Kappa_pp
+int magi_matern_cross_launch(magi_handle* h, hipStream_t s, const double* dT, int T, const double* dI, int N, double phi1, double phi2, double nu,
+                             double* dKs, double* dPKs);
+double magi_matern_diag_pp(double phi1, double phi2, double nu);
+// build.hip: the strided fp64 MFMA GEMM of the matrix build (k_gemm_f64 through launch_gemm), C(m, n) = sum_k A(m, k) B(n, k) with
+// A(m, k) = A[m sAm + k sAk], B(n, k) = B[n sBn + k sBk], C(m, n) = C[m ldc + n], over inner x outer batches: batch* step the inner index,
+// batch*2 the outer one.  Every output's k loop runs in the same order whatever the shape and the strides.
+struct MagiGemm {
+    const double* A; long sAm, sAk, batchA, batchA2;
+    const double* B; long sBn, sBk, batchB, batchB2;
+    double* C; long ldc, batchC, batchC2;
+    int M, N, K, inner, outer;
+};
+int magi_gemm_strided(magi_handle* h, hipStream_t s, const MagiGemm& g);
+// summary.hip: the statistics of magi_summarize for K columns of C x R draws that are ALREADY on the device in chunk layout
+// (chunk[column][C R], what the gathers of summarize_block produce for a plain block): begin allocates the result arrays, every
+// chunk call runs k_sum_moments / k_sum_ess / k_sum_order on columns [k0, k0 + nc) as summarize_block does, end downloads what the
+// caller wants (null: not), waits for the stream and releases everything -- it is also the clean-up of an error path.
+struct MagiColStats;
+int magi_colstats_begin(magi_handle* h, const char* who, int C, int R, long long K, int max_cols, int n_q, const double* probs, int max_lag,
+                        bool want_ess, bool want_quant, MagiColStats** out);
+int magi_colstats_chunk(magi_handle* h, MagiColStats* st, const double* dchunk, int nc, long long k0);
+int magi_colstats_end(magi_handle* h, MagiColStats* st, double* mean, double* sd, double* quant, double* rhat, double* ess, double* mcse, int* nonfinite);
 int magi_matern_blocks_device(magi_handle* h, const double* I, int N, double phi1, double phi2, double nu,
                               double* Kappa, double* p_Kappa, double* Kappa_pp);

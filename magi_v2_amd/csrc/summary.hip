@@ -353,6 +353,78 @@ int check_probs(magi_handle* h, const char* who, int n_q, const double* probs, S
 
 }  // namespace
 
+// The device-source route for columns already in chunk layout (magi_internal.h; gp.hip): the launches of summarize_block without its gather.
+struct MagiColStats {
+    const char* who;
+    int C, R, n_q, max_lag, max_cols;
+    long long K;
+    bool want_ess, want_q;
+    SumProbs probs;
+    double *buf, *yb, *col, *mean, *sd, *rhat, *ess, *mcse, *quant;
+    int* count;
+};
+
+int magi_colstats_begin(magi_handle* h, const char* who, int C, int R, long long K, int max_cols, int n_q, const double* probs, int max_lag,
+                        bool want_ess, bool want_quant, MagiColStats** out) {
+    *out = nullptr;
+    SumProbs pr;
+    int rc = check_draws(h, who, C, R);
+    if (rc == MAGI_OK) rc = check_probs(h, who, n_q, probs, pr);
+    if (rc) return rc;
+    MagiColStats* st = new MagiColStats{};
+    st->who = who; st->C = C; st->R = R; st->n_q = n_q; st->max_lag = max_lag; st->max_cols = max_cols; st->K = K;
+    st->want_ess = want_ess; st->want_q = want_quant && n_q > 0; st->probs = pr;
+    const size_t cc = (size_t)max_cols, n_yb = R >= 4 ? cc * 2 * (size_t)C : 0, nq = st->want_q ? (size_t)n_q * K : 0;
+    // one device buffer: ybar (cc 2 C) | col (cc 4) | mean, sd, rhat, ess, mcse (K each) | quant (n_q K) | the counter (1 int)
+    hipError_t e = hipMalloc((void**)&st->buf, (n_yb + cc * 4 + 5 * (size_t)K + nq) * sizeof(double) + sizeof(int));
+    if (e != hipSuccess) {
+        delete st;
+        return magi_fail(h, MAGI_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    }
+    st->yb = st->buf; st->col = st->yb + n_yb; st->mean = st->col + cc * 4; st->sd = st->mean + K; st->rhat = st->sd + K; st->ess = st->rhat + K;
+    st->mcse = st->ess + K; st->quant = st->mcse + K;
+    st->count = reinterpret_cast<int*>(st->quant + nq);
+    *out = st;
+    MAGI_HIP_CHECK(h, hipMemsetAsync(st->count, 0, sizeof(int), h->stream));
+    return MAGI_OK;
+}
+
+int magi_colstats_chunk(magi_handle* h, MagiColStats* st, const double* chunk, int nc, long long k0) {
+    if (nc < 1 || nc > st->max_cols || k0 < 0 || k0 + nc > st->K) return magi_fail(h, MAGI_E_BADARG, std::string(st->who) + ": statistics chunk out of range");
+    const int C = st->C, R = st->R;
+    int rc = magi_launch(h, "k_sum_moments: ", k_sum_moments, dim3((unsigned)nc), dim3(SUM_WG), h->stream, C, R, chunk, st->yb, st->col, k0, (int)MODE_PLAIN, 1, 1,
+                         st->mean, st->sd, st->rhat, st->count);
+    if (rc == MAGI_OK && st->want_ess)
+        rc = magi_launch(h, "k_sum_ess: ", k_sum_ess, dim3((unsigned)nc), dim3(SUM_WG), h->stream, C, R, st->max_lag, chunk, (const double*)st->yb,
+                         (const double*)st->col, k0, (int)MODE_PLAIN, 1, 1, st->ess, st->mcse);
+    if (rc == MAGI_OK && st->want_q)
+        rc = magi_launch(h, "k_sum_order: ", k_sum_order, dim3((unsigned)nc), dim3(SUM_WG), h->stream, C * R, chunk, (const double*)st->col, k0,
+                         (int)MODE_PLAIN, 1, 1, st->K, st->n_q, st->probs, st->quant);
+    return rc;
+}
+
+int magi_colstats_end(magi_handle* h, MagiColStats* st, double* mean, double* sd, double* quant, double* rhat, double* ess, double* mcse, int* nonfinite) {
+    if (!st) return MAGI_OK;
+    const size_t kb = (size_t)st->K * sizeof(double);
+    int count = 0;
+    hipError_t e = hipSuccess;
+    if (mean) e = hipMemcpyAsync(mean, st->mean, kb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && sd) e = hipMemcpyAsync(sd, st->sd, kb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && rhat) e = hipMemcpyAsync(rhat, st->rhat, kb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && ess && st->want_ess) e = hipMemcpyAsync(ess, st->ess, kb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && mcse && st->want_ess) e = hipMemcpyAsync(mcse, st->mcse, kb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && quant && st->want_q) e = hipMemcpyAsync(quant, st->quant, (size_t)st->n_q * kb, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess && nonfinite) e = hipMemcpyAsync(&count, st->count, sizeof(int), hipMemcpyDeviceToHost, h->stream);
+    const hipError_t es = hipStreamSynchronize(h->stream);          // (also on an error path: nothing may be in flight when the buffer goes)
+    const std::string who = st->who;
+    (void)hipFree(st->buf);
+    delete st;
+    if (e == hipSuccess) e = es;
+    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, who + ": " + hipGetErrorString(e));
+    if (nonfinite) *nonfinite += count;
+    return MAGI_OK;
+}
+
 int magi_summarize(magi_handle* h, int C, int R, int K, const double* draws, int n_q, const double* probs, int max_lag, double* mean, double* sd,
                    double* quant, double* rhat, double* ess, double* mcse_mean, int* n_nonfinite) {
     if (!h) return MAGI_E_BADARG;

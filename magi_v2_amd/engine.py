@@ -96,6 +96,11 @@ _SYMBOLS = {
                                           C.c_int, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip]),
     "magi_summarize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int] + [_dp] * 6 + [_ip]),
     "magi_sampler_summarize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int] + [_dp] * 18 + [_ip]),
+    "magi_matern_cross": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_double, _dp, _dp]),
+    "magi_gp_predict": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp, C.c_double, _dp, C.c_int, _dp, C.c_int, _dp] + [_dp] * 4),
+    "magi_sampler_gp_predict": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp, C.c_int, _dp, C.c_int]
+                                + [_dp] * 16 + [_ip]),
+    "magi_gp_profile": (C.c_int, [C.c_void_p, _dp]),
     "magi_elpd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp] + [_dp] * 6 + [_ip]),
     "magi_sampler_elpd": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [_dp] * 6 + [_ip, _ip, _dp, _ip]),
 }
@@ -352,6 +357,73 @@ class MagiEngine:
         out = {b: dict(zip(SUMMARY_STATS, arrs)) for b, arrs in blocks.items()}
         out.update(probs=probs, n_nonfinite=int(nf.value))
         return out
+
+    def matern_cross(self, t_new, I, phi1, phi2, nu=2.01):
+        """Matern cross blocks of the times ``t_new`` [T] against the grid times ``I`` [N] (magi_matern_cross): (Ks, pKs), each [T, N],
+        Ks[m, j] = k(t_new[m], I[j]) and pKs its derivative in the first argument; with ``t_new = I`` the Kappa and p_Kappa of
+        ``matern_blocks`` bit for bit."""
+        t_new, I = _f64(np.asarray(t_new, dtype=np.float64).reshape(-1)), _f64(np.asarray(I, dtype=np.float64).reshape(-1))
+        T, N = t_new.shape[0], I.shape[0]
+        Ks, pKs = np.empty((T, N)), np.empty((T, N))
+        self._check(self._lib.magi_matern_cross(self._h, _ptr(t_new), T, _ptr(I), N, float(phi1), float(phi2), float(nu), _ptr(Ks), _ptr(pKs)))
+        return Ks, pKs
+
+    def gp_predict(self, I, phi1s, phi2s, mu, t_new, X, nu=2.01, derivative=True):
+        """The draws ``X`` [S, N, D] of the trajectory on the grid ``I`` conditioned to the times ``t_new`` [T] against the resident dense
+        C_inv (magi_gp_predict; the definitions are in include/magi_hip.h): dict(x_new [S, T, D], the conditional means; cond_var [T, D],
+        their conditional variance; with ``derivative`` dx_new and dcond_var, the same for x'(t))."""
+        I = _f64(np.asarray(I, dtype=np.float64).reshape(-1))
+        t_new = _f64(np.asarray(t_new, dtype=np.float64).reshape(-1))
+        N, T = I.shape[0], t_new.shape[0]
+        phi1s = _f64(np.asarray(phi1s, dtype=np.float64).reshape(-1))
+        D = phi1s.shape[0]
+        phi2s, mu = _f64(np.asarray(phi2s, dtype=np.float64).reshape(-1), (D,)), _f64(np.asarray(mu, dtype=np.float64).reshape(-1), (D,))
+        X = _f64(X)
+        S = X.shape[0]
+        X = _f64(X, (S, N, D))
+        out = {"x_new": np.empty((S, T, D)), "cond_var": np.empty((T, D)),
+               "dx_new": np.empty((S, T, D)) if derivative else None, "dcond_var": np.empty((T, D)) if derivative else None}
+        self._check(self._lib.magi_gp_predict(self._h, _ptr(I), N, D, _ptr(phi1s), _ptr(phi2s), float(nu), _ptr(mu), T, _ptr(t_new), S, _ptr(X),
+                                              _ptr(out["x_new"]), _ptr(out["dx_new"]), _ptr(out["cond_var"]), _ptr(out["dcond_var"])))
+        return out
+
+    def sampler_gp_predict(self, I, phi1s, phi2s, t_new, chains=None, member=None, nu=2.01, probs=DEFAULT_PROBS, max_lag=0, derivative=True,
+                           return_draws=False):
+        """The finished sampler run's trajectory draws conditioned to the times ``t_new`` [T], computed on the device-resident samples
+        (magi_sampler_gp_predict): no draw is copied to the host.  ``I``, ``phi1s``, ``phi2s``, ``nu``: the grid and hyper-parameters the
+        resident C_inv was built with.  Returns dict(t, X, dX, cond_var, dcond_var, probs, n_nonfinite): X a dict as ``summarize`` returns
+        over the conditional means x_new, of shape [T, D]; cond_var [T, D] their conditional variance; dX / dcond_var the same for x'(t)
+        (None without ``derivative``).  ``return_draws`` adds X_draws (and dX_draws) [chains, draws, T, D].  ``chains`` / ``member`` as in
+        ``sampler_summary``; a member's matrices and mu are its own."""
+        chain0, n_sel = self._chain_range(chains, member)
+        I = _f64(np.asarray(I, dtype=np.float64).reshape(-1), (self.N,))
+        t_new = _f64(np.asarray(t_new, dtype=np.float64).reshape(-1))
+        T, D = t_new.shape[0], self.D
+        phi1s, phi2s = _f64(np.asarray(phi1s, dtype=np.float64).reshape(-1), (D,)), _f64(np.asarray(phi2s, dtype=np.float64).reshape(-1), (D,))
+        probs, n_q = self._probs(probs)
+        R = self._cfg.num_results if self._cfg is not None else 0
+        xs = _summary_arrays((T, D), n_q)
+        dxs = _summary_arrays((T, D), n_q) if derivative else [None] * 6
+        cv, dcv = np.empty((T, D)), (np.empty((T, D)) if derivative else None)
+        xd = np.empty((n_sel, R, T, D)) if return_draws else None
+        dxd = np.empty((n_sel, R, T, D)) if return_draws and derivative else None
+        nf = C.c_int32(0)
+        self._check(self._lib.magi_sampler_gp_predict(self._h, chain0, n_sel, _ptr(I), _ptr(phi1s), _ptr(phi2s), float(nu), T, _ptr(t_new), n_q,
+                                                      _ptr(probs), int(max_lag), _ptr(xd), _ptr(dxd), _ptr(cv), _ptr(dcv),
+                                                      *[_ptr(a) for a in xs + dxs], C.byref(nf)))
+        out = {"t": t_new, "X": dict(zip(SUMMARY_STATS, xs)), "dX": dict(zip(SUMMARY_STATS, dxs)) if derivative else None,
+               "cond_var": cv, "dcond_var": dcv, "probs": probs, "n_nonfinite": int(nf.value)}
+        if return_draws:
+            out["X_draws"] = xd
+            if derivative:
+                out["dX_draws"] = dxd
+        return out
+
+    def gp_profile(self):
+        """Device time (ms) of the stages of the last gp_predict / sampler_gp_predict under ``set_option("gp_profile", 1)`` (magi_gp_profile)."""
+        ms = np.zeros(5)
+        self._check(self._lib.magi_gp_profile(self._h, _ptr(ms)))
+        return dict(zip(("cross_blocks", "weights", "application_gemm", "application_epilogue", "statistics"), ms.tolist()))
 
     def _elpd_outputs(self, n, loo):
         return {s: (np.empty(n) if (loo or s in ("lpd", "p_waic", "elpd_waic")) else None) for s in ELPD_POINTWISE}
