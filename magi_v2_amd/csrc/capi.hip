@@ -263,6 +263,17 @@ int magi_ensure_chains(magi_handle* h, int n) {
     return MAGI_OK;
 }
 
+// the one place that knows which drift ids this library serves.  hint: the message says where a traced drift's library comes from
+int magi_check_drift_id(magi_handle* h, int drift_id, bool hint) {
+#ifdef MAGI_USER_DRIFT_HEADER
+    if (drift_id != MAGI_DRIFT_USER) return magi_fail(h, MAGI_E_BADARG, "this library is specialised for a traced f_vec: drift id must be MAGI_DRIFT_USER");
+#else
+    if (drift_id < MAGI_DRIFT_SEIR3 || drift_id > MAGI_DRIFT_SIRW)
+        return magi_fail(h, MAGI_E_BADARG, std::string("unknown drift id") + (hint ? " (a traced f_vec needs its own library: magi_v2_amd.jit)" : ""));
+#endif
+    return MAGI_OK;
+}
+
 extern "C" {
 
 const char* magi_version(void) { return "magi_hip 0.1.0 gfx950"; }
@@ -478,11 +489,7 @@ int magi_theta_init(magi_handle* h, int drift_id, int P, const double* Xhat, con
     if (!Xhat || !mu || !theta) return magi_fail(h, MAGI_E_BADARG, "null pointer");
     if (!h->dDense[0] || h->dense_N <= 0) return magi_fail(h, MAGI_E_STATE, "no resident matrices: build or set them first");
     if (num_iters < 0 || !(learning_rate > 0.0)) return magi_fail(h, MAGI_E_BADARG, "num_iters >= 0 and learning_rate > 0");
-#ifdef MAGI_USER_DRIFT_HEADER
-    if (drift_id != MAGI_DRIFT_USER) return magi_fail(h, MAGI_E_BADARG, "this library is specialised for a traced f_vec: drift id must be MAGI_DRIFT_USER");
-#else
-    if (drift_id < MAGI_DRIFT_SEIR3 || drift_id > MAGI_DRIFT_SIRW) return magi_fail(h, MAGI_E_BADARG, "unknown drift id (a traced f_vec needs its own library: magi_v2_amd.jit)");
-#endif
+    if (int rc = magi_check_drift_id(h, drift_id)) return rc;
     for (int i = 0; i < h->dense_N * h->dense_D; ++i)
         if (std::isnan(Xhat[i])) return magi_fail(h, MAGI_E_NAN, "NaN in Xhat");
     (void)hipSetDevice(h->device);
@@ -517,19 +524,14 @@ int magi_set_problem(magi_handle* h, const double* mu, const double* N_ds, const
     if (!mu || !N_ds || !LB || (n_obs > 0 && (!obs_idx || !y))) return magi_fail(h, MAGI_E_BADARG, "null pointer");
     DevProblem& pb = h->pb;
     int needD, needP;
-#ifdef MAGI_USER_DRIFT_HEADER
-    if (drift_id != MAGI_DRIFT_USER)
-        return magi_fail(h, MAGI_E_BADARG, "this library is specialised for a traced f_vec: drift id must be MAGI_DRIFT_USER");
-    needD = MAGI_USER_D; needP = MAGI_USER_P;
-#else
-    switch (drift_id) {
-    case MAGI_DRIFT_SEIR3: needD = 3; needP = 3; break;
-    case MAGI_DRIFT_SEIR4: needD = 4; needP = 3; break;
-    case MAGI_DRIFT_SIRW: needD = 4; needP = 5; break;
-    case MAGI_DRIFT_USER: return magi_fail(h, MAGI_E_BADARG, "no user drift compiled into this library (magi_v2_amd.jit builds one)");
-    default: return magi_fail(h, MAGI_E_BADARG, "unknown drift id");
-    }
+#ifndef MAGI_USER_DRIFT_HEADER
+    if (drift_id == MAGI_DRIFT_USER) return magi_fail(h, MAGI_E_BADARG, "no user drift compiled into this library (magi_v2_amd.jit builds one)");
 #endif
+    if (int rc = magi_check_drift_id(h, drift_id, false)) return rc;
+    // (the dispatch below sends every id it does not know to its last arm: it is right only behind the check above)
+#define MAGI_CALL(DR) needD = DriftT<DR>::D, needP = DriftT<DR>::P
+    MAGI_DRIFT_DISPATCH(drift_id, MAGI_CALL);
+#undef MAGI_CALL
     if (pb.D != needD || P != needP)
         return magi_fail(h, MAGI_E_BADARG, "drift expects D=" + std::to_string(needD) + ", P=" + std::to_string(needP));
     if (magi_user_drift_time_dependent() && h->times_N != pb.N)

@@ -3,9 +3,10 @@
 // the limits of C and R.  Every sum runs in one fixed order (lane-strided partials, a butterfly, the four waves added as
 // (w0 + w1) + (w2 + w3)) and the only atomics are integer ones: results are bit-identical from run to run.
 #pragma once
-#include "magi_internal.h"
+#include "scratch.h"
 
 #include <algorithm>
+#include <cmath>
 #include <string>
 
 namespace colstat {
@@ -15,7 +16,13 @@ constexpr int G_TILE = 64;            // the gathers: 64 x 64 doubles per workgr
 constexpr int SUM_LDS = 2048;         // doubles of LDS a statistics kernel sorts / stages (16 KiB: four workgroups per CU and more)
 constexpr size_t CHUNK_DOUBLES = (size_t)1 << 23;
 
+constexpr int MAX_Q = 16;
+
 struct SumLB { double v[MAGI_MAX_D]; };
+struct SumProbs { double p[MAX_Q]; };
+
+// how a block's columns are read and reported: as they are, or a sample row's X, sigma or theta block on its natural scale
+enum { MODE_PLAIN = 0, MODE_X = 1, MODE_SIGMA = 2, MODE_THETA = 3 };
 
 // the reductions over the workgroup, each in one fixed order; every thread receives the result
 __device__ __forceinline__ double wg_sum(double v, double* red /* LDS [4] */) {
@@ -90,6 +97,19 @@ inline int check_draws(magi_handle* h, const char* who, long long C, long long R
     return MAGI_OK;
 }
 
+// the quantile probabilities every summarising entry point takes; fills pr
+inline int check_probs(magi_handle* h, const char* who, int n_q, const double* probs, SumProbs& pr) {
+    if (n_q < 0 || n_q > MAX_Q) return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": 0 <= n_q <= 16 probabilities");
+    if (n_q > 0 && !probs) return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": probs is NULL");
+    for (int q = 0; q < MAX_Q; ++q) pr.p[q] = 0.0;
+    for (int q = 0; q < n_q; ++q) {
+        if (!std::isfinite(probs[q]) || probs[q] < 0.0 || probs[q] > 1.0)
+            return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": probs[" + std::to_string(q) + "] is not a finite number in [0, 1]");
+        pr.p[q] = probs[q];
+    }
+    return MAGI_OK;
+}
+
 // columns per chunk of a block of K columns of S draws (at most 2^23 doubles; the test switch summary_chunk_cols forces small chunks)
 inline size_t chunk_cols(const magi_handle* h, size_t S, size_t K) {
     size_t cc = std::max<size_t>(1, CHUNK_DOUBLES / S);
@@ -99,3 +119,21 @@ inline size_t chunk_cols(const magi_handle* h, size_t S, size_t K) {
 }
 
 }  // namespace colstat
+
+// summary.hip: the statistics of magi_summarize for K columns of C x R draws on the device in chunk layout (chunk[column][C R], what
+// k_sum_gather produces and what gp.hip's GEMM writes).  take: declares the result arrays in the caller's scratch (before its alloc());
+// chunk: k_sum_moments / k_sum_ess / k_sum_order on columns [k0, k0 + nc), reported at out_index(mode, column, N, D); down: queues the
+// downloads the caller wants (null: not) and that of the count of columns with a non-finite draw, to be read after s.finish().
+struct MagiColStats {
+    int C, R, n_q, max_lag, max_cols;
+    long long K;
+    bool want_ess, want_q;
+    colstat::SumProbs probs;
+    double *yb, *col, *mean, *sd, *rhat, *ess, *mcse, *quant;
+    int* count;
+    int n_bad;                        // the downloaded count
+};
+void magi_colstats_take(MagiScratch& s, MagiColStats& st, int C, int R, long long K, int max_cols, int n_q, const colstat::SumProbs& probs, int max_lag,
+                        bool want_ess, bool want_quant);
+int magi_colstats_chunk(magi_handle* h, const char* who, const MagiColStats& st, const double* dchunk, int nc, long long k0, int mode, int N, int D);
+void magi_colstats_down(MagiScratch& s, MagiColStats& st, double* mean, double* sd, double* quant, double* rhat, double* ess, double* mcse);

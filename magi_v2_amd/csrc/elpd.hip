@@ -299,56 +299,49 @@ int elpd_block(magi_handle* h, const char* who, const double* dsrc, const double
     const size_t cc = chunk_cols(h, S, (size_t)K);
     SumLB lb{};
     for (int d = 0; d < pb.D && d < MAGI_MAX_D; ++d) lb.v[d] = pb.LB[d];
-    // one device buffer: chunk (cc S) | staging of the host route (cc S) | lpd, p_waic, elpd_waic, elpd_loo, p_loo, khat (K each) |
-    // flag (K ints) | the counter (1 int) | the observed entries (K ints)
-    const size_t n_stage = hsrc ? cc * S : 0, n_idx = oidx.size();
-    const size_t doubles = cc * S + n_stage + 6 * (size_t)K;
-    double* buf = nullptr;
-    MAGI_HIP_CHECK(h, hipMalloc((void**)&buf, doubles * sizeof(double) + ((size_t)K + 1 + n_idx) * sizeof(int)));
-    double *chunk = buf, *stage = chunk + cc * S, *dlpd = stage + n_stage, *dpw = dlpd + K, *dew = dpw + K, *del = dew + K, *dpl = del + K, *dkh = dpl + K;
-    int *dflag = reinterpret_cast<int*>(dkh + K), *dcount = dflag + K, *didx = dcount + 1;
+    const size_t k = (size_t)K, n_idx = oidx.size();
+    MagiScratch sc(h, who);
+    double *chunk, *stage /* the host route's strided upload */, *dlpd, *dpw, *dew, *del, *dpl, *dkh;
+    int *dflag, *dcount, *didx /* the observed entries */;
+    sc.take(chunk, cc * S); sc.take(stage, hsrc ? cc * S : 0);
+    sc.take(dlpd, k); sc.take(dpw, k); sc.take(dew, k); sc.take(del, k); sc.take(dpl, k); sc.take(dkh, k);
+    sc.take(dflag, k); sc.take(dcount, 1, true); sc.take(didx, n_idx);
+    if (int rc = sc.alloc()) return rc;
     std::vector<double> back(loglik_out ? cc * S : 0);
-    int rc = MAGI_OK, count = 0;
-    hipError_t e = hipMemsetAsync(dcount, 0, sizeof(int), h->stream);
-    if (e == hipSuccess && n_idx) e = hipMemcpyAsync(didx, oidx.data(), n_idx * sizeof(int), hipMemcpyHostToDevice, h->stream);
-    for (size_t c0 = 0; c0 < (size_t)K && rc == MAGI_OK && e == hipSuccess; c0 += cc) {
+    int count = 0;
+    if (n_idx) sc.up(didx, oidx.data(), n_idx * sizeof(int));
+    for (size_t c0 = 0; c0 < (size_t)K && sc.ok(); c0 += cc) {
         const int nc = (int)std::min(cc, (size_t)K - c0);
-        if (hsrc) {
-            e = hipMemcpy2DAsync(stage, (size_t)nc * sizeof(double), hsrc + c0, (size_t)K * sizeof(double), (size_t)nc * sizeof(double), S,
-                                 hipMemcpyHostToDevice, h->stream);
-            if (e != hipSuccess) break;
-        }
-        rc = magi_launch(h, "k_ll_gather: ", k_ll_gather, dim3((unsigned)((S + G_TILE - 1) / G_TILE), (unsigned)((nc + G_TILE - 1) / G_TILE)),
-                         dim3(G_TILE, 4), h->stream, (int)S, nc, hsrc ? (const double*)stage : dsrc, hsrc ? (long long)nc : ld,
-                         hsrc ? (const int*)nullptr : (const int*)(didx + c0), pb, lb, chunk);
-        if (rc == MAGI_OK)
-            rc = magi_launch(h, "k_ll_waic: ", k_ll_waic, dim3((unsigned)nc), dim3(SUM_WG), h->stream, (int)S, (const double*)chunk, (long long)c0,
-                             dlpd, dpw, dew, dflag, dcount);
-        if (rc == MAGI_OK && want_loo)
-            rc = magi_launch(h, "k_ll_psis: ", k_ll_psis, dim3((unsigned)nc), dim3(SUM_WG), h->stream, (int)S, M, m, (const double*)chunk,
-                             (long long)c0, (const int*)dflag, (const double*)dlpd, del, dpl, dkh);
-        if (rc == MAGI_OK && loglik_out) {                     // chunk [nc][S] -> loglik_out [S][K]
-            e = hipMemcpyAsync(back.data(), chunk, (size_t)nc * S * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-            if (e != hipSuccess) break;
+        if (hsrc)
+            sc.note(hipMemcpy2DAsync(stage, (size_t)nc * sizeof(double), hsrc + c0, (size_t)K * sizeof(double), (size_t)nc * sizeof(double), S,
+                                     hipMemcpyHostToDevice, h->stream));
+        if (sc.ok())
+            sc.note(magi_launch(h, "k_ll_gather: ", k_ll_gather, dim3((unsigned)((S + G_TILE - 1) / G_TILE), (unsigned)((nc + G_TILE - 1) / G_TILE)),
+                                dim3(G_TILE, 4), h->stream, (int)S, nc, hsrc ? (const double*)stage : dsrc, hsrc ? (long long)nc : ld,
+                                hsrc ? (const int*)nullptr : (const int*)(didx + c0), pb, lb, chunk));
+        if (sc.ok())
+            sc.note(magi_launch(h, "k_ll_waic: ", k_ll_waic, dim3((unsigned)nc), dim3(SUM_WG), h->stream, (int)S, (const double*)chunk, (long long)c0,
+                                dlpd, dpw, dew, dflag, dcount));
+        if (sc.ok() && want_loo)
+            sc.note(magi_launch(h, "k_ll_psis: ", k_ll_psis, dim3((unsigned)nc), dim3(SUM_WG), h->stream, (int)S, M, m, (const double*)chunk,
+                                (long long)c0, (const int*)dflag, (const double*)dlpd, del, dpl, dkh));
+        if (sc.ok() && loglik_out) {                           // chunk [nc][S] -> loglik_out [S][K]
+            sc.down(back.data(), chunk, (size_t)nc * S * sizeof(double));
+            if (sc.ok()) sc.note(hipStreamSynchronize(h->stream));
+            if (!sc.ok()) break;
             for (int c = 0; c < nc; ++c)
                 for (size_t s = 0; s < S; ++s) loglik_out[s * (size_t)K + c0 + c] = back[(size_t)c * S + s];
         }
     }
-    const bool ok = rc == MAGI_OK;
-    const size_t kb = (size_t)K * sizeof(double);
-    if (ok && e == hipSuccess && o.lpd) e = hipMemcpyAsync(o.lpd, dlpd, kb, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && o.p_waic) e = hipMemcpyAsync(o.p_waic, dpw, kb, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && o.elpd_waic) e = hipMemcpyAsync(o.elpd_waic, dew, kb, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && o.elpd_loo) e = hipMemcpyAsync(o.elpd_loo, del, kb, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && o.p_loo) e = hipMemcpyAsync(o.p_loo, dpl, kb, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && o.khat) e = hipMemcpyAsync(o.khat, dkh, kb, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess) e = hipMemcpyAsync(&count, dcount, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-    const hipError_t es = hipStreamSynchronize(h->stream);          // (also on an error path: nothing may be in flight when the buffer goes)
-    (void)hipFree(buf);
-    if (rc != MAGI_OK) return rc;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
+    const size_t kb = k * sizeof(double);
+    sc.down_opt(o.lpd, dlpd, kb);
+    sc.down_opt(o.p_waic, dpw, kb);
+    sc.down_opt(o.elpd_waic, dew, kb);
+    sc.down_opt(o.elpd_loo, del, kb);
+    sc.down_opt(o.p_loo, dpl, kb);
+    sc.down_opt(o.khat, dkh, kb);
+    sc.down(&count, dcount, sizeof(int));
+    if (int rc = sc.finish()) return rc;
     if (nonfinite) *nonfinite = count;
     return MAGI_OK;
 }
@@ -372,28 +365,9 @@ int magi_sampler_elpd(magi_handle* h, int chain0, int n_sel, double* lpd, double
                       double* khat, int* obs_index, int* n_obs_out, double* loglik_out, int* n_nonfinite) {
     if (!h) return MAGI_E_BADARG;
     static const char* who = "magi_sampler_elpd";
-    if (!h->sampler_ready) return magi_fail(h, MAGI_E_STATE, "sampler not initialised");
-    if (chain0 < 0 || n_sel < 1 || (long long)chain0 + n_sel > h->n_chains)
-        return magi_fail(h, MAGI_E_BADARG, "magi_sampler_elpd: chains [chain0, chain0 + n_sel) must lie inside the sampler's " + std::to_string(h->n_chains));
-    int member = -1;
-    if (h->group_n) {
-        const int per = h->group_per > 0 ? h->group_per : h->n_chains;
-        member = chain0 / per;
-        if ((chain0 + n_sel - 1) / per != member)
-            return magi_fail(h, MAGI_E_BADARG, "magi_sampler_elpd: the chain range spans more than one member of the group (their posteriors differ)");
-    }
-    (void)hipSetDevice(h->device);
-    std::vector<ChainCtl> ctl((size_t)n_sel);
-    MAGI_HIP_CHECK(h, hipMemcpy(ctl.data(), h->ch.ctl + chain0, sizeof(ChainCtl) * n_sel, hipMemcpyDeviceToHost));
-    for (int c = 0; c < n_sel; ++c)
-        if (ctl[c].k < h->cfg.total)
-            return magi_fail(h, MAGI_E_STATE, "magi_sampler_elpd: chain " + std::to_string(chain0 + c) + " has taken " + std::to_string((long long)ctl[c].k) +
-                                                  " of " + std::to_string((long long)h->cfg.total) + " transitions");
-    const int R = h->num_results;
-    int rc = check_draws(h, who, n_sel, R);
-    if (rc) return rc;
-    DevProblem pb = h->pb;                                     // the handle's problem, or the member's own as the sampler read it (magi_sampler_init)
-    if (member >= 0) MAGI_HIP_CHECK(h, hipMemcpy(&pb, h->d_members + member, sizeof(DevProblem), hipMemcpyDeviceToHost));
+    MagiChainRange cr;
+    if (int rc = magi_finished_chains(h, who, chain0, n_sel, &cr)) return rc;
+    const DevProblem& pb = cr.pb;
     std::vector<double> y((size_t)pb.ND);
     MAGI_HIP_CHECK(h, hipMemcpy(y.data(), pb.yobs, y.size() * sizeof(double), hipMemcpyDeviceToHost));
     std::vector<int> oidx;
@@ -404,6 +378,5 @@ int magi_sampler_elpd(magi_handle* h, int chain0, int n_sel, double* lpd, double
     if (obs_index) std::copy(oidx.begin(), oidx.end(), obs_index);
     if (n_nonfinite) *n_nonfinite = 0;
     if (K == 0 || !(lpd || p_waic || elpd_waic || elpd_loo || p_loo || khat || loglik_out || n_nonfinite)) return MAGI_OK;
-    const double* base = h->ch.samples + (size_t)chain0 * R * pb.dimp;
-    return elpd_block(h, who, base, nullptr, pb.dimp, n_sel, R, K, oidx, pb, ElpdOut{lpd, p_waic, elpd_waic, elpd_loo, p_loo, khat}, loglik_out, n_nonfinite);
+    return elpd_block(h, who, cr.base, nullptr, pb.dimp, n_sel, cr.R, K, oidx, pb, ElpdOut{lpd, p_waic, elpd_waic, elpd_loo, p_loo, khat}, loglik_out, n_nonfinite);
 }

@@ -10,7 +10,7 @@
 // caller's host layout [S][N][D] uploaded as it is: only the strides differ); mu enters through the two row constants, formed by
 // k_gp_rows from the row sums of the same W / Wd the GEMM reads and added by k_gp_shift -- no pass over the samples subtracts it.  The
 // GEMM writes chunk[column = (m, d)][S], the layout the statistics kernels of summary.hip consume (magi_colstats_*), so the summaries
-// need no gather; the draws themselves, when the caller wants them, go through k_gp_transpose to the host layout [S][T][D].
+// need no gather; the draws themselves, when the caller wants them, go through k_transpose of summary.hip (magi_transpose) to the host layout [S][T][D].
 // The rows of t_new go in chunks so that no buffer exceeds 2^23 doubles (64 MiB, the rule of summary.hip) unless a single row needs
 // more; W and Wd of a chunk are formed once and serve every draw.  Nothing depends on the chunking: an output's k loop runs in the same
 // order wherever its row falls in a tile, and every row sum runs in one fixed order (lane-strided partials, colstat::wg_sum), so
@@ -23,7 +23,6 @@
 namespace {
 
 using namespace colstat;
-constexpr int TR = 64;                // k_gp_transpose: 64 x 64 doubles per workgroup of 64 x 4 threads
 
 struct GpComp { double phi1[MAGI_MAX_D], diag_pp[MAGI_MAX_D], mu[MAGI_MAX_D]; };
 
@@ -56,28 +55,10 @@ __global__ __launch_bounds__(SUM_WG) void k_gp_shift(int S, double* __restrict__
     if (s < S) chunk[(size_t)blockIdx.x * S + s] += shift[blockIdx.x];
 }
 
-// chunk[nc][S] -> out[S][nc] through an LDS tile; grid (ceil(S / 64), ceil(nc / 64)), block (64, 4)
-__global__ __launch_bounds__(TR * 4) void k_gp_transpose(int S, int nc, const double* __restrict__ chunk, double* __restrict__ out) {
-    __shared__ double tile[TR][TR + 1];                       // (+1: the column reads below fall on 32 different bank pairs)
-    const int s0 = blockIdx.x * TR, c0 = blockIdx.y * TR, tx = threadIdx.x, ty = threadIdx.y;
-    for (int c = ty; c < TR; c += 4)
-        if (c0 + c < nc && s0 + tx < S) tile[c][tx] = chunk[(size_t)(c0 + c) * S + s0 + tx];
-    __syncthreads();
-    for (int r = ty; r < TR; r += 4)
-        if (s0 + r < S && c0 + tx < nc) out[(size_t)(s0 + r) * nc + c0 + tx] = tile[tx][r];
-}
-
-struct GpBuf {                        // releases its buffer after the stream has drained (also on every error path)
-    magi_handle* h;
-    double* p = nullptr;
-    ~GpBuf() {
-        (void)hipStreamSynchronize(h->stream);
-        if (p) (void)hipFree(p);
-    }
-};
-
 struct GpDraws {                      // the B operand of the application GEMM: B(n = s, k) of component d at base[d bd + s sn + k sk]
-    const double* base;
+    const double* base;               // on the device, or null: gp_core uploads `host` (n_host doubles) into its scratch and reads that
+    const double* host;
+    size_t n_host;
     long sn, sk, bd;
     int C, R;                         // S = C R draws
 };
@@ -132,9 +113,9 @@ struct GpStage {
     }
 };
 
-// the whole computation: dCinv the dense C^-1 stack [D][N][N] on the device, I and t_new on the host, the draws on the device
+// the whole computation: dCinv the dense C^-1 stack [D][N][N] on the device, I and t_new on the host, the draws on either
 int gp_core(magi_handle* h, const char* who, const double* dCinv, const double* I, int N, int D, const double* phi1, const double* phi2, double nu,
-            const double* mu, int T, const double* t_new, const GpDraws& dr, int n_q, const double* probs, int max_lag, const GpOut& o) {
+            const double* mu, int T, const double* t_new, GpDraws dr, int n_q, const SumProbs& probs, int max_lag, const GpOut& o) {
     const size_t S = (size_t)dr.C * dr.R;
     const bool want_x_stats = any(o.x) || o.n_nonfinite, want_dx_stats = any(o.dx);
     const bool deriv = o.dx_new || o.dcond_var || want_dx_stats;
@@ -148,89 +129,80 @@ int gp_core(magi_handle* h, const char* who, const double* dCinv, const double* 
     for (double& t : h->gp_ms) t = 0.0;
     const GpStage prof{h, h->opt.gp_profile != 0};
 
-    // one device buffer: I (N) | t_new (T) | Ks, pKs (2 planes) | W, Wd (2 planes) | shift (2 tc D) | var (2 T D) | x, dx chunks (2 cplanes) |
-    // staging of the draws on their way to the host (1 cplane)
-    GpBuf buf{h};
-    const size_t doubles = (size_t)N + T + 4 * plane + 2 * (size_t)tc * D + 2 * (size_t)T * D + (apply ? 2 * cplane : 0) + (stage ? cplane : 0);
-    MAGI_HIP_CHECK(h, hipMalloc((void**)&buf.p, doubles * sizeof(double)));
-    double *dI = buf.p, *dT = dI + N, *ks = dT + T, *w = ks + 2 * plane, *shift = w + 2 * plane, *var = shift + 2 * (size_t)tc * D,
-           *xc = var + 2 * (size_t)T * D, *st = xc + (apply ? 2 * cplane : 0);
-    MAGI_HIP_CHECK(h, hipMemcpyAsync(dI, I, sizeof(double) * N, hipMemcpyHostToDevice, h->stream));
-    MAGI_HIP_CHECK(h, hipMemcpyAsync(dT, t_new, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
+    // scratch: I | t_new | Ks, pKs | W, Wd | shift [2][tc][D] | var [2][T][D] | the x and dx chunks | the staging of the draws on their way to the
+    // host | the draws a host caller brought | the statistics' arrays
+    MagiScratch s(h, who);
+    MagiColStats sx, sdx;
+    double *dI, *dT, *ks, *w, *shift, *var, *xc, *st, *dX;
+    s.take(dI, (size_t)N); s.take(dT, (size_t)T); s.take(ks, 2 * plane); s.take(w, 2 * plane); s.take(shift, 2 * (size_t)tc * D); s.take(var, 2 * (size_t)T * D);
+    s.take(xc, apply ? 2 * cplane : 0); s.take(st, stage ? cplane : 0); s.take(dX, dr.base ? 0 : dr.n_host);
+    if (want_x_stats) magi_colstats_take(s, sx, dr.C, dr.R, (long long)T * D, tc * D, n_q, probs, max_lag, o.x[4] || o.x[5], o.x[2] != nullptr);
+    if (want_dx_stats) magi_colstats_take(s, sdx, dr.C, dr.R, (long long)T * D, tc * D, n_q, probs, max_lag, o.dx[4] || o.dx[5], o.dx[2] != nullptr);
+    if (int rc = s.alloc()) return rc;
+    if (!dr.base) {
+        s.up(dX, dr.host, dr.n_host * sizeof(double));
+        dr.base = dX;
+    }
+    s.up(dI, I, sizeof(double) * N);
+    s.up(dT, t_new, sizeof(double) * T);
 
-    MagiColStats *sx = nullptr, *sdx = nullptr;
-    int rc = MAGI_OK, count = 0;
-    if (want_x_stats) rc = magi_colstats_begin(h, who, dr.C, dr.R, (long long)T * D, tc * D, n_q, probs, max_lag, o.x[4] || o.x[5], o.x[2] != nullptr, &sx);
-    if (rc == MAGI_OK && want_dx_stats)
-        rc = magi_colstats_begin(h, who, dr.C, dr.R, (long long)T * D, tc * D, n_q, probs, max_lag, o.dx[4] || o.dx[5], o.dx[2] != nullptr, &sdx);
-    hipError_t e = hipSuccess;
-    for (int m0 = 0; m0 < T && rc == MAGI_OK && e == hipSuccess; m0 += tc) {
+    for (int m0 = 0; m0 < T && s.ok(); m0 += tc) {
         const int nt = std::min(tc, T - m0), nc = nt * D;
         // (the planes of a short last chunk are packed at ITS pitch nt: every stride below is in nt)
         const size_t pl = (size_t)D * nt * N, cpl = (size_t)nc * S;
         prof.begin();
-        for (int d = 0; d < D && rc == MAGI_OK; ++d)
-            rc = magi_matern_cross_launch(h, h->stream, dT + m0, nt, dI, N, phi1[d], phi2[d], nu, ks + (size_t)d * nt * N,
-                                          deriv ? ks + pl + (size_t)d * nt * N : nullptr);
+        for (int d = 0; d < D && s.ok(); ++d)
+            s.note(magi_matern_cross_launch(h, h->stream, dT + m0, nt, dI, N, phi1[d], phi2[d], nu, ks + (size_t)d * nt * N,
+                                            deriv ? ks + pl + (size_t)d * nt * N : nullptr));
         prof.end(0);
-        if (rc) break;
+        if (!s.ok()) break;
         prof.begin();
         MagiGemm g{};           // W_d = Ks_d C^-1_d: rows of Ks times columns of C^-1 as stored, B(n, k) = C^-1[k][n]
         g.A = ks; g.sAm = N; g.sAk = 1; g.batchA = (long)nt * N; g.batchA2 = (long)pl;
         g.B = dCinv; g.sBn = 1; g.sBk = N; g.batchB = (long)N * N; g.batchB2 = 0;
         g.C = w; g.ldc = N; g.batchC = (long)nt * N; g.batchC2 = (long)pl;
         g.M = nt; g.N = N; g.K = N; g.inner = D; g.outer = nz;
-        rc = magi_gemm_strided(h, h->stream, g);
-        if (rc == MAGI_OK)
-            rc = magi_launch(h, "k_gp_rows: ", k_gp_rows, dim3((unsigned)nt, (unsigned)D, (unsigned)nz), dim3(SUM_WG), h->stream, nt, N, D, T, m0, (const double*)w,
-                             (const double*)ks, cp, var, shift);
+        s.note(magi_gemm_strided(h, h->stream, g));
+        if (s.ok())
+            s.note(magi_launch(h, "k_gp_rows: ", k_gp_rows, dim3((unsigned)nt, (unsigned)D, (unsigned)nz), dim3(SUM_WG), h->stream, nt, N, D, T, m0, (const double*)w,
+                               (const double*)ks, cp, var, shift));
         prof.end(1);
-        if (rc || !apply) continue;
+        if (!s.ok() || !apply) continue;
         prof.begin();
         MagiGemm a{};           // chunk[(m, d)][s] = sum_k W_d[m][k] B_d(s, k): the draws read in place
         a.A = w; a.sAm = N; a.sAk = 1; a.batchA = (long)nt * N; a.batchA2 = (long)pl;
         a.B = dr.base; a.sBn = dr.sn; a.sBk = dr.sk; a.batchB = dr.bd; a.batchB2 = 0;
         a.C = xc; a.ldc = (long)D * (long)S; a.batchC = (long)S; a.batchC2 = (long)cpl;
         a.M = nt; a.N = (int)S; a.K = N; a.inner = D; a.outer = nz;
-        rc = magi_gemm_strided(h, h->stream, a);
+        s.note(magi_gemm_strided(h, h->stream, a));
         prof.end(2);
         prof.begin();
         // (shift is [2][nt][D] at this chunk's pitch, the chunk planes [2][nc][S]: one launch adds both)
-        if (rc == MAGI_OK)
-            rc = magi_launch(h, "k_gp_shift: ", k_gp_shift, dim3((unsigned)(nz * nc), (unsigned)((S + SUM_WG - 1) / SUM_WG)), dim3(SUM_WG), h->stream, (int)S, xc,
-                             (const double*)shift);
+        if (s.ok())
+            s.note(magi_launch(h, "k_gp_shift: ", k_gp_shift, dim3((unsigned)(nz * nc), (unsigned)((S + SUM_WG - 1) / SUM_WG)), dim3(SUM_WG), h->stream, (int)S, xc,
+                               (const double*)shift));
         prof.end(3);
-        if (rc) break;
+        if (!s.ok()) break;
         prof.begin();
-        if (sx) rc = magi_colstats_chunk(h, sx, xc, nc, (long long)m0 * D);
-        if (rc == MAGI_OK && sdx) rc = magi_colstats_chunk(h, sdx, xc + cpl, nc, (long long)m0 * D);
+        if (want_x_stats) s.note(magi_colstats_chunk(h, who, sx, xc, nc, (long long)m0 * D, MODE_PLAIN, 1, 1));
+        if (s.ok() && want_dx_stats) s.note(magi_colstats_chunk(h, who, sdx, xc + cpl, nc, (long long)m0 * D, MODE_PLAIN, 1, 1));
         prof.end(4);
         double* const dst[2] = {o.x_new, o.dx_new};
-        for (int z = 0; z < 2 && rc == MAGI_OK && e == hipSuccess; ++z) {
+        for (int z = 0; z < 2 && s.ok(); ++z) {
             if (!dst[z]) continue;
-            rc = magi_launch(h, "k_gp_transpose: ", k_gp_transpose, dim3((unsigned)((S + TR - 1) / TR), (unsigned)((nc + TR - 1) / TR)), dim3(TR, 4), h->stream,
-                             (int)S, nc, (const double*)(xc + z * cpl), st);
-            if (rc == MAGI_OK)
-                e = hipMemcpy2DAsync(dst[z] + (size_t)m0 * D, (size_t)T * D * sizeof(double), st, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double), S,
-                                     hipMemcpyDeviceToHost, h->stream);
+            s.note(magi_transpose(h, nc, (int)S, xc + z * cpl, S, st, (size_t)nc));          // chunk[nc][S] -> st[S][nc]
+            if (s.ok())
+                s.note(hipMemcpy2DAsync(dst[z] + (size_t)m0 * D, (size_t)T * D * sizeof(double), st, (size_t)nc * sizeof(double), (size_t)nc * sizeof(double), S,
+                                        hipMemcpyDeviceToHost, h->stream));
         }
     }
     const size_t vb = (size_t)T * D * sizeof(double);
-    if (rc == MAGI_OK && e == hipSuccess && o.cond_var) e = hipMemcpyAsync(o.cond_var, var, vb, hipMemcpyDeviceToHost, h->stream);
-    if (rc == MAGI_OK && e == hipSuccess && o.dcond_var) e = hipMemcpyAsync(o.dcond_var, var + (size_t)T * D, vb, hipMemcpyDeviceToHost, h->stream);
-    const bool ok = rc == MAGI_OK && e == hipSuccess;
-    // (the ends also release the statistics' buffers on an error path: then nothing is downloaded)
-    const int r1 = magi_colstats_end(h, sx, ok ? o.x[0] : nullptr, ok ? o.x[1] : nullptr, ok ? o.x[2] : nullptr, ok ? o.x[3] : nullptr, ok ? o.x[4] : nullptr,
-                                     ok ? o.x[5] : nullptr, ok ? &count : nullptr);
-    const int r2 = magi_colstats_end(h, sdx, ok ? o.dx[0] : nullptr, ok ? o.dx[1] : nullptr, ok ? o.dx[2] : nullptr, ok ? o.dx[3] : nullptr,
-                                     ok ? o.dx[4] : nullptr, ok ? o.dx[5] : nullptr, ok ? &count : nullptr);
-    const hipError_t es = hipStreamSynchronize(h->stream);
-    if (rc != MAGI_OK) return rc;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    if (r1 != MAGI_OK) return r1;
-    if (r2 != MAGI_OK) return r2;
-    if (o.n_nonfinite) *o.n_nonfinite = count;
+    s.down_opt(o.cond_var, var, vb);
+    s.down_opt(o.dcond_var, var + (size_t)T * D, vb);
+    if (want_x_stats) magi_colstats_down(s, sx, o.x[0], o.x[1], o.x[2], o.x[3], o.x[4], o.x[5]);
+    if (want_dx_stats) magi_colstats_down(s, sdx, o.dx[0], o.dx[1], o.dx[2], o.dx[3], o.dx[4], o.dx[5]);
+    if (int rc = s.finish()) return rc;
+    if (o.n_nonfinite) *o.n_nonfinite = (want_x_stats ? sx.n_bad : 0) + (want_dx_stats ? sdx.n_bad : 0);
     return MAGI_OK;
 }
 
@@ -263,16 +235,16 @@ int magi_matern_cross(magi_handle* h, const double* t_new, int T, const double* 
     if ((rc = check_times(h, who, "I", I, N))) return rc;
     (void)hipSetDevice(h->device);
     const size_t tn = (size_t)T * N;
-    GpBuf buf{h};
-    MAGI_HIP_CHECK(h, hipMalloc((void**)&buf.p, ((size_t)T + N + 2 * tn) * sizeof(double)));
-    double *dT = buf.p, *dI = dT + T, *dK = dI + N, *dP = dK + tn;
-    MAGI_HIP_CHECK(h, hipMemcpyAsync(dT, t_new, sizeof(double) * T, hipMemcpyHostToDevice, h->stream));
-    MAGI_HIP_CHECK(h, hipMemcpyAsync(dI, I, sizeof(double) * N, hipMemcpyHostToDevice, h->stream));
-    if ((rc = magi_matern_cross_launch(h, h->stream, dT, T, dI, N, phi1, phi2, nu, Ks ? dK : nullptr, pKs ? dP : nullptr))) return rc;
-    if (Ks) MAGI_HIP_CHECK(h, hipMemcpyAsync(Ks, dK, tn * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (pKs) MAGI_HIP_CHECK(h, hipMemcpyAsync(pKs, dP, tn * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));
-    return MAGI_OK;
+    MagiScratch s(h, who);
+    double *dT, *dI, *dK, *dP;
+    s.take(dT, (size_t)T); s.take(dI, (size_t)N); s.take(dK, tn); s.take(dP, tn);
+    if ((rc = s.alloc())) return rc;
+    s.up(dT, t_new, sizeof(double) * T);
+    s.up(dI, I, sizeof(double) * N);
+    if (s.ok()) s.note(magi_matern_cross_launch(h, h->stream, dT, T, dI, N, phi1, phi2, nu, Ks ? dK : nullptr, pKs ? dP : nullptr));
+    s.down_opt(Ks, dK, tn * sizeof(double));
+    s.down_opt(pKs, dP, tn * sizeof(double));
+    return s.finish();
 }
 
 int magi_gp_predict(magi_handle* h, const double* I, int N, int D, const double* phi1, const double* phi2, double nu, const double* mu, int T,
@@ -287,14 +259,10 @@ int magi_gp_predict(magi_handle* h, const double* I, int N, int D, const double*
         return magi_fail(h, MAGI_E_STATE, "magi_gp_predict: no resident matrices of this N, D: build or set them first");
     (void)hipSetDevice(h->device);
     // the draws go up in the caller's layout [S][N][D]: B(n = s, k) of component d at X[s N D + k D + d]
-    GpBuf dX{h};
-    const size_t nx = (size_t)S * N * D;
-    MAGI_HIP_CHECK(h, hipMalloc((void**)&dX.p, nx * sizeof(double)));
-    MAGI_HIP_CHECK(h, hipMemcpyAsync(dX.p, X, nx * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    const GpDraws dr{dX.p, (long)N * D, (long)D, 1, 1, S};
+    const GpDraws dr{nullptr, X, (size_t)S * N * D, (long)N * D, (long)D, 1, 1, S};
     GpOut o{};
     o.x_new = x_new; o.dx_new = dx_new; o.cond_var = cond_var; o.dcond_var = dcond_var;
-    return gp_core(h, who, h->dDense[0], I, N, D, phi1, phi2, nu, mu, T, t_new, dr, 0, nullptr, 0, o);
+    return gp_core(h, who, h->dDense[0], I, N, D, phi1, phi2, nu, mu, T, t_new, dr, 0, SumProbs{}, 0, o);
 }
 
 int magi_sampler_gp_predict(magi_handle* h, int chain0, int n_sel, const double* I, const double* phi1, const double* phi2, double nu, int T,
@@ -303,52 +271,27 @@ int magi_sampler_gp_predict(magi_handle* h, int chain0, int n_sel, const double*
                             double* dx_mean, double* dx_sd, double* dx_quant, double* dx_rhat, double* dx_ess, double* dx_mcse_mean, int* n_nonfinite) {
     if (!h) return MAGI_E_BADARG;
     static const char* who = "magi_sampler_gp_predict";
-    if (!h->sampler_ready) return magi_fail(h, MAGI_E_STATE, "sampler not initialised");
-    if (chain0 < 0 || n_sel < 1 || (long long)chain0 + n_sel > h->n_chains)
-        return magi_fail(h, MAGI_E_BADARG, "magi_sampler_gp_predict: chains [chain0, chain0 + n_sel) must lie inside the sampler's " + std::to_string(h->n_chains));
-    const magi_handle* owner = h;                                  // whose matrices: the handle's, or the member's own on a group
-    int member = -1;
-    if (h->group_n) {
-        const int per = h->group_per > 0 ? h->group_per : h->n_chains;
-        member = chain0 / per;
-        if ((chain0 + n_sel - 1) / per != member)
-            return magi_fail(h, MAGI_E_BADARG, "magi_sampler_gp_predict: the chain range spans more than one member of the group (their posteriors differ)");
-        owner = h->members[(size_t)member];
-    }
-    const DevProblem& pb = h->pb;
-    const int R = h->num_results;
-    double mu[MAGI_MAX_D] = {};
-    for (int d = 0; d < pb.D; ++d) mu[d] = pb.mu[d];
-    int rc = check_draws(h, who, n_sel, R);
+    MagiChainRange cr;
+    int rc = magi_finished_chains(h, who, chain0, n_sel, &cr);
     if (rc) return rc;
-    if (n_q < 0 || n_q > 16) return magi_fail(h, MAGI_E_BADARG, "magi_sampler_gp_predict: 0 <= n_q <= 16 probabilities");
-    if (n_q > 0 && !probs) return magi_fail(h, MAGI_E_BADARG, "magi_sampler_gp_predict: probs is NULL");
-    for (int q = 0; q < n_q; ++q)
-        if (!std::isfinite(probs[q]) || probs[q] < 0.0 || probs[q] > 1.0)
-            return magi_fail(h, MAGI_E_BADARG, "magi_sampler_gp_predict: probs[" + std::to_string(q) + "] is not a finite number in [0, 1]");
-    (void)hipSetDevice(h->device);
-    if (member >= 0) {                                             // the member's problem as the sampler read it (magi_sampler_init)
-        DevProblem mp;
-        MAGI_HIP_CHECK(h, hipMemcpy(&mp, h->d_members + member, sizeof(DevProblem), hipMemcpyDeviceToHost));
-        for (int d = 0; d < pb.D; ++d) mu[d] = mp.mu[d];
-    }
+    SumProbs pr;
+    if ((rc = check_probs(h, who, n_q, probs, pr))) return rc;
+    const magi_handle* owner = cr.member >= 0 ? h->members[(size_t)cr.member] : h;      // whose matrices: the handle's, or the member's own on a group
+    const DevProblem& pb = h->pb;                                  // the shapes; mu is cr.pb's: the member's own as the sampler read it
+    const int R = cr.R;
+    double mu[MAGI_MAX_D] = {};
+    for (int d = 0; d < pb.D; ++d) mu[d] = cr.pb.mu[d];
     if ((rc = check_predict(h, who, I, pb.N, pb.D, phi1, phi2, nu, mu, T, t_new, (long long)n_sel * R, x_new || dx_new))) return rc;
     if (!owner->dDense[0] || owner->dense_N != pb.N || owner->dense_D != pb.D)
         return magi_fail(h, MAGI_E_STATE, "magi_sampler_gp_predict: no resident dense matrices of the problem's N, D");
-    std::vector<ChainCtl> ctl((size_t)n_sel);
-    MAGI_HIP_CHECK(h, hipMemcpy(ctl.data(), h->ch.ctl + chain0, sizeof(ChainCtl) * n_sel, hipMemcpyDeviceToHost));
-    for (int c = 0; c < n_sel; ++c)
-        if (ctl[c].k < h->cfg.total)
-            return magi_fail(h, MAGI_E_STATE, "magi_sampler_gp_predict: chain " + std::to_string(chain0 + c) + " has taken " + std::to_string((long long)ctl[c].k) +
-                                                  " of " + std::to_string((long long)h->cfg.total) + " transitions");
     // a sample row is [D][N] | sig_pre | th_pre | pad, dimp apart: B(n = s, k) of component d at samples[s dimp + d N + k]
-    const GpDraws dr{h->ch.samples + (size_t)chain0 * R * pb.dimp, (long)pb.dimp, 1, (long)pb.N, n_sel, R};
+    const GpDraws dr{cr.base, nullptr, 0, (long)pb.dimp, 1, (long)pb.N, n_sel, R};
     GpOut o{};
     o.x_new = x_new; o.dx_new = dx_new; o.cond_var = cond_var; o.dcond_var = dcond_var; o.n_nonfinite = n_nonfinite;
     double* const xs[6] = {x_mean, x_sd, x_quant, x_rhat, x_ess, x_mcse_mean};
     double* const dxs[6] = {dx_mean, dx_sd, dx_quant, dx_rhat, dx_ess, dx_mcse_mean};
     for (int i = 0; i < 6; ++i) { o.x[i] = xs[i]; o.dx[i] = dxs[i]; }
-    return gp_core(h, who, owner->dDense[0], I, pb.N, pb.D, phi1, phi2, nu, mu, T, t_new, dr, n_q, probs, max_lag, o);
+    return gp_core(h, who, owner->dDense[0], I, pb.N, pb.D, phi1, phi2, nu, mu, T, t_new, dr, n_q, pr, max_lag, o);
 }
 
 int magi_gp_profile(magi_handle* h, double* ms) {

@@ -1193,11 +1193,17 @@ int magi_launch(magi_handle* h, const char* what, void (*k)(P...), dim3 grid, di
     return MAGI_OK;
 }
 
-// ode.hip, for ode_adaptive.hip: both integrate into trj[T D][S_pad] with S_pad = roundup(S, MAGI_ODE_PAD) and status[S_pad]; R = T D.
-// magi_ode_stats: mean, sd [R] and n_failed over the draws with status 0 (k_ode_stats); magi_ode_transpose: out[S][R] (k_ode_transpose).
+// capi.hip: MAGI_OK where this library serves drift_id (a compiled-in drift, or MAGI_DRIFT_USER in a library built for a traced f_vec),
+// else the error; hint: with the pointer to magi_v2_amd.jit in the message
+int magi_check_drift_id(magi_handle* h, int drift_id, bool hint = true);
+
+// summary.hip, for ode.hip and ode_adaptive.hip: both integrate into trj[T D][S_pad] with S_pad = roundup(S, MAGI_ODE_PAD) and status[S_pad];
+// R = T D.  magi_ode_stats: mean, sd [R] and n_failed over the draws with status 0 (k_ode_stats); magi_ode_transpose: out[S][R].
+// magi_transpose: in[rows][ld_in] -> out[cols][ld_out] (k_transpose; what magi_ode_transpose launches, and gp.hip for its draws).
 constexpr int MAGI_ODE_PAD = 64;
 int magi_ode_stats(magi_handle* h, int S, int S_pad, int R, const double* trj, const int* status, double* mean, double* sd, int* n_failed);
 int magi_ode_transpose(magi_handle* h, int S, int S_pad, int R, const double* trj, double* out);
+int magi_transpose(magi_handle* h, int rows, int cols, const double* in, size_t ld_in, double* out, size_t ld_out);
 
 // launchers implemented in logpost.hip / sampler.hip ---------------------------------------------
 int magi_launch_gradient(magi_handle* h, int n_chains, hipStream_t s);        // phases 1-3
@@ -1259,14 +1265,15 @@ struct MagiGemm {
     int M, N, K, inner, outer;
 };
 int magi_gemm_strided(magi_handle* h, hipStream_t s, const MagiGemm& g);
-// summary.hip: the statistics of magi_summarize for K columns of C x R draws that are ALREADY on the device in chunk layout
-// (chunk[column][C R], what the gathers of summarize_block produce for a plain block): begin allocates the result arrays, every
-// chunk call runs k_sum_moments / k_sum_ess / k_sum_order on columns [k0, k0 + nc) as summarize_block does, end downloads what the
-// caller wants (null: not), waits for the stream and releases everything -- it is also the clean-up of an error path.
-struct MagiColStats;
-int magi_colstats_begin(magi_handle* h, const char* who, int C, int R, long long K, int max_cols, int n_q, const double* probs, int max_lag,
-                        bool want_ess, bool want_quant, MagiColStats** out);
-int magi_colstats_chunk(magi_handle* h, MagiColStats* st, const double* dchunk, int nc, long long k0);
-int magi_colstats_end(magi_handle* h, MagiColStats* st, double* mean, double* sd, double* quant, double* rhat, double* ess, double* mcse, int* nonfinite);
+// summary.hip: chains [chain0, chain0 + n_sel) of a sampler that has finished, for the post-processing entry points (who: the caller's
+// name in the messages).  Refuses a sampler that is not initialised, a range outside its chains or across two members of a group, a
+// chain with transitions left, and C = n_sel, R = num_results beyond the statistics' limits.
+struct MagiChainRange {
+    int member;                       // the group member that owns the chains, -1 without a group
+    DevProblem pb;                    // the handle's problem, or the member's own as the sampler read it (magi_sampler_init)
+    int R;                            // draws per chain
+    const double* base;               // the first selected chain's rows in ch.samples (R rows of pb.dimp doubles per chain)
+};
+int magi_finished_chains(magi_handle* h, const char* who, int chain0, int n_sel, MagiChainRange* out);
 int magi_matern_blocks_device(magi_handle* h, const double* I, int N, double phi1, double phi2, double nu,
                               double* Kappa, double* p_Kappa, double* Kappa_pp);

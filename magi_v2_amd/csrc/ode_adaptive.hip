@@ -4,9 +4,9 @@
 //                     ode23s for stiff draws: its J comes from DriftT<>::jt with unit vectors, its T from DriftT<>::ft (drift_ft_at), and
 //                     W = I - h d J is factored in registers.  The controller is stated in include/magi_hip.h and restated op for op in
 //                     tests/ode_adaptive_reference.py.  Lanes take different numbers of steps; the wave runs until its last lane is done.
-//   mean / sd / n_failed and the host layout: k_ode_stats and k_ode_transpose of csrc/ode.hip (magi_ode_stats, magi_ode_transpose).
+//   mean / sd / n_failed and the host layout: k_ode_stats and k_transpose of csrc/summary.hip (magi_ode_stats, magi_ode_transpose).
 // Depends on the drift: not in jit._DRIFT_FREE.
-#include "magi_internal.h"
+#include "ode_common.h"
 
 #include <cmath>
 
@@ -262,57 +262,20 @@ __global__ __launch_bounds__(ODE_WG) void k_ode_adaptive(int S, int S_pad, int T
     n_rej[s] = nr;
 }
 
-// magi_ode_solve_adaptive for one drift: the buffer of solve() plus reason, n_accepted, n_rejected (S_pad ints each) behind status
+// magi_ode_solve_adaptive for one drift: the host path of magi_ode_solve (ode_common.h) with reason, n_accepted, n_rejected behind status
 template <int DRIFT>
 int solve_adaptive(magi_handle* h, int P, int S, const double* x0, const double* theta, int T, const double* t_out, int method, double rtol,
                    double atol, double h0, int max_steps, double* traj, double* mean, double* sd, int* status, int* reason, int* n_accepted,
                    int* n_rejected, int* n_failed) {
-    using DR = DriftT<DRIFT>;
-    constexpr int D = DR::D;
-    if (P != DR::P) return magi_fail(h, MAGI_E_BADARG, "magi_ode_solve_adaptive: drift expects P=" + std::to_string(DR::P));
-    const size_t S_pad = ((size_t)S + ODE_WG - 1) / ODE_WG * ODE_WG, R = (size_t)T * D, cells = S_pad * R;
-    if (cells > ((size_t)1 << 28))
-        return magi_fail(h, MAGI_E_BADARG, "magi_ode_solve_adaptive: roundup(S, 64) * T * D exceeds 2^28 (a 2 GiB device buffer)");
-    const bool stats = mean || sd || n_failed;
-    const size_t n_out = traj ? (size_t)S * R : 0, nx = (size_t)S * D, nth = (size_t)S * P;
-    const size_t doubles = cells + n_out + nx + nth + (size_t)T + 2 * R;
-    double* buf = nullptr;
-    MAGI_HIP_CHECK(h, hipMalloc((void**)&buf, doubles * sizeof(double) + (4 * S_pad + 1) * sizeof(int)));
-    double *dtrj = buf, *dout = dtrj + cells, *dx = dout + n_out, *dth = dx + nx, *dt = dth + nth, *dmean = dt + T, *dsd = dmean + R;
-    int *dstatus = reinterpret_cast<int*>(dsd + R), *dreason = dstatus + S_pad, *dacc = dreason + S_pad, *drej = dacc + S_pad, *dnf = drej + S_pad;
-    int rc = MAGI_OK;
-    hipError_t e = hipMemcpyAsync(dx, x0, nx * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dth, theta, nth * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dt, t_out, (size_t)T * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) {
-        const dim3 grid((unsigned)(S_pad / ODE_WG)), wg(ODE_WG);
-        if (method == MAGI_ODE_DOPRI5)
-            rc = magi_launch(h, "k_ode_adaptive (dopri5): ", k_ode_adaptive<DRIFT, MAGI_ODE_DOPRI5>, grid, wg, h->stream, S, (int)S_pad, T, rtol, atol,
-                             h0, max_steps, (const double*)dx, (const double*)dth, (const double*)dt, dtrj, dstatus, dreason, dacc, drej);
-        else
-            rc = magi_launch(h, "k_ode_adaptive (ros23): ", k_ode_adaptive<DRIFT, MAGI_ODE_ROS23>, grid, wg, h->stream, S, (int)S_pad, T, rtol, atol,
-                             h0, max_steps, (const double*)dx, (const double*)dth, (const double*)dt, dtrj, dstatus, dreason, dacc, drej);
-    }
-    if (rc == MAGI_OK && e == hipSuccess && stats)
-        rc = magi_ode_stats(h, S, (int)S_pad, (int)R, dtrj, dstatus, dmean, dsd, dnf);
-    if (rc == MAGI_OK && e == hipSuccess && traj)
-        rc = magi_ode_transpose(h, S, (int)S_pad, (int)R, dtrj, dout);
-    const bool ok = rc == MAGI_OK;
-    const size_t ni = (size_t)S * sizeof(int);
-    if (ok && e == hipSuccess && traj) e = hipMemcpyAsync(traj, dout, n_out * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && mean) e = hipMemcpyAsync(mean, dmean, R * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && sd) e = hipMemcpyAsync(sd, dsd, R * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && status) e = hipMemcpyAsync(status, dstatus, ni, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && reason) e = hipMemcpyAsync(reason, dreason, ni, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && n_accepted) e = hipMemcpyAsync(n_accepted, dacc, ni, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && n_rejected) e = hipMemcpyAsync(n_rejected, drej, ni, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && n_failed) e = hipMemcpyAsync(n_failed, dnf, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-    const hipError_t es = hipStreamSynchronize(h->stream);          // (also on an error path: nothing may be in flight when the buffer goes)
-    (void)hipFree(buf);
-    if (rc != MAGI_OK) return rc;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("magi_ode_solve_adaptive: ") + hipGetErrorString(e));
-    return MAGI_OK;
+    return ode_solve_host<DriftT<DRIFT>>(
+        h, "magi_ode_solve_adaptive", P, S, x0, theta, T, t_out, traj, mean, sd, status, n_failed, true, reason, n_accepted, n_rejected, [&](const OdeDev& d) {
+            const dim3 grid((unsigned)(d.S_pad / ODE_WG)), wg(ODE_WG);
+            if (method == MAGI_ODE_DOPRI5)
+                return magi_launch(h, "k_ode_adaptive (dopri5): ", k_ode_adaptive<DRIFT, MAGI_ODE_DOPRI5>, grid, wg, h->stream, S, d.S_pad, T, rtol, atol, h0,
+                                   max_steps, d.x0, d.theta, d.t, d.trj, d.status, d.reason, d.n_accepted, d.n_rejected);
+            return magi_launch(h, "k_ode_adaptive (ros23): ", k_ode_adaptive<DRIFT, MAGI_ODE_ROS23>, grid, wg, h->stream, S, d.S_pad, T, rtol, atol, h0, max_steps,
+                               d.x0, d.theta, d.t, d.trj, d.status, d.reason, d.n_accepted, d.n_rejected);
+        });
 }
 
 }  // namespace
@@ -321,29 +284,19 @@ int magi_ode_solve_adaptive(magi_handle* h, int drift_id, int P, int S, const do
                             double rtol, double atol, double h0, int max_steps, double* traj, double* mean, double* sd, int* status, int* reason,
                             int* n_accepted, int* n_rejected, int* n_failed) {
     if (!h) return MAGI_E_BADARG;
-    const std::string me = "magi_ode_solve_adaptive: ";
-    if (!x0 || !theta || !t_out) return magi_fail(h, MAGI_E_BADARG, me + "null pointer (x0, theta and t_out are required)");
-    if (S < 1 || S > (1 << 20)) return magi_fail(h, MAGI_E_BADARG, me + "1 <= S <= 2^20 draws");
-    if (T < 2 || T > (1 << 16)) return magi_fail(h, MAGI_E_BADARG, me + "2 <= T <= 2^16 output times");
-    if (method != MAGI_ODE_DOPRI5 && method != MAGI_ODE_ROS23)
-        return magi_fail(h, MAGI_E_BADARG, me + "unknown method (MAGI_ODE_DOPRI5 or MAGI_ODE_ROS23)");
-    if (!std::isfinite(rtol) || !std::isfinite(atol)) return magi_fail(h, MAGI_E_BADARG, me + "rtol and atol must both be finite");
-    if (rtol < 1e-13 || rtol > 1e-1) return magi_fail(h, MAGI_E_BADARG, me + "1e-13 <= rtol <= 1e-1");
-    if (atol < 0.0) return magi_fail(h, MAGI_E_BADARG, me + "atol >= 0");
-    if (!std::isfinite(h0) || h0 < 0.0) return magi_fail(h, MAGI_E_BADARG, me + "h0 >= 0 and finite (0: the first output interval)");
-    if (max_steps < 1 || max_steps > (1 << 24)) return magi_fail(h, MAGI_E_BADARG, me + "1 <= max_steps <= 2^24");
-    for (int j = 0; j < T; ++j) {
-        if (!std::isfinite(t_out[j])) return magi_fail(h, MAGI_E_BADARG, me + "t_out[" + std::to_string(j) + "] is not finite");
-        if (j > 0 && !(t_out[j] > t_out[j - 1]))
-            return magi_fail(h, MAGI_E_BADARG, me + "t_out is not strictly increasing at index " + std::to_string(j));
-    }
-#ifdef MAGI_USER_DRIFT_HEADER
-    if (drift_id != MAGI_DRIFT_USER) return magi_fail(h, MAGI_E_BADARG, "this library is specialised for a traced f_vec: drift id must be MAGI_DRIFT_USER");
-#else
-    if (drift_id < MAGI_DRIFT_SEIR3 || drift_id > MAGI_DRIFT_SIRW) return magi_fail(h, MAGI_E_BADARG, "unknown drift id (a traced f_vec needs its own library: magi_v2_amd.jit)");
-#endif
+    int rc = check_ode_common(h, "magi_ode_solve_adaptive", drift_id, S, x0, theta, T, t_out, [&] {
+        const std::string me = "magi_ode_solve_adaptive: ";
+        if (method != MAGI_ODE_DOPRI5 && method != MAGI_ODE_ROS23)
+            return magi_fail(h, MAGI_E_BADARG, me + "unknown method (MAGI_ODE_DOPRI5 or MAGI_ODE_ROS23)");
+        if (!std::isfinite(rtol) || !std::isfinite(atol)) return magi_fail(h, MAGI_E_BADARG, me + "rtol and atol must both be finite");
+        if (rtol < 1e-13 || rtol > 1e-1) return magi_fail(h, MAGI_E_BADARG, me + "1e-13 <= rtol <= 1e-1");
+        if (atol < 0.0) return magi_fail(h, MAGI_E_BADARG, me + "atol >= 0");
+        if (!std::isfinite(h0) || h0 < 0.0) return magi_fail(h, MAGI_E_BADARG, me + "h0 >= 0 and finite (0: the first output interval)");
+        if (max_steps < 1 || max_steps > (1 << 24)) return magi_fail(h, MAGI_E_BADARG, me + "1 <= max_steps <= 2^24");
+        return (int)MAGI_OK;
+    });
+    if (rc) return rc;
     (void)hipSetDevice(h->device);
-    int rc = MAGI_OK;
 #define MAGI_CALL(DR) \
     rc = solve_adaptive<DR>(h, P, S, x0, theta, T, t_out, method, rtol, atol, h0, max_steps, traj, mean, sd, status, reason, n_accepted, n_rejected, n_failed)
     MAGI_DRIFT_DISPATCH(drift_id, MAGI_CALL);

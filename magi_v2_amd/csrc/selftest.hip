@@ -7,7 +7,7 @@
 //   path 2: DriftT<>::coefs(theta), ::basis(x): f_d = sum_k coefs[d][k] basis[d][k]   (k_stream_sep and its point phase, the mirror)
 //   path 3: DriftT<>::f1(d, ..) per component (the VALU / matrix-core streaming kernels; a hand-written body of its own in the compiled-in drifts)
 // Depends on the drift: a build for a traced drift compiles this unit again (it is not in jit._DRIFT_FREE).
-#include "magi_internal.h"
+#include "scratch.h"
 
 namespace {
 
@@ -81,36 +81,32 @@ int probe(magi_handle* h, int drift, int P, int path, int n, const double* x, co
     if (path == 2 && !DR::SEP) return magi_fail(h, MAGI_E_BADARG, "path 2: this drift has no separable form");
     const bool deriv = path < 2;
     if (deriv && (!g || !c || !t)) return magi_fail(h, MAGI_E_BADARG, "null pointer");
-    // one device buffer: x | g | f | c (n D each), t (n P), th (P), times (n)
-    const size_t nd = (size_t)n * D, np_ = (size_t)n * P, total = 4 * nd + np_ + P + (size_t)n;
-    double* buf = nullptr;
-    MAGI_HIP_CHECK(h, hipMalloc((void**)&buf, total * sizeof(double)));
-    double *dx = buf, *dg = buf + nd, *df = buf + 2 * nd, *dc = buf + 3 * nd, *dt = buf + 4 * nd, *dth = dt + np_;
-    const double* dtt = tt ? dth + P : nullptr;
-    int rc = MAGI_OK;
-    hipError_t e = hipMemcpyAsync(dx, x, nd * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dth, th, P * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && tt) e = hipMemcpyAsync(dth + P, tt, (size_t)n * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess && deriv) e = hipMemcpyAsync(dg, g, nd * sizeof(double), hipMemcpyHostToDevice, h->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(df, 0, (2 * nd + np_) * sizeof(double), h->stream);
-    if (e == hipSuccess) {
+    const size_t nd = (size_t)n * D, np_ = (size_t)n * P;
+    MagiScratch s(h, "magi_drift_probe");
+    double *dx, *dg, *dout /* f | c (n D each) | t (n P): the outputs, cleared by one memset */, *dth, *dtimes;
+    s.take(dx, nd); s.take(dg, nd); s.take(dout, 2 * nd + np_, true); s.take(dth, (size_t)P); s.take(dtimes, tt ? (size_t)n : 0);
+    if (int rc = s.alloc()) return rc;
+    double *df = dout, *dc = dout + nd, *dt = dout + 2 * nd;
+    const double* dtt = tt ? dtimes : nullptr;
+    s.up(dx, x, nd * sizeof(double));
+    s.up(dth, th, P * sizeof(double));
+    if (tt) s.up(dtimes, tt, (size_t)n * sizeof(double));
+    if (deriv) s.up(dg, g, nd * sizeof(double));
+    if (s.ok()) {
         const dim3 grid((n + 255) / 256), block(256);
         switch (path) {
-        case 0: rc = magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 0>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt, dtt); break;
-        case 1: rc = magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 1>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt, dtt); break;
-        case 2: rc = magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 2>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt, dtt); break;
-        default: rc = magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 3>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt, dtt); break;
+        case 0: s.note(magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 0>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt, dtt)); break;
+        case 1: s.note(magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 1>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt, dtt)); break;
+        case 2: s.note(magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 2>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt, dtt)); break;
+        default: s.note(magi_launch(h, "k_drift_probe: ", k_drift_probe<DRIFT, 3>, grid, block, h->stream, drift, n, dx, dth, dg, df, dc, dt, dtt)); break;
         }
     }
-    if (rc == MAGI_OK && e == hipSuccess) e = hipMemcpyAsync(f, df, nd * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (rc == MAGI_OK && e == hipSuccess && deriv) e = hipMemcpyAsync(c, dc, nd * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (rc == MAGI_OK && e == hipSuccess && deriv) e = hipMemcpyAsync(t, dt, np_ * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    const hipError_t es = hipStreamSynchronize(h->stream);          // (also on an error path: nothing may be in flight when the buffer goes)
-    (void)hipFree(buf);
-    if (rc != MAGI_OK) return rc;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("magi_drift_probe: ") + hipGetErrorString(e));
-    return MAGI_OK;
+    s.down(f, df, nd * sizeof(double));
+    if (deriv) {
+        s.down(c, dc, nd * sizeof(double));
+        s.down(t, dt, np_ * sizeof(double));
+    }
+    return s.finish();
 }
 
 }  // namespace
@@ -126,13 +122,9 @@ int magi_drift_probe_at(magi_handle* h, int drift_id, int P, int path, int n, co
     if (!x || !th || !f) return magi_fail(h, MAGI_E_BADARG, "null pointer");
     if (path < 0 || path > 3) return magi_fail(h, MAGI_E_BADARG, "path: 0 f / jt, 1 runtime-switch entries, 2 separable members, 3 f1");
     if (n < 1 || n > (1 << 20)) return magi_fail(h, MAGI_E_BADARG, "1 <= n <= 2^20 points");
-#ifdef MAGI_USER_DRIFT_HEADER
-    if (drift_id != MAGI_DRIFT_USER) return magi_fail(h, MAGI_E_BADARG, "this library is specialised for a traced f_vec: drift id must be MAGI_DRIFT_USER");
-#else
-    if (drift_id < MAGI_DRIFT_SEIR3 || drift_id > MAGI_DRIFT_SIRW) return magi_fail(h, MAGI_E_BADARG, "unknown drift id (a traced f_vec needs its own library: magi_v2_amd.jit)");
-#endif
+    int rc = magi_check_drift_id(h, drift_id);
+    if (rc) return rc;
     (void)hipSetDevice(h->device);
-    int rc = MAGI_OK;
 #define MAGI_CALL(DR) rc = probe<DR>(h, drift_id, P, path, n, x, th, g, f, c, t, tt)
     MAGI_DRIFT_DISPATCH(drift_id, MAGI_CALL);
 #undef MAGI_CALL

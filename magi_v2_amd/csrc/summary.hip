@@ -2,7 +2,7 @@
 // pooled mean, sd (ddof 1) and quantiles (exact order statistics, linear interpolation), split R-hat, ESS (Geyer's initial monotone
 // sequence over the split chains' autocovariances) and the Monte-Carlo standard error of the mean -- definitions in include/magi_hip.h and DESIGN.md 4.4.
 // A sample row is [D][N] | sig_pre[D] | th_pre[P] | pad: the draws of one column lie dimp doubles apart.  So
-//   k_sum_gather    tiled gather + transpose through an LDS tile (as k_ode_transpose): rows x columns of the source -> chunk[column][C R],
+//   k_sum_gather    tiled gather + transpose through an LDS tile (as k_transpose): rows x columns of the source -> chunk[column][C R],
 //                   the natural-scale transform (softplus_ref + LB for sigma, the parameter's support for theta) applied on the way.  Columns go in chunks of at most 2^23
 //                   doubles (64 MiB; the host route stages its strided upload in a second buffer of that size).
 //   k_sum_moments   one workgroup per column: non-finite / constant detection, mean, sd (two passes), then one WAVE per split chain for
@@ -13,6 +13,13 @@
 //                   of 8 bits, LDS histogram) on the order-preserving 64-bit key, then one pass for the next-larger order statistic.
 // Every sum runs in one fixed order (lane-strided partials, a butterfly, the four waves added as (w0 + w1) + (w2 + w3)); the only atomics
 // are integer ones: the results are bit-identical from run to run.  Does not depend on the drift (jit._DRIFT_FREE).
+// Also the home of what the trajectory calls need that does not depend on the drift either (ode.hip, ode_adaptive.hip and gp.hip launch them
+// through magi_ode_stats, magi_ode_transpose, magi_transpose), so that a traced drift's library reuses this unit's object:
+//   k_ode_stats     mean and sample standard deviation per (j, d) over the draws with status 0: two passes, lane-strided partial sums,
+//                   then a butterfly -- one fixed summation order, bit-identical from run to run.
+//   k_transpose     in[rows][ld_in] -> out[cols][ld_out] through an LDS tile, guarded on both sides: trj[T D][S_pad] -> the host layout
+//                   [S][T D], and gp.hip's chunk[(m, d)][S] -> [S][(m, d)].
+// and of magi_finished_chains, the chain range of a finished sampler that magi_sampler_summarize / _elpd / _gp_predict work on.
 #include "colstat.h"
 
 #include <cmath>
@@ -20,12 +27,7 @@
 
 namespace {
 
-using namespace colstat;              // SUM_WG, G_TILE, SUM_LDS, the workgroup reductions, to_key / radix_select, check_draws (shared with elpd.hip)
-constexpr int MAX_Q = 16;
-
-enum { MODE_PLAIN = 0, MODE_X = 1, MODE_SIGMA = 2, MODE_THETA = 3 };
-
-struct SumProbs { double p[MAX_Q]; };
+using namespace colstat;              // SUM_WG, G_TILE, SUM_LDS, the workgroup reductions, to_key / radix_select, the MODE_*, check_draws / check_probs
 
 __global__ __launch_bounds__(G_TILE * 4) void k_sum_gather(int S, int nc, const double* __restrict__ src /* rows ld apart, nc columns */,
                                                            long long ld, int mode, int lb0, SumLB lb, const double2* __restrict__ tsup /* MODE_THETA: the parameters' supports, or null */,
@@ -279,149 +281,159 @@ __global__ __launch_bounds__(SUM_WG) void k_sum_order(int S, const double* __res
     }
 }
 
+__global__ __launch_bounds__(SUM_WG) void k_ode_stats(int S, int S_pad, const double* __restrict__ trj /* [T D][S_pad] */,
+                                                      const int* __restrict__ status /* [S_pad] */, double* __restrict__ mean /* [T D] */,
+                                                      double* __restrict__ sd /* [T D] */, int* __restrict__ n_failed) {
+    __shared__ double red[SUM_WG / 64];
+    const double* row = trj + (size_t)blockIdx.x * S_pad;
+    double sum = 0.0, cnt = 0.0;
+    for (int s = threadIdx.x; s < S; s += SUM_WG) {
+        const bool ok = status[s] == 0;
+        sum += ok ? row[s] : 0.0;
+        cnt += ok ? 1.0 : 0.0;
+    }
+    sum = wg_sum(sum, red);
+    cnt = wg_sum(cnt, red);                                    // (exact: an integer <= 2^20)
+    const double nan = __builtin_nan("");
+    const double mu = cnt > 0.0 ? sum / cnt : nan;
+    double ss = 0.0;
+    for (int s = threadIdx.x; s < S; s += SUM_WG) {
+        const double dv = row[s] - mu;
+        ss += status[s] == 0 ? dv * dv : 0.0;
+    }
+    ss = wg_sum(ss, red);
+    if (threadIdx.x == 0) {
+        mean[blockIdx.x] = mu;
+        sd[blockIdx.x] = cnt > 1.0 ? sqrt(ss / (cnt - 1.0)) : nan;
+        if (blockIdx.x == 0) *n_failed = S - (int)cnt;
+    }
+}
+
+// grid (ceil(cols / 64), ceil(rows / 64)), block (64, 4)
+__global__ __launch_bounds__(G_TILE * 4) void k_transpose(int rows, int cols, const double* __restrict__ in /* [rows][ld_in] */, size_t ld_in,
+                                                          double* __restrict__ out /* [cols][ld_out] */, size_t ld_out) {
+    __shared__ double tile[G_TILE][G_TILE + 1];               // (+1: the column reads below fall on 32 different bank pairs)
+    const int r0 = blockIdx.y * G_TILE, c0 = blockIdx.x * G_TILE, tx = threadIdx.x, ty = threadIdx.y;
+    for (int r = ty; r < G_TILE; r += 4)
+        if (r0 + r < rows && c0 + tx < cols) tile[r][tx] = in[(size_t)(r0 + r) * ld_in + c0 + tx];
+    __syncthreads();
+    for (int c = ty; c < G_TILE; c += 4)
+        if (c0 + c < cols && r0 + tx < rows) out[(size_t)(c0 + c) * ld_out + r0 + tx] = tile[tx][c];
+}
+
 struct SumOut { double *mean, *sd, *quant, *rhat, *ess, *mcse; };
 
 // one block of K columns of C x R draws: from the device (dsrc: column j of row r at dsrc[r ld + j]) or from the host (hsrc [C R][K]).
-// Adds the block's columns with a non-finite draw to *nonfinite.
+// Adds the block's columns with a non-finite draw to *nonfinite.  Scratch: the chunk, the staging of the host route's strided upload,
+// and the statistics' arrays.
 int summarize_block(magi_handle* h, const char* who, const double* dsrc, const double* hsrc, long long ld, int C, int R, long long K, int mode,
                     int N, int D, const SumLB& lb, const double2* tsup, const double4* prior, int n_q, const SumProbs& probs, int max_lag, const SumOut& o, int* nonfinite) {
-    const size_t S = (size_t)C * R, M = 2 * (size_t)C;
+    const size_t S = (size_t)C * R;
     const size_t cc = chunk_cols(h, S, (size_t)K);
-    const bool diag = R >= 4, want_ess = o.ess || o.mcse, want_q = n_q > 0 && o.quant;
-    // one device buffer: chunk (cc S) | staging of the host route (cc S) | ybar (cc M) | col (cc 4) | mean, sd, rhat, ess, mcse (K each) |
-    // quant (n_q K) | the counter (1 int)
-    const size_t n_stage = hsrc ? cc * S : 0, n_yb = diag ? cc * M : 0, nq = want_q ? (size_t)n_q * K : 0;
-    const size_t doubles = cc * S + n_stage + n_yb + cc * 4 + 5 * (size_t)K + nq;
-    double* buf = nullptr;
-    MAGI_HIP_CHECK(h, hipMalloc((void**)&buf, doubles * sizeof(double) + sizeof(int)));
-    double *chunk = buf, *stage = chunk + cc * S, *yb = stage + n_stage, *col = yb + n_yb, *dmean = col + cc * 4, *dsd = dmean + K, *drhat = dsd + K,
-           *dess = drhat + K, *dmcse = dess + K, *dq = dmcse + K;
-    int* dcount = reinterpret_cast<int*>(dq + nq);
-    int rc = MAGI_OK, count = 0;
-    hipError_t e = hipMemsetAsync(dcount, 0, sizeof(int), h->stream);
-    for (size_t c0 = 0; c0 < (size_t)K && rc == MAGI_OK && e == hipSuccess; c0 += cc) {
+    MagiScratch s(h, who);
+    MagiColStats st;
+    double *chunk, *stage;
+    s.take(chunk, cc * S);
+    s.take(stage, hsrc ? cc * S : 0);
+    magi_colstats_take(s, st, C, R, K, (int)cc, n_q, probs, max_lag, o.ess || o.mcse, o.quant != nullptr);
+    if (int rc = s.alloc()) return rc;
+    for (size_t c0 = 0; c0 < (size_t)K && s.ok(); c0 += cc) {
         const int nc = (int)std::min(cc, (size_t)K - c0);
         const double* src = dsrc ? dsrc + c0 : stage;
         const long long sld = dsrc ? ld : nc;
-        if (hsrc) {
-            e = hipMemcpy2DAsync(stage, (size_t)nc * sizeof(double), hsrc + c0, (size_t)K * sizeof(double), (size_t)nc * sizeof(double), S,
-                                 hipMemcpyHostToDevice, h->stream);
-            if (e != hipSuccess) break;
-        }
-        rc = magi_launch(h, "k_sum_gather: ", k_sum_gather, dim3((unsigned)((S + G_TILE - 1) / G_TILE), (unsigned)((nc + G_TILE - 1) / G_TILE)),
-                         dim3(G_TILE, 4), h->stream, (int)S, nc, src, sld, mode, (int)c0, lb, tsup, prior, chunk);
-        if (rc == MAGI_OK)
-            rc = magi_launch(h, "k_sum_moments: ", k_sum_moments, dim3((unsigned)nc), dim3(SUM_WG), h->stream, C, R, (const double*)chunk, yb, col,
-                             (long long)c0, mode, N, D, dmean, dsd, drhat, dcount);
-        if (rc == MAGI_OK && want_ess)
-            rc = magi_launch(h, "k_sum_ess: ", k_sum_ess, dim3((unsigned)nc), dim3(SUM_WG), h->stream, C, R, max_lag, (const double*)chunk,
-                             (const double*)yb, (const double*)col, (long long)c0, mode, N, D, dess, dmcse);
-        if (rc == MAGI_OK && want_q)
-            rc = magi_launch(h, "k_sum_order: ", k_sum_order, dim3((unsigned)nc), dim3(SUM_WG), h->stream, (int)S, (const double*)chunk,
-                             (const double*)col, (long long)c0, mode, N, D, K, n_q, probs, dq);
+        if (hsrc)
+            s.note(hipMemcpy2DAsync(stage, (size_t)nc * sizeof(double), hsrc + c0, (size_t)K * sizeof(double), (size_t)nc * sizeof(double), S,
+                                    hipMemcpyHostToDevice, h->stream));
+        if (s.ok())
+            s.note(magi_launch(h, "k_sum_gather: ", k_sum_gather, dim3((unsigned)((S + G_TILE - 1) / G_TILE), (unsigned)((nc + G_TILE - 1) / G_TILE)),
+                               dim3(G_TILE, 4), h->stream, (int)S, nc, src, sld, mode, (int)c0, lb, tsup, prior, chunk));
+        if (s.ok()) s.note(magi_colstats_chunk(h, who, st, chunk, nc, (long long)c0, mode, N, D));
     }
-    const bool ok = rc == MAGI_OK;
-    const size_t kb = (size_t)K * sizeof(double);
-    if (ok && e == hipSuccess && o.mean) e = hipMemcpyAsync(o.mean, dmean, kb, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && o.sd) e = hipMemcpyAsync(o.sd, dsd, kb, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && o.rhat) e = hipMemcpyAsync(o.rhat, drhat, kb, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && o.ess) e = hipMemcpyAsync(o.ess, dess, kb, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && o.mcse) e = hipMemcpyAsync(o.mcse, dmcse, kb, hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess && want_q) e = hipMemcpyAsync(o.quant, dq, nq * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-    if (ok && e == hipSuccess) e = hipMemcpyAsync(&count, dcount, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-    const hipError_t es = hipStreamSynchronize(h->stream);          // (also on an error path: nothing may be in flight when the buffer goes)
-    (void)hipFree(buf);
-    if (rc != MAGI_OK) return rc;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    if (nonfinite) *nonfinite += count;
-    return MAGI_OK;
-}
-
-// the checks the two entry points share; fills pr
-int check_probs(magi_handle* h, const char* who, int n_q, const double* probs, SumProbs& pr) {
-    if (n_q < 0 || n_q > MAX_Q) return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": 0 <= n_q <= 16 probabilities");
-    if (n_q > 0 && !probs) return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": probs is NULL");
-    for (int q = 0; q < MAX_Q; ++q) pr.p[q] = 0.0;
-    for (int q = 0; q < n_q; ++q) {
-        if (!std::isfinite(probs[q]) || probs[q] < 0.0 || probs[q] > 1.0)
-            return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": probs[" + std::to_string(q) + "] is not a finite number in [0, 1]");
-        pr.p[q] = probs[q];
-    }
+    magi_colstats_down(s, st, o.mean, o.sd, o.quant, o.rhat, o.ess, o.mcse);
+    if (int rc = s.finish()) return rc;
+    if (nonfinite) *nonfinite += st.n_bad;
     return MAGI_OK;
 }
 
 }  // namespace
 
-// The device-source route for columns already in chunk layout (magi_internal.h; gp.hip): the launches of summarize_block without its gather.
-struct MagiColStats {
-    const char* who;
-    int C, R, n_q, max_lag, max_cols;
-    long long K;
-    bool want_ess, want_q;
-    SumProbs probs;
-    double *buf, *yb, *col, *mean, *sd, *rhat, *ess, *mcse, *quant;
-    int* count;
-};
-
-int magi_colstats_begin(magi_handle* h, const char* who, int C, int R, long long K, int max_cols, int n_q, const double* probs, int max_lag,
-                        bool want_ess, bool want_quant, MagiColStats** out) {
-    *out = nullptr;
-    SumProbs pr;
-    int rc = check_draws(h, who, C, R);
-    if (rc == MAGI_OK) rc = check_probs(h, who, n_q, probs, pr);
-    if (rc) return rc;
-    MagiColStats* st = new MagiColStats{};
-    st->who = who; st->C = C; st->R = R; st->n_q = n_q; st->max_lag = max_lag; st->max_cols = max_cols; st->K = K;
-    st->want_ess = want_ess; st->want_q = want_quant && n_q > 0; st->probs = pr;
-    const size_t cc = (size_t)max_cols, n_yb = R >= 4 ? cc * 2 * (size_t)C : 0, nq = st->want_q ? (size_t)n_q * K : 0;
-    // one device buffer: ybar (cc 2 C) | col (cc 4) | mean, sd, rhat, ess, mcse (K each) | quant (n_q K) | the counter (1 int)
-    hipError_t e = hipMalloc((void**)&st->buf, (n_yb + cc * 4 + 5 * (size_t)K + nq) * sizeof(double) + sizeof(int));
-    if (e != hipSuccess) {
-        delete st;
-        return magi_fail(h, MAGI_E_HIP, std::string(who) + ": " + hipGetErrorString(e));
-    }
-    st->yb = st->buf; st->col = st->yb + n_yb; st->mean = st->col + cc * 4; st->sd = st->mean + K; st->rhat = st->sd + K; st->ess = st->rhat + K;
-    st->mcse = st->ess + K; st->quant = st->mcse + K;
-    st->count = reinterpret_cast<int*>(st->quant + nq);
-    *out = st;
-    MAGI_HIP_CHECK(h, hipMemsetAsync(st->count, 0, sizeof(int), h->stream));
-    return MAGI_OK;
+int magi_ode_stats(magi_handle* h, int S, int S_pad, int R, const double* trj, const int* status, double* mean, double* sd, int* n_failed) {
+    return magi_launch(h, "k_ode_stats: ", k_ode_stats, dim3((unsigned)R), dim3(SUM_WG), h->stream, S, S_pad, trj, status, mean, sd, n_failed);
 }
 
-int magi_colstats_chunk(magi_handle* h, MagiColStats* st, const double* chunk, int nc, long long k0) {
-    if (nc < 1 || nc > st->max_cols || k0 < 0 || k0 + nc > st->K) return magi_fail(h, MAGI_E_BADARG, std::string(st->who) + ": statistics chunk out of range");
-    const int C = st->C, R = st->R;
-    int rc = magi_launch(h, "k_sum_moments: ", k_sum_moments, dim3((unsigned)nc), dim3(SUM_WG), h->stream, C, R, chunk, st->yb, st->col, k0, (int)MODE_PLAIN, 1, 1,
-                         st->mean, st->sd, st->rhat, st->count);
-    if (rc == MAGI_OK && st->want_ess)
-        rc = magi_launch(h, "k_sum_ess: ", k_sum_ess, dim3((unsigned)nc), dim3(SUM_WG), h->stream, C, R, st->max_lag, chunk, (const double*)st->yb,
-                         (const double*)st->col, k0, (int)MODE_PLAIN, 1, 1, st->ess, st->mcse);
-    if (rc == MAGI_OK && st->want_q)
-        rc = magi_launch(h, "k_sum_order: ", k_sum_order, dim3((unsigned)nc), dim3(SUM_WG), h->stream, C * R, chunk, (const double*)st->col, k0,
-                         (int)MODE_PLAIN, 1, 1, st->K, st->n_q, st->probs, st->quant);
+int magi_transpose(magi_handle* h, int rows, int cols, const double* in, size_t ld_in, double* out, size_t ld_out) {
+    return magi_launch(h, "k_transpose: ", k_transpose, dim3((unsigned)((cols + G_TILE - 1) / G_TILE), (unsigned)((rows + G_TILE - 1) / G_TILE)), dim3(G_TILE, 4),
+                       h->stream, rows, cols, in, ld_in, out, ld_out);
+}
+
+int magi_ode_transpose(magi_handle* h, int S, int S_pad, int R, const double* trj, double* out) {
+    return magi_transpose(h, R, S, trj, (size_t)S_pad, out, (size_t)R);
+}
+
+void magi_colstats_take(MagiScratch& s, MagiColStats& st, int C, int R, long long K, int max_cols, int n_q, const SumProbs& probs, int max_lag,
+                        bool want_ess, bool want_quant) {
+    st = MagiColStats{};
+    st.C = C; st.R = R; st.n_q = n_q; st.max_lag = max_lag; st.max_cols = max_cols; st.K = K;
+    st.want_ess = want_ess; st.want_q = want_quant && n_q > 0; st.probs = probs;
+    const size_t cc = (size_t)max_cols, k = (size_t)K;
+    s.take(st.yb, R >= 4 ? cc * 2 * (size_t)C : 0);           // (R < 4: no diagnostics, k_sum_moments leaves before it touches ybar)
+    s.take(st.col, cc * 4);
+    s.take(st.mean, k); s.take(st.sd, k); s.take(st.rhat, k); s.take(st.ess, k); s.take(st.mcse, k);
+    s.take(st.quant, st.want_q ? (size_t)n_q * k : 0);
+    s.take(st.count, 1, true);
+}
+
+int magi_colstats_chunk(magi_handle* h, const char* who, const MagiColStats& st, const double* chunk, int nc, long long k0, int mode, int N, int D) {
+    if (nc < 1 || nc > st.max_cols || k0 < 0 || k0 + nc > st.K) return magi_fail(h, MAGI_E_BADARG, std::string(who) + ": statistics chunk out of range");
+    const int C = st.C, R = st.R;
+    int rc = magi_launch(h, "k_sum_moments: ", k_sum_moments, dim3((unsigned)nc), dim3(SUM_WG), h->stream, C, R, chunk, st.yb, st.col, k0, mode, N, D, st.mean,
+                         st.sd, st.rhat, st.count);
+    if (rc == MAGI_OK && st.want_ess)
+        rc = magi_launch(h, "k_sum_ess: ", k_sum_ess, dim3((unsigned)nc), dim3(SUM_WG), h->stream, C, R, st.max_lag, chunk, (const double*)st.yb,
+                         (const double*)st.col, k0, mode, N, D, st.ess, st.mcse);
+    if (rc == MAGI_OK && st.want_q)
+        rc = magi_launch(h, "k_sum_order: ", k_sum_order, dim3((unsigned)nc), dim3(SUM_WG), h->stream, C * R, chunk, (const double*)st.col, k0, mode, N, D, st.K,
+                         st.n_q, st.probs, st.quant);
     return rc;
 }
 
-int magi_colstats_end(magi_handle* h, MagiColStats* st, double* mean, double* sd, double* quant, double* rhat, double* ess, double* mcse, int* nonfinite) {
-    if (!st) return MAGI_OK;
-    const size_t kb = (size_t)st->K * sizeof(double);
-    int count = 0;
-    hipError_t e = hipSuccess;
-    if (mean) e = hipMemcpyAsync(mean, st->mean, kb, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && sd) e = hipMemcpyAsync(sd, st->sd, kb, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && rhat) e = hipMemcpyAsync(rhat, st->rhat, kb, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && ess && st->want_ess) e = hipMemcpyAsync(ess, st->ess, kb, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && mcse && st->want_ess) e = hipMemcpyAsync(mcse, st->mcse, kb, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && quant && st->want_q) e = hipMemcpyAsync(quant, st->quant, (size_t)st->n_q * kb, hipMemcpyDeviceToHost, h->stream);
-    if (e == hipSuccess && nonfinite) e = hipMemcpyAsync(&count, st->count, sizeof(int), hipMemcpyDeviceToHost, h->stream);
-    const hipError_t es = hipStreamSynchronize(h->stream);          // (also on an error path: nothing may be in flight when the buffer goes)
-    const std::string who = st->who;
-    (void)hipFree(st->buf);
-    delete st;
-    if (e == hipSuccess) e = es;
-    if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, who + ": " + hipGetErrorString(e));
-    if (nonfinite) *nonfinite += count;
+void magi_colstats_down(MagiScratch& s, MagiColStats& st, double* mean, double* sd, double* quant, double* rhat, double* ess, double* mcse) {
+    const size_t kb = (size_t)st.K * sizeof(double);
+    s.down_opt(mean, st.mean, kb);
+    s.down_opt(sd, st.sd, kb);
+    s.down_opt(rhat, st.rhat, kb);
+    if (st.want_ess) {
+        s.down_opt(ess, st.ess, kb);
+        s.down_opt(mcse, st.mcse, kb);
+    }
+    if (st.want_q) s.down_opt(quant, st.quant, (size_t)st.n_q * kb);
+    s.down(&st.n_bad, st.count, sizeof(int));
+}
+
+int magi_finished_chains(magi_handle* h, const char* who, int chain0, int n_sel, MagiChainRange* out) {
+    const std::string me = std::string(who) + ": ";
+    if (!h->sampler_ready) return magi_fail(h, MAGI_E_STATE, "sampler not initialised");
+    if (chain0 < 0 || n_sel < 1 || (long long)chain0 + n_sel > h->n_chains)
+        return magi_fail(h, MAGI_E_BADARG, me + "chains [chain0, chain0 + n_sel) must lie inside the sampler's " + std::to_string(h->n_chains));
+    out->member = -1;
+    if (h->group_n) {
+        const int per = h->group_per > 0 ? h->group_per : h->n_chains;
+        out->member = chain0 / per;
+        if ((chain0 + n_sel - 1) / per != out->member)
+            return magi_fail(h, MAGI_E_BADARG, me + "the chain range spans more than one member of the group (their posteriors differ)");
+    }
+    (void)hipSetDevice(h->device);
+    std::vector<ChainCtl> ctl((size_t)n_sel);
+    MAGI_HIP_CHECK(h, hipMemcpy(ctl.data(), h->ch.ctl + chain0, sizeof(ChainCtl) * n_sel, hipMemcpyDeviceToHost));
+    for (int c = 0; c < n_sel; ++c)
+        if (ctl[c].k < h->cfg.total)
+            return magi_fail(h, MAGI_E_STATE, me + "chain " + std::to_string(chain0 + c) + " has taken " + std::to_string((long long)ctl[c].k) + " of " +
+                                                  std::to_string((long long)h->cfg.total) + " transitions");
+    out->R = h->num_results;
+    if (int rc = check_draws(h, who, n_sel, out->R)) return rc;
+    out->pb = h->pb;
+    if (out->member >= 0) MAGI_HIP_CHECK(h, hipMemcpy(&out->pb, h->d_members + out->member, sizeof(DevProblem), hipMemcpyDeviceToHost));
+    out->base = h->ch.samples + (size_t)chain0 * out->R * out->pb.dimp;
     return MAGI_OK;
 }
 
@@ -450,42 +462,18 @@ int magi_sampler_summarize(magi_handle* h, int chain0, int n_sel, int n_q, const
                            int* n_nonfinite) {
     if (!h) return MAGI_E_BADARG;
     static const char* who = "magi_sampler_summarize";
-    if (!h->sampler_ready) return magi_fail(h, MAGI_E_STATE, "sampler not initialised");
-    if (chain0 < 0 || n_sel < 1 || (long long)chain0 + n_sel > h->n_chains)
-        return magi_fail(h, MAGI_E_BADARG, "magi_sampler_summarize: chains [chain0, chain0 + n_sel) must lie inside the sampler's " + std::to_string(h->n_chains));
-    SumProbs pr;
-    int rc = check_probs(h, who, n_q, probs, pr);
+    MagiChainRange cr;
+    int rc = magi_finished_chains(h, who, chain0, n_sel, &cr);
     if (rc) return rc;
-    int member = -1;
-    if (h->group_n) {
-        const int per = h->group_per > 0 ? h->group_per : h->n_chains;
-        member = chain0 / per;
-        if ((chain0 + n_sel - 1) / per != member)
-            return magi_fail(h, MAGI_E_BADARG, "magi_sampler_summarize: the chain range spans more than one member of the group (their posteriors differ)");
-    }
-    (void)hipSetDevice(h->device);
-    std::vector<ChainCtl> ctl((size_t)n_sel);
-    MAGI_HIP_CHECK(h, hipMemcpy(ctl.data(), h->ch.ctl + chain0, sizeof(ChainCtl) * n_sel, hipMemcpyDeviceToHost));
-    for (int c = 0; c < n_sel; ++c)
-        if (ctl[c].k < h->cfg.total)
-            return magi_fail(h, MAGI_E_STATE, "magi_sampler_summarize: chain " + std::to_string(chain0 + c) + " has taken " + std::to_string((long long)ctl[c].k) +
-                                                  " of " + std::to_string((long long)h->cfg.total) + " transitions");
-    const int R = h->num_results;
-    if ((rc = check_draws(h, who, n_sel, R))) return rc;
-    const DevProblem& pb = h->pb;
+    SumProbs pr;
+    if ((rc = check_probs(h, who, n_q, probs, pr))) return rc;
+    const DevProblem& pb = h->pb;                              // the shapes; the bounds, supports and priors are cr.pb's: the member's own on a group
+    const int R = cr.R;
     SumLB lb{};
-    const double2* tsup = pb.tsup;                             // the parameters' supports: the handle's, or the member's own on a group
-    const double4* prior = pb.prior;                           // likewise the prior table
-    if (member >= 0) {                                         // the member's problem as the sampler read it (magi_sampler_init)
-        DevProblem mp;
-        MAGI_HIP_CHECK(h, hipMemcpy(&mp, h->d_members + member, sizeof(DevProblem), hipMemcpyDeviceToHost));
-        for (int d = 0; d < pb.D; ++d) lb.v[d] = mp.LB[d];
-        tsup = mp.tsup;
-        prior = mp.prior;
-    } else {
-        for (int d = 0; d < pb.D; ++d) lb.v[d] = pb.LB[d];
-    }
-    const double* base = h->ch.samples + (size_t)chain0 * R * pb.dimp;
+    for (int d = 0; d < pb.D; ++d) lb.v[d] = cr.pb.LB[d];
+    const double2* tsup = cr.pb.tsup;
+    const double4* prior = cr.pb.prior;
+    const double* base = cr.base;
     int count = 0;
     if (X_mean || X_sd || X_quant || X_rhat || X_ess || X_mcse_mean || n_nonfinite)
         rc = summarize_block(h, who, base, nullptr, pb.dimp, n_sel, R, pb.ND, MODE_X, pb.N, pb.D, lb, nullptr, nullptr, n_q, pr, max_lag,

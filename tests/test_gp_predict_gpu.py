@@ -138,6 +138,9 @@ def teardown_module(module):
 
 KEYS = ("x_new", "dx_new", "cond_var", "dcond_var")
 SHAPES = [(1, 130), (3, 127), (130, 1), (130, 130)]
+# the tile edges of the transpose to the host layout (64 x 64 tiles over S draws x nc = rows D columns): S around one and two tiles, with
+# gp_chunk_rows 3 and 33 (nc = 6 and 66, below and just above a tile) among the chunkings below
+EDGE_SHAPES = [(63, 130), (64, 130), (65, 130), (129, 130)]
 
 
 def _check_against_reference(b, S, T):
@@ -154,13 +157,13 @@ def _check_against_reference(b, S, T):
     return got
 
 
-@pytest.mark.parametrize("S, T", SHAPES)
+@pytest.mark.parametrize("S, T", SHAPES + EDGE_SHAPES)
 @pytest.mark.parametrize("N", [129, 300])
 def test_gp_predict_on_built_matrices_is_within_the_bars_and_independent_of_chunks_and_runs(N, S, T):
     b = built(N)
     got = _check_against_reference(b, S, T)
     try:
-        for rows in (1, 64, 129):
+        for rows in (1, 3, 33, 64, 129):
             b.e.set_option("gp_chunk_rows", rows)
             chunked = b.run(S, T)
             for k in KEYS:

@@ -111,17 +111,21 @@ def test_ode_unit_is_built_declared_and_bound():
 
 
 def test_ode_unit_compiles_clean_without_scratch_or_spills():
-    """The EXEC-prologue guard passes, and tools/resource_usage.py shows every kernel of the unit in the base library -- k_ode_rk4 for the
-    three compiled-in drifts, k_ode_stats, k_ode_transpose -- with 0 spilled registers and 0 scratch."""
-    from magi_v2_amd import build, isa_check
+    """The EXEC-prologue guard passes, and tools/resource_usage.py shows every kernel of the call in the base library -- k_ode_rk4 for the
+    three compiled-in drifts in ode.hip; k_ode_stats and k_transpose in summary.hip, the drift-free unit a traced drift's library reuses --
+    with 0 spilled registers and 0 scratch."""
+    from magi_v2_amd import build, isa_check, jit
     if shutil.which(build.hipcc()) is None:
         pytest.skip("no hipcc")
     build.build_lib(verbose=False)
-    isa = build.isa_path(os.path.join(build.OBJDIR, "ode.hip.o"))
-    assert os.path.exists(isa) and isa_check.check_file(isa) == []
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), "ode.hip"], capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    rows = [[c.strip() for c in line.split("|")] for line in r.stdout.splitlines() if line.startswith("k_ode_")]
-    assert sorted(row[0].split("(")[0] for row in rows) == ["k_ode_rk4<0>", "k_ode_rk4<1>", "k_ode_rk4<2>", "k_ode_stats", "k_ode_transpose"], r.stdout
+    assert "summary.hip" in jit._DRIFT_FREE
+    rows = []
+    for unit, prefixes in (("ode.hip", ("k_ode_",)), ("summary.hip", ("k_ode_", "k_transpose"))):
+        isa = build.isa_path(os.path.join(build.OBJDIR, unit + ".o"))
+        assert os.path.exists(isa) and isa_check.check_file(isa) == []
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "resource_usage.py"), unit], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        rows += [[c.strip() for c in line.split("|")] for line in r.stdout.splitlines() if line.startswith(prefixes)]
+    assert sorted(row[0].split("(")[0] for row in rows) == ["k_ode_rk4<0>", "k_ode_rk4<1>", "k_ode_rk4<2>", "k_ode_stats", "k_transpose"], rows
     for name, vgprs, vspill, sspill, scratch, occ, lds in rows:
         assert (vspill, sspill, scratch) == ("0", "0", "0"), (name, vspill, sspill, scratch)

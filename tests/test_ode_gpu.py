@@ -27,7 +27,7 @@ from tests.test_ode_cpu import order_errors
 pytestmark = pytest.mark.gpu
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-SIZES = (1, 63, 64, 65, 257)          # lane, wave and workgroup edges
+SIZES = (1, 63, 64, 65, 129, 257)     # lane, wave and workgroup edges; with T D = 6 (seir3, T = 2) and 66 (sqrt_outflow's grid) also the transpose's tile edges
 
 
 @pytest.fixture(scope="module")
@@ -61,7 +61,7 @@ def bars(got, want):
 
 @pytest.mark.parametrize("drift,substeps", [(d, 4) for d in R.CASES] + [(d, 1) for d in R.SUBSTEPS_1_CASES])
 def test_scheme_parity_at_the_lane_wave_and_workgroup_edges(engines, drift, substeps):
-    """S = 1, 63, 64, 65, 257 draws on T = 2 and on the case's grid: every draw finite and within the bar of the float64 reference."""
+    """S = 1, 63, 64, 65, 129, 257 draws on T = 2 and on the case's grid: every draw finite and within the bar of the float64 reference."""
     case = R.CASES[drift]
     want, wstatus = R.reference(drift, substeps)
     assert (wstatus == 0).all()
