@@ -99,7 +99,14 @@ int magi_matern_blocks(magi_handle* h, const double* I, int N, double phi1, doub
 /* User-overwritten or golden matrices (the reference lets users overwrite C_d_invs, m_ds,
  * K_d_invs between fit and predict, magi_v2.py:77-80).  [D][N][N] row-major.  With
  * bandsize >= 0 entries with |i-j| > bandsize are dropped exactly as tf.linalg.band_part
- * does (magi_v2.py:271-274) and the matrices are kept in banded storage N x (2b+1). */
+ * does (magi_v2.py:271-274) and the matrices are kept in banded storage N x (2b+1).
+ * What a matrix change does to the problem.  magi_set_matrices and magi_build_dense forget the problem, whatever the shape: magi_set_problem
+ * must follow (it resets the model), and until it has, the model calls and their getters (magi_set_theta_support, magi_set_prior,
+ * magi_set_obs_model, magi_get_*) return MAGI_E_STATE like every call that needs a problem; so do magi_build_matrices and
+ * magi_pack_resident when N or D change.  magi_pack_resident and magi_build_matrices at an unchanged (N, D) keep the problem AND its
+ * model: mu, N_ds, beta, the observations, the supports of theta, the priors (a fixed variance stays in place of its LB entry), the
+ * links with the transformed data and the weights all stay in force on the new operands, exactly as if they had been set after the
+ * change.  The sampler state and the captured graph are invalidated either way: magi_sampler_init comes next. */
 int magi_set_matrices(magi_handle* h, int N, int D, int bandsize,
                       const double* C_inv, const double* m, const double* K_inv);
 
@@ -265,7 +272,15 @@ int magi_sampler_init(magi_handle* h, const magi_sampler_cfg* cfg, int n_chains,
 
 /* Advance every chain by up to n_steps transitions (burn-in steps count); blocks until done.
  * leapfrogs_done, if not NULL, receives the gradient evaluations taken in this call (sum over
- * chains); kernel_ms the device time between the first and last launch of the call. */
+ * chains); kernel_ms the device time between the first and last launch of the call.
+ * Between two magi_sampler_run calls of one run the chains stand at a transition boundary, and the calls that need the handle only for
+ * its device, its stream or its resident dense matrices may be made: magi_summarize, magi_elpd, magi_gp_predict, magi_matern_cross,
+ * magi_ode_solve, magi_ode_solve_adaptive, magi_dense_apply, magi_theta_init (it captures a graph of its own on the same stream) and
+ * magi_fit_hparams.  Each works in memory of its own, touches neither the chains, the problem nor the sampler's captured graph, and has
+ * finished on the stream when it returns: the continued run is the uninterrupted one bit for bit.  (The calls that end a paused run
+ * say so where they are declared: a matrix, problem, times or model change, magi_logpost_grad*, magi_time_gradient and
+ * magi_sampler_profile -- the next magi_sampler_run then returns MAGI_E_STATE.)  Option "no_graph" may be switched between two calls
+ * as well: direct launches and graph replay run the same kernels on the same arguments. */
 int magi_sampler_run(magi_handle* h, int n_steps, int64_t* leapfrogs_done, double* kernel_ms);
 
 /* Steps completed so far per chain (burn-in included). */
