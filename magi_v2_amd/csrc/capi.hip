@@ -34,8 +34,7 @@ void free_dev(void* p) { if (p) (void)hipFree(p); }
 
 void free_matrices(magi_handle* h) {
     free_dev(h->dCsym); free_dev(h->dM); free_dev(h->dMt); free_dev(h->dKsym); free_dev(h->dYobs);
-    free_dev(h->dObsw);
-    h->dObsw = nullptr; h->pb.obsw = nullptr; h->pb.obs_links = 0;
+    magi_model_default(h->pb, &h->model);          // (frees dObsw)
     free_dev(h->dTimes);
     h->dTimes = nullptr; h->times_N = 0; h->times_cap = 0; h->pb.tgrid = nullptr;
     free_dev(h->dTiles); free_dev(h->dTasks);
@@ -59,14 +58,7 @@ void free_chains(magi_handle* h) {
     h->d_chain_ids = nullptr; h->d_fin = nullptr;
     h->d_scale = h->d_macc = h->d_mwork = nullptr;
     h->window_k0.clear();
-    h->cap_chains = 0; h->n_chains = 0; h->samples_cap = 0; h->diag_cap = 0;
-    h->sampler_ready = false;
-}
-
-void drop_graph(magi_handle* h) {
-    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
-    if (h->graph) (void)hipGraphDestroy(h->graph);
-    h->graph_exec = nullptr; h->graph = nullptr; h->graph_valid = false;
+    h->cap_chains = 0; h->n_chains = 0; h->samples_cap = 0; h->diag_cap = 0; h->tpart_elems = 0; h->vop_elems = 0;
 }
 
 // host <-> device state layout: host X[N][D] row-major  <->  device comp-major [D][N] | sig | th
@@ -99,7 +91,7 @@ int upload_states(magi_handle* h, int n, const double* X, const double* sp, cons
 }
 
 int build_graph(magi_handle* h) {
-    drop_graph(h);
+    magi_stale(h, STALE_GRAPH);
     MAGI_HIP_CHECK(h, hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     int rc = MAGI_OK;
     for (int s = 0; s < kGraphSlots && rc == MAGI_OK; ++s) {          // kGraphSlots is even: a graph starts at slot parity 0
@@ -113,11 +105,6 @@ int build_graph(magi_handle* h) {
     h->graph_valid = true;
     h->graph_slots = kGraphSlots;
     return MAGI_OK;
-}
-
-// doubles of tpart for n chains: the larger of the two streaming paths' layouts
-size_t tpart_elems(const magi_handle* h, int n) {
-    return std::max(magi_sep_tpart_elems(h->pb, n), (size_t)n * 4 * h->pb.D * h->pb.nb * h->pb.Np);
 }
 
 // The options of a handle (MagiOptions), one row each: the name magi_set_option takes, the environment variable magi_create reads
@@ -194,6 +181,20 @@ int group_refresh(magi_handle* h, int n_chains) {
     return MAGI_OK;
 }
 
+// The shared tail of magi_set_times and the three model setters, behind their validation: nothing in flight reads the old table; the sampler
+// level is raised before anything can fail; then, unless the table is `plain` (the default, which the kernels serve without a table), n entries
+// go to dbuf, grown to them first.  cap: dbuf's capacity (the times), or none for a table of one fixed size that is allocated once.
+template <typename T>
+int model_upload(magi_handle* h, const T* tab, size_t n, T*& dbuf, size_t* cap, bool plain) {
+    if (h->stream) MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+    magi_stale(h, STALE_SAMPLER);
+    if (plain) return MAGI_OK;
+    size_t once = dbuf ? n : 0;
+    if (int rc = magi_grow(h, dbuf, cap ? *cap : once, n, "model table")) return rc;
+    MAGI_HIP_CHECK(h, hipMemcpy(dbuf, tab, n * sizeof(T), hipMemcpyHostToDevice));
+    return MAGI_OK;
+}
+
 }  // namespace
 
 void magi_options_from_env(MagiOptions& o) {
@@ -202,54 +203,78 @@ void magi_options_from_env(MagiOptions& o) {
             (void)set_option(o, r, r.rule == FLAG ? 1 : r.rule == FAMILY ? (!strcmp(e, "mc") ? 1 : !strcmp(e, "valu") ? 2 : 0) : atoll(e));
 }
 
+// What makes which state of a handle stale.  Every level includes the ones before it; the call, the level it raises, and why -- the code's
+// counterpart of the sentences of include/magi_hip.h ("forget the problem", "invalidates the sampler state and the captured graph"):
+//
+//   call                                                    level     why
+//   build_graph                                             GRAPH     the old graph goes before the new capture
+//   magi_ensure_chains: another chain count / kernel        GRAPH     grid sizes and the kernel are baked into the graph
+//   magi_sampler_set_metric / _metric_window / _adapt_metric GRAPH    ch.scale / ch.macc change between null and non-null: kernel arguments
+//   magi_logpost_grad*, magi_time_gradient, _debug_wg_trace SAMPLER   they evaluate in the chains' buffers: the sampler's state is clobbered
+//   magi_sampler_init (behind magi_ensure_chains)           SAMPLER   cfg and the output buffers are kernel arguments, the chains are set up anew;
+//                                                                     sampler_ready is set at the call's end, the only place that sets it
+//   magi_sampler_profile (at its end)                       SAMPLER   the chains stand inside a transition
+//   magi_sampler_run: slot budget exhausted                 SAMPLER   a corrupted control block
+//   magi_set_times / _theta_support / _prior / _obs_model   SAMPLER   "invalidates the sampler state and the captured graph": the problem, pointers
+//     (model_upload)                                                  included, is a kernel argument by value
+//   magi_pack_matrices at an unchanged (N, D)               SAMPLER   "the sampler state and the captured graph are invalidated either way"; problem
+//     (magi_pack_resident, magi_build_matrices)                       and model stay (have_matrices is down while it works)
+//   magi_ensure_chains: more chains than there is room for  CHAINS    the block is released and allocated as a whole
+//   magi_destroy                                            CHAINS    (then free_matrices)
+//   magi_set_problem                                        PROBLEM   the old problem is forgotten first (dimp may change: the chains go), the model
+//                                                                     reset; have_problem is set again at the call's end
+//   magi_pack_matrices at another (N, D)                    MATRICES  yobs and dim depend on N, D: "so do magi_build_matrices and magi_pack_resident
+//                                                                     when N or D change"
+//   magi_set_matrices, magi_build_dense                     MATRICES  "forget the problem, whatever the shape"; the packed operands describe the OLD
+//                                                                     dense stacks until a pack has succeeded
+//
+// "SAMPLER includes GRAPH" drops a graph that some of these calls could have kept (the log-posterior and timing calls, the end of
+// magi_sampler_profile, the budget exit).  That cannot be observed: a graph is replayed by magi_sampler_run alone, which needs sampler_ready,
+// which magi_sampler_init alone sets -- behind its own raise of the level.  Likewise the chains and the model go where the problem is
+// forgotten, not at the magi_set_problem that has to follow: the chains hold nothing a call accepts without a problem, and magi_set_problem
+// releases them and resets the model whatever it finds.  magi_sampler_init raises its level before its first step that can fail: a failed
+// initialisation leaves a sampler that is not ready, not the previous run over buffers the failed call has already rewritten.
+void magi_stale(magi_handle* h, MagiStale level) {
+    if (h->graph_exec) (void)hipGraphExecDestroy(h->graph_exec);
+    if (h->graph) (void)hipGraphDestroy(h->graph);
+    h->graph_exec = nullptr; h->graph = nullptr; h->graph_valid = false;
+    if (level >= STALE_SAMPLER) h->sampler_ready = false;
+    if (level >= STALE_CHAINS) free_chains(h);
+    if (level >= STALE_PROBLEM) { h->have_problem = false; magi_model_default(h->pb, &h->model); }
+    if (level >= STALE_MATRICES) h->have_matrices = false;
+}
+
 double* magi_workspace(magi_handle* h, int k, size_t n) {
-    if (n <= h->ws_cap[k]) return h->ws[k];
-    if (h->ws[k]) (void)hipFree(h->ws[k]);
-    h->ws[k] = nullptr; h->ws_cap[k] = 0;
-    if (hipMalloc(&h->ws[k], n * sizeof(double)) != hipSuccess) {
-        (void)hipGetLastError();
-        h->ws[k] = nullptr;
-        magi_fail(h, MAGI_E_HIP, "work space allocation failed (" + std::to_string(n * sizeof(double) >> 20) + " MiB)");
-        return nullptr;
-    }
-    h->ws_cap[k] = n;
-    return h->ws[k];
+    return magi_grow(h, h->ws[k], h->ws_cap[k], n, "work space") == MAGI_OK ? h->ws[k] : nullptr;
 }
 
 int magi_ensure_chains(magi_handle* h, int n) {
     if (!h->group_n && (!h->have_matrices || !h->have_problem)) return magi_fail(h, MAGI_E_STATE, "set matrices and problem first");
     if (n <= 0 || n > 4096) return magi_fail(h, MAGI_E_BADARG, "n_chains out of range");
     if (n > h->cap_chains) {
-        free_chains(h);
-        const size_t vbytes = (size_t)n * V_COUNT * h->pb.dimp * sizeof(double);
-        MAGI_HIP_CHECK(h, hipMalloc(&h->ch.vec, vbytes));
-        MAGI_HIP_CHECK(h, hipMemset(h->ch.vec, 0, vbytes));
-        MAGI_HIP_CHECK(h, hipMalloc(&h->ch.ctl, sizeof(ChainCtl) * n));
-        MAGI_HIP_CHECK(h, hipMemset(h->ch.ctl, 0, sizeof(ChainCtl) * n));
-        MAGI_HIP_CHECK(h, hipMalloc(&h->ch.par, sizeof(double) * PAR_COUNT * n));
-        MAGI_HIP_CHECK(h, hipMemset(h->ch.par, 0, sizeof(double) * PAR_COUNT * n));
-        MAGI_HIP_CHECK(h, hipMalloc(&h->ch.plan, sizeof(LeafPlan) * 2 * n));
-        MAGI_HIP_CHECK(h, hipMemset(h->ch.plan, 0, sizeof(LeafPlan) * 2 * n));
-        h->ch.n_wg = magi_leap_wgs(h->pb);
-        MAGI_HIP_CHECK(h, hipMalloc(&h->ch.part, sizeof(double) * PART_K * h->ch.n_wg * n));
-        MAGI_HIP_CHECK(h, hipMemset(h->ch.part, 0, sizeof(double) * PART_K * h->ch.n_wg * n));
-        const size_t tpn = tpart_elems(h, n);
-        MAGI_HIP_CHECK(h, hipMalloc(&h->ch.tpart, sizeof(double) * tpn));
-        MAGI_HIP_CHECK(h, hipMemset(h->ch.tpart, 0, sizeof(double) * tpn));     // slots outside the block band stay zero
-        const size_t opn = (size_t)2 * ((n + 15) / 16) * h->pb.D * h->pb.Np * 16;
-        MAGI_HIP_CHECK(h, hipMalloc(&h->ch.xop, sizeof(double) * opn));
-        MAGI_HIP_CHECK(h, hipMemset(h->ch.xop, 0, sizeof(double) * opn));
-        h->vop_elems = magi_drift_separable(h->pb.drift) ? magi_sep_vop_elems(h->pb, n) : 16;
-        MAGI_HIP_CHECK(h, hipMalloc(&h->ch.vop, sizeof(double) * h->vop_elems));
-        MAGI_HIP_CHECK(h, hipMemset(h->ch.vop, 0, sizeof(double) * h->vop_elems));
-        MAGI_HIP_CHECK(h, hipMalloc(&h->ch.gctl, sizeof(GlobalCtl)));
-        MAGI_HIP_CHECK(h, hipMemset(h->ch.gctl, 0, sizeof(GlobalCtl)));
+        magi_stale(h, STALE_CHAINS);     // (all null and cap_chains 0 before the first allocation, cap_chains set behind the last: the next call cleans up a failure)
+        DevChains& c = h->ch;
+        const DevProblem& pb = h->pb;
+        auto zeroed = [h](auto*& p, size_t elems) {
+            MAGI_HIP_CHECK(h, hipMalloc(reinterpret_cast<void**>(&p), sizeof(*p) * elems));
+            MAGI_HIP_CHECK(h, hipMemset(p, 0, sizeof(*p) * elems));
+            return (int)MAGI_OK;
+        };
+        c.n_wg = magi_leap_wgs(pb);
+        h->tpart_elems = std::max(magi_sep_tpart_elems(pb, n), (size_t)n * 4 * pb.D * pb.nb * pb.Np);      // the larger of the two streaming paths' layouts
+        h->vop_elems = magi_drift_separable(pb.drift) ? magi_sep_vop_elems(pb, n) : 16;
+        int rc;
+        if ((rc = zeroed(c.vec, (size_t)n * V_COUNT * pb.dimp)) || (rc = zeroed(c.ctl, (size_t)n)) || (rc = zeroed(c.par, (size_t)PAR_COUNT * n)) ||
+            (rc = zeroed(c.plan, (size_t)2 * n)) || (rc = zeroed(c.part, (size_t)PART_K * c.n_wg * n)) ||
+            (rc = zeroed(c.tpart, h->tpart_elems)) ||                                     // slots outside the block band stay zero
+            (rc = zeroed(c.xop, (size_t)2 * ((n + 15) / 16) * pb.D * pb.Np * 16)) || (rc = zeroed(c.vop, h->vop_elems)) || (rc = zeroed(c.gctl, (size_t)1)))
+            return rc;
         MAGI_HIP_CHECK(h, hipMalloc(&h->d_chain_ids, sizeof(long long) * n));
         MAGI_HIP_CHECK(h, hipMalloc(&h->d_fin, sizeof(double) * 8 * n));
         h->cap_chains = n;
     }
     const StreamKernel k = magi_stream_kernel(h, n);
-    if (h->n_chains != n || k != h->stream_kernel) drop_graph(h);
+    if (h->n_chains != n || k != h->stream_kernel) magi_stale(h, STALE_GRAPH);
     if (h->n_chains != n && h->ch.vop)       // the mirror's layout depends on the chain count: entries the new layout never writes must read zero
         MAGI_HIP_CHECK(h, hipMemsetAsync(h->ch.vop, 0, sizeof(double) * h->vop_elems, h->stream));
     h->n_chains = n;
@@ -257,7 +282,7 @@ int magi_ensure_chains(magi_handle* h, int n) {
     h->stream_kernel = k;
     const bool sepk = k == StreamKernel::Sep8 || k == StreamKernel::Sep16;
     if ((h->ch.sep != 0) != sepk && h->ch.tpart)      // the two streaming paths lay tpart out differently: slots the new one never writes must read zero
-        MAGI_HIP_CHECK(h, hipMemsetAsync(h->ch.tpart, 0, sizeof(double) * tpart_elems(h, h->cap_chains), h->stream));
+        MAGI_HIP_CHECK(h, hipMemsetAsync(h->ch.tpart, 0, sizeof(double) * h->tpart_elems, h->stream));
     h->ch.sep = sepk ? 1 : 0;
     h->ch.mc = k == StreamKernel::Mc ? 1 : 0;
     return MAGI_OK;
@@ -333,12 +358,11 @@ void magi_destroy(magi_handle* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    drop_graph(h);
-    free_chains(h);
+    magi_stale(h, STALE_CHAINS);
     free_matrices(h);
     free_dev(h->d_members);          // (a group's members are the caller's)
-    free_dev(h->dTsup);
-    free_dev(h->dPrior);
+    free_dev(h->model.dTsup);
+    free_dev(h->model.dPrior);
     for (int i = 0; i < 4; ++i) if (h->ev[i]) (void)hipEventDestroy(h->ev[i]);
     if (h->ev_t0) (void)hipEventDestroy(h->ev_t0);
     if (h->ev_t1) (void)hipEventDestroy(h->ev_t1);
@@ -375,18 +399,12 @@ int magi_group_create(magi_handle* const* members, int n_members, magi_handle** 
     g->pb.Csym = g->pb.M = g->pb.Mt = g->pb.Ksym = g->pb.yobs = g->pb.tiles = nullptr;
     g->pb.tasks = g->pb.stasks = nullptr;
     g->pb.tgrid = nullptr;
-    g->pb.tsup = nullptr;                          // (every member brings its own supports)
-    g->pb.prior = nullptr;                         // (and its own priors)
-    g->pb.fixed_mask = 0;
-    g->pb.obs_links = 0;                           // (and its own observation model)
-    g->pb.obsw = nullptr;
-    hipError_t e = hipMalloc(&g->d_members, sizeof(DevProblem) * n_members);
-    if (e != hipSuccess) {
-        magi_destroy(g);
-        return magi_fail(nullptr, MAGI_E_HIP, std::string("group table: ") + hipGetErrorString(e));
-    }
-    *out = g;
-    return MAGI_OK;
+    magi_model_default(g->pb, nullptr);            // (every member brings its own supports, priors and observation model)
+    size_t cap = 0;
+    const int rc = magi_grow(g, g->d_members, cap, (size_t)n_members, "group table");      // (the message stays in magi_last_error(NULL))
+    if (rc) magi_destroy(g);
+    else *out = g;
+    return rc;
 }
 
 int magi_set_matrices(magi_handle* h, int N, int D, int bandsize, const double* C_inv, const double* m,
@@ -396,8 +414,7 @@ int magi_set_matrices(magi_handle* h, int N, int D, int bandsize, const double* 
     if (!C_inv || !m || !K_inv) return magi_fail(h, MAGI_E_BADARG, "null matrix pointer");
     if (N < 2 || D < 1 || D > MAGI_MAX_D) return magi_fail(h, MAGI_E_BADARG, "need N >= 2 and 1 <= D <= " + std::to_string(MAGI_MAX_D));
     (void)hipSetDevice(h->device);
-    h->have_matrices = false;          // the packed operands describe the OLD dense stacks until the pack below has succeeded
-    h->sampler_ready = false;
+    magi_stale(h, STALE_MATRICES);     // the packed operands describe the OLD dense stacks until the pack below has succeeded
     const size_t bytes = (size_t)D * N * N * sizeof(double);
     int rc = magi_ensure_dense(h, N, D);
     if (rc) return rc;
@@ -416,8 +433,7 @@ int magi_build_dense(magi_handle* h, const double* I, int N, int D, int n_sel, c
     if (N < 2 || D < 1 || D > MAGI_MAX_D || n_sel < 1 || n_sel > D) return magi_fail(h, MAGI_E_BADARG, "need N >= 2, 1 <= D <= " + std::to_string(MAGI_MAX_D) + " and 1 <= n_sel <= D");
     if (!(nu > 1.0)) return magi_fail(h, MAGI_E_BADARG, "nu must exceed 1 (once-differentiable Matern)");
     (void)hipSetDevice(h->device);
-    h->have_matrices = false;          // the packed operands no longer match the dense stacks until magi_pack_resident
-    h->sampler_ready = false;
+    magi_stale(h, STALE_MATRICES);     // the packed operands no longer match the dense stacks until magi_pack_resident
     std::vector<int> s(sel, sel + n_sel);
     return magi_build_dense_device(h, I, N, D, n_sel, s.data(), phi1, phi2, nu);
 }
@@ -548,17 +564,14 @@ int magi_set_problem(magi_handle* h, const double* mu, const double* N_ds, const
         yobs[(size_t)d * N + i] = y[k];
         obs_e[(size_t)k] = (int64_t)d * N + i;
     }
-    free_dev(h->dYobs);
-    h->dYobs = nullptr;
-    free_dev(h->dObsw);                                            // (a new problem: identity links, no weights; the data kept for magi_set_obs_model)
-    h->dObsw = nullptr;
-    pb.obsw = nullptr;
-    pb.obs_links = 0;
-    for (int d = 0; d < MAGI_MAX_D; ++d) h->ob_link[d] = MAGI_LINK_IDENTITY;
-    h->obs_w.clear();
-    h->obs_e.swap(obs_e);
-    h->obs_y.assign(y, y + n_obs);
-    MAGI_HIP_CHECK(h, hipMalloc(&h->dYobs, sizeof(double) * N * D));
+    // the old problem is forgotten before the first call that can fail (dimp may change: the chains go); the new one starts from the default model
+    for (int d = 0; d < MAGI_MAX_D; ++d) h->model.lb_orig[d] = d < D ? LB[d] : 0.0;
+    magi_stale(h, STALE_PROBLEM);                                  // (pb.LB = lb_orig)
+    h->model.obs_e.swap(obs_e);
+    h->model.obs_y.assign(y, y + n_obs);
+    pb.yobs = nullptr;
+    size_t cap = 0;                                                // (sized exactly: a new block for every problem)
+    if (int rc = magi_grow(h, h->dYobs, cap, (size_t)N * D, "observations")) return rc;
     MAGI_HIP_CHECK(h, hipMemcpy(h->dYobs, yobs.data(), sizeof(double) * N * D, hipMemcpyHostToDevice));
     pb.yobs = h->dYobs;
     pb.P = P;
@@ -569,17 +582,8 @@ int magi_set_problem(magi_handle* h, const double* mu, const double* N_ds, const
     for (int d = 0; d < MAGI_MAX_D; ++d) {
         pb.mu[d] = d < D ? mu[d] : 0.0;
         pb.N_ds[d] = d < D ? N_ds[d] : 0.0;
-        pb.LB[d] = d < D ? LB[d] : 0.0;
     }
-    for (int p = 0; p < MAGI_MAX_P; ++p) { h->th_kind[p] = MAGI_THETA_POSITIVE; h->th_bound[p] = 0.0; }      // (a new problem: every parameter positive)
-    pb.tsup = nullptr;
-    for (int j = 0; j < MAGI_MAX_D + MAGI_MAX_P; ++j) { h->pr_kind[j] = MAGI_PRIOR_FLAT; h->pr_a[j] = h->pr_b[j] = 0.0; }      // (and every prior flat)
-    pb.prior = nullptr;
-    pb.fixed_mask = 0;
-    for (int d = 0; d < MAGI_MAX_D; ++d) h->lb_orig[d] = pb.LB[d];
     h->have_problem = true;
-    free_chains(h);          // dimp may have changed
-    drop_graph(h);
     return MAGI_OK;
 }
 
@@ -595,19 +599,11 @@ int magi_set_times(magi_handle* h, const double* t, int n) {
         if (!std::isfinite(t[i])) return magi_fail(h, MAGI_E_BADARG, "magi_set_times: t[" + std::to_string(i) + "] is not finite");
     (void)hipSetDevice(h->device);
     const size_t np_ = ((size_t)n + MAGI_TB - 1) / MAGI_TB * MAGI_TB;        // = pb.Np: padded with the last time, no load needs a bounds test
-    if (h->stream) MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // (nothing in flight reads the old times)
-    h->sampler_ready = false;
-    drop_graph(h);                                                           // (the problem, pointer included, is a kernel argument of the captured graph)
-    h->times_N = 0;
-    if (np_ > h->times_cap) {
-        free_dev(h->dTimes);
-        h->dTimes = nullptr; h->times_cap = 0; h->pb.tgrid = nullptr;
-        MAGI_HIP_CHECK(h, hipMalloc(&h->dTimes, np_ * sizeof(double)));
-        h->times_cap = np_;
-    }
     std::vector<double> pad(np_, t[n - 1]);
     std::copy(t, t + n, pad.begin());
-    MAGI_HIP_CHECK(h, hipMemcpy(h->dTimes, pad.data(), np_ * sizeof(double), hipMemcpyHostToDevice));
+    h->times_N = 0;
+    h->pb.tgrid = nullptr;
+    if (int rc = model_upload(h, pad.data(), np_, h->dTimes, &h->times_cap, false)) return rc;
     h->pb.tgrid = h->dTimes;
     h->times_N = n;
     return MAGI_OK;
@@ -636,22 +632,17 @@ int magi_set_theta_support(magi_handle* h, int P, const int* kind, const double*
             return magi_fail(h, MAGI_E_BADARG, "magi_set_theta_support: the bound of parameter " + std::to_string(p) + " is missing or not finite");
         kd[p] = k;
         bd[p] = bounded ? bound[p] : 0.0;
-        if (prior_needs_positive(h->pr_kind[h->pb.D + p]) && !support_is_positive(k, bd[p]))
+        if (prior_needs_positive(h->model.pr_kind[h->pb.D + p]) && !support_is_positive(k, bd[p]))
             return magi_fail(h, MAGI_E_BADARG, "magi_set_theta_support: parameter " + std::to_string(p) + " has a lognormal, gamma or inverse-gamma prior (magi_set_prior), "
                                                "which needs a support inside (0, inf): POSITIVE, or LOWER with a bound >= 0");
         tab[p] = make_double2(k == MAGI_THETA_REAL ? 0.0 : k == MAGI_THETA_UPPER ? -1.0 : 1.0, bd[p]);
         plain = plain && k == MAGI_THETA_POSITIVE;
     }
     (void)hipSetDevice(h->device);
-    if (h->stream) MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // (nothing in flight reads the old table)
-    if (!plain) {
-        if (!h->dTsup) MAGI_HIP_CHECK(h, hipMalloc(&h->dTsup, sizeof(double2) * MAGI_MAX_P));
-        MAGI_HIP_CHECK(h, hipMemcpy(h->dTsup, tab, sizeof(tab), hipMemcpyHostToDevice));
-    }
-    h->sampler_ready = false;
-    drop_graph(h);                                                           // (the problem, pointer included, is a kernel argument of the captured graph)
-    for (int p = 0; p < MAGI_MAX_P; ++p) { h->th_kind[p] = kd[p]; h->th_bound[p] = bd[p]; }
-    h->pb.tsup = plain ? nullptr : h->dTsup;                                 // all-positive: no table, the kernels' default path
+    MagiModel& m = h->model;
+    if (int rc = model_upload(h, tab, (size_t)MAGI_MAX_P, m.dTsup, nullptr, plain)) return rc;
+    for (int p = 0; p < MAGI_MAX_P; ++p) { m.th_kind[p] = kd[p]; m.th_bound[p] = bd[p]; }
+    h->pb.tsup = plain ? nullptr : m.dTsup;                                  // all-positive: no table, the kernels' default path
     return MAGI_OK;
 }
 
@@ -661,8 +652,8 @@ int magi_get_theta_support(magi_handle* h, int P, int* kind, double* bound) {
     if (!h->have_problem) return magi_fail(h, MAGI_E_STATE, "magi_get_theta_support: set the problem first");
     if (P != h->pb.P) return magi_fail(h, MAGI_E_BADARG, "magi_get_theta_support: P = " + std::to_string(P) + ", the problem has " + std::to_string(h->pb.P) + " parameters");
     for (int p = 0; p < P; ++p) {
-        if (kind) kind[p] = h->th_kind[p];
-        if (bound) bound[p] = h->th_bound[p];
+        if (kind) kind[p] = h->model.th_kind[p];
+        if (bound) bound[p] = h->model.th_bound[p];
     }
     return MAGI_OK;
 }
@@ -692,7 +683,7 @@ int magi_set_prior(magi_handle* h, int n, const int* kind, const double* a, cons
         const bool a_pos = k == MAGI_PRIOR_GAMMA || k == MAGI_PRIOR_INVGAMMA || k == MAGI_PRIOR_FIXED;      // (shape, shape, value; a normal's or lognormal's m is free)
         if ((a_pos && !(a[e] > 0.0)) || (k != MAGI_PRIOR_FIXED && !(b[e] > 0.0)))
             return magi_fail(h, MAGI_E_BADARG, "magi_set_prior: " + who + ": sd, shape, rate, scale and a fixed value must be > 0");
-        if (e >= D && prior_needs_positive(k) && !support_is_positive(h->th_kind[e - D], h->th_bound[e - D]))
+        if (e >= D && prior_needs_positive(k) && !support_is_positive(h->model.th_kind[e - D], h->model.th_bound[e - D]))
             return magi_fail(h, MAGI_E_BADARG, "magi_set_prior: " + who + ": a lognormal, gamma or inverse-gamma prior needs a support inside (0, inf): POSITIVE, or LOWER with a "
                                                "bound >= 0 (magi_set_theta_support comes first)");
         kd[e] = k; av[e] = a[e]; bv[e] = k == MAGI_PRIOR_FIXED ? 0.0 : b[e];
@@ -701,18 +692,13 @@ int magi_set_prior(magi_handle* h, int n, const int* kind, const double* a, cons
         plain = false;
     }
     (void)hipSetDevice(h->device);
-    if (h->stream) MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // (nothing in flight reads the old table)
-    if (!plain) {
-        if (!h->dPrior) MAGI_HIP_CHECK(h, hipMalloc(&h->dPrior, sizeof(double4) * NT));
-        MAGI_HIP_CHECK(h, hipMemcpy(h->dPrior, tab, sizeof(tab), hipMemcpyHostToDevice));
-    }
-    h->sampler_ready = false;
-    drop_graph(h);                                                           // (the problem, pointer included, is a kernel argument of the captured graph)
-    for (int j = 0; j < NT; ++j) { h->pr_kind[j] = kd[j]; h->pr_a[j] = av[j]; h->pr_b[j] = bv[j]; }
-    h->pb.prior = plain ? nullptr : h->dPrior;                               // all flat: no table, the kernels' default path
+    MagiModel& m = h->model;
+    if (int rc = model_upload(h, tab, (size_t)NT, m.dPrior, nullptr, plain)) return rc;
+    for (int j = 0; j < NT; ++j) { m.pr_kind[j] = kd[j]; m.pr_a[j] = av[j]; m.pr_b[j] = bv[j]; }
+    h->pb.prior = plain ? nullptr : m.dPrior;                                // all flat: no table, the kernels' default path
     h->pb.fixed_mask = 0;                                                    // a fixed sigma^2_d: bit d, and its constant in place of LB[d]
     for (int d = 0; d < D; ++d) {
-        h->pb.LB[d] = kd[d] == MAGI_PRIOR_FIXED ? av[d] : h->lb_orig[d];
+        h->pb.LB[d] = kd[d] == MAGI_PRIOR_FIXED ? av[d] : m.lb_orig[d];
         if (kd[d] == MAGI_PRIOR_FIXED) h->pb.fixed_mask |= 1 << d;
     }
     return MAGI_OK;
@@ -724,9 +710,9 @@ int magi_get_prior(magi_handle* h, int n, int* kind, double* a, double* b) {
     if (!h->have_problem) return magi_fail(h, MAGI_E_STATE, "magi_get_prior: set the problem first");
     if (n != h->pb.D + h->pb.P) return magi_fail(h, MAGI_E_BADARG, "magi_get_prior: n = " + std::to_string(n) + ", the problem has D + P = " + std::to_string(h->pb.D + h->pb.P) + " parameter entries");
     for (int e = 0; e < n; ++e) {
-        if (kind) kind[e] = h->pr_kind[e];
-        if (a) a[e] = h->pr_a[e];
-        if (b) b[e] = h->pr_b[e];
+        if (kind) kind[e] = h->model.pr_kind[e];
+        if (a) a[e] = h->model.pr_a[e];
+        if (b) b[e] = h->model.pr_b[e];
     }
     return MAGI_OK;
 }
@@ -737,8 +723,8 @@ int magi_set_obs_model(magi_handle* h, int D, const int* link, int64_t n_obs, co
     if (!h->have_problem) return magi_fail(h, MAGI_E_STATE, "magi_set_obs_model: set the problem first (magi_set_problem resets the observation model)");
     const int N = h->pb.N;
     if (D != h->pb.D) return magi_fail(h, MAGI_E_BADARG, "magi_set_obs_model: D = " + std::to_string(D) + ", the problem has " + std::to_string(h->pb.D) + " components");
-    if (n_obs != (int64_t)h->obs_e.size())
-        return magi_fail(h, MAGI_E_BADARG, "magi_set_obs_model: n_obs = " + std::to_string(n_obs) + ", magi_set_problem was given " + std::to_string(h->obs_e.size()) + " observations");
+    if (n_obs != (int64_t)h->model.obs_e.size())
+        return magi_fail(h, MAGI_E_BADARG, "magi_set_obs_model: n_obs = " + std::to_string(n_obs) + ", magi_set_problem was given " + std::to_string(h->model.obs_e.size()) + " observations");
     int lk[MAGI_MAX_D] = {};
     int links = 0;
     for (int d = 0; link && d < D; ++d) {
@@ -754,25 +740,22 @@ int magi_set_obs_model(magi_handle* h, int D, const int* link, int64_t n_obs, co
     std::vector<double> gy((size_t)N * D, std::nan("")), w;
     if (weight) w.assign((size_t)N * D, 1.0);
     for (int64_t k = 0; k < n_obs; ++k) {
-        const int64_t e = h->obs_e[(size_t)k];
+        const int64_t e = h->model.obs_e[(size_t)k];
         const int d = (int)(e / N);
-        const double y = h->obs_y[(size_t)k];
+        const double y = h->model.obs_y[(size_t)k];
         if (!std::isnan(y) && ((lk[d] == MAGI_LINK_LOG && !(y > 0.0)) || (lk[d] == MAGI_LINK_SQRT && !(y >= 0.0))))
             return magi_fail(h, MAGI_E_BADARG, "magi_set_obs_model: observation " + std::to_string(k) + " of component " + std::to_string(d) + " is outside the domain of its link (log: y > 0, sqrt: y >= 0)");
         gy[(size_t)e] = lk[d] == MAGI_LINK_LOG ? std::log(y) : lk[d] == MAGI_LINK_SQRT ? std::sqrt(y) : y;
         if (weight) w[(size_t)e] = weight[k];
     }
     (void)hipSetDevice(h->device);
-    if (h->stream) MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));       // (nothing in flight reads the old data)
-    if (weight && !h->dObsw) MAGI_HIP_CHECK(h, hipMalloc(&h->dObsw, sizeof(double) * N * D));
-    if (weight) MAGI_HIP_CHECK(h, hipMemcpy(h->dObsw, w.data(), sizeof(double) * N * D, hipMemcpyHostToDevice));
+    MagiModel& m = h->model;
+    if (int rc = model_upload(h, w.data(), (size_t)N * D, m.dObsw, nullptr, !weight)) return rc;
     MAGI_HIP_CHECK(h, hipMemcpy(h->dYobs, gy.data(), sizeof(double) * N * D, hipMemcpyHostToDevice));
-    h->sampler_ready = false;
-    drop_graph(h);                                                           // (the problem is a kernel argument of the captured graph)
-    for (int d = 0; d < MAGI_MAX_D; ++d) h->ob_link[d] = lk[d];
-    if (weight) h->obs_w.assign(weight, weight + n_obs); else h->obs_w.clear();
+    for (int d = 0; d < MAGI_MAX_D; ++d) m.ob_link[d] = lk[d];
+    if (weight) m.obs_w.assign(weight, weight + n_obs); else m.obs_w.clear();
     h->pb.obs_links = links;                                                 // all identity and no weights: the kernels' default path
-    h->pb.obsw = weight ? h->dObsw : nullptr;
+    h->pb.obsw = weight ? m.dObsw : nullptr;
     return MAGI_OK;
 }
 
@@ -781,10 +764,10 @@ int magi_get_obs_model(magi_handle* h, int D, int* link, int64_t n_obs, double* 
     if (h->group_n) return refuse_group(h, "magi_get_obs_model");
     if (!h->have_problem) return magi_fail(h, MAGI_E_STATE, "magi_get_obs_model: set the problem first");
     if (D != h->pb.D) return magi_fail(h, MAGI_E_BADARG, "magi_get_obs_model: D = " + std::to_string(D) + ", the problem has " + std::to_string(h->pb.D) + " components");
-    if (n_obs != (int64_t)h->obs_e.size())
-        return magi_fail(h, MAGI_E_BADARG, "magi_get_obs_model: n_obs = " + std::to_string(n_obs) + ", magi_set_problem was given " + std::to_string(h->obs_e.size()) + " observations");
-    for (int d = 0; link && d < D; ++d) link[d] = h->ob_link[d];
-    for (int64_t k = 0; weight && k < n_obs; ++k) weight[k] = h->obs_w.empty() ? 1.0 : h->obs_w[(size_t)k];
+    if (n_obs != (int64_t)h->model.obs_e.size())
+        return magi_fail(h, MAGI_E_BADARG, "magi_get_obs_model: n_obs = " + std::to_string(n_obs) + ", magi_set_problem was given " + std::to_string(h->model.obs_e.size()) + " observations");
+    for (int d = 0; link && d < D; ++d) link[d] = h->model.ob_link[d];
+    for (int64_t k = 0; weight && k < n_obs; ++k) weight[k] = h->model.obs_w.empty() ? 1.0 : h->model.obs_w[(size_t)k];
     return MAGI_OK;
 }
 
@@ -796,7 +779,7 @@ static int logpost_grad_impl(magi_handle* h, bool fused, int n_chains, const dou
     (void)hipSetDevice(h->device);
     int rc = magi_ensure_chains(h, n_chains);
     if (rc) return rc;
-    h->sampler_ready = false;
+    magi_stale(h, STALE_SAMPLER);
     const DevProblem& pb = h->pb;
     if ((rc = upload_states(h, n_chains, X, sig_pre, th_pre))) return rc;
     MAGI_HIP_CHECK(h, hipMemsetAsync(h->ch.gctl, 0, sizeof(GlobalCtl), h->stream));
@@ -869,6 +852,7 @@ int magi_sampler_init(magi_handle* h, const magi_sampler_cfg* cfg, int n_chains,
     int rc;
     if (h->group_n && (rc = group_refresh(h, n_chains))) return rc;
     if ((rc = magi_ensure_chains(h, n_chains))) return rc;
+    magi_stale(h, STALE_SAMPLER);    // cfg and the buffers are baked into the captured graph; the sampler is ready again at the end of this call
     const DevProblem& pb = h->pb;
     SamplerCfgDev& c = h->cfg;
     c.total = cfg->num_results + cfg->num_burnin_steps;
@@ -886,36 +870,21 @@ int magi_sampler_init(magi_handle* h, const magi_sampler_cfg* cfg, int n_chains,
     c.seed = seed;
     h->num_results = cfg->num_results;
 
-    // output buffers
-    const size_t need_s = (size_t)n_chains * std::max(1, cfg->num_results) * pb.dimp;
-    if (need_s > h->samples_cap) {
-        free_dev(h->ch.samples);
-        h->ch.samples = nullptr;
-        MAGI_HIP_CHECK(h, hipMalloc(&h->ch.samples, need_s * sizeof(double)));
-        h->samples_cap = need_s;
-    }
-    const size_t need_d = (size_t)n_chains * c.total;
-    if (need_d > h->diag_cap) {
-        DevChains& d = h->ch;
-        free_dev(d.d_step_size); free_dev(d.d_lar); free_dev(d.d_target); free_dev(d.d_energy); free_dev(d.d_beta);
-        free_dev(d.d_leapfrogs); free_dev(d.d_depth); free_dev(d.d_flags);
-        MAGI_HIP_CHECK(h, hipMalloc(&d.d_step_size, need_d * sizeof(double)));
-        MAGI_HIP_CHECK(h, hipMalloc(&d.d_lar, need_d * sizeof(double)));
-        MAGI_HIP_CHECK(h, hipMalloc(&d.d_target, need_d * sizeof(double)));
-        MAGI_HIP_CHECK(h, hipMalloc(&d.d_energy, need_d * sizeof(double)));
-        MAGI_HIP_CHECK(h, hipMalloc(&d.d_beta, need_d * sizeof(double)));
-        MAGI_HIP_CHECK(h, hipMalloc(&d.d_leapfrogs, need_d * sizeof(int)));
-        MAGI_HIP_CHECK(h, hipMalloc(&d.d_depth, need_d * sizeof(int)));
-        MAGI_HIP_CHECK(h, hipMalloc(&d.d_flags, need_d * sizeof(int)));
-        h->diag_cap = need_d;
-    }
-    {   // steps not taken yet read as NaN / -1, not as whatever the allocation held
-        DevChains& d = h->ch;
-        MAGI_HIP_CHECK(h, hipMemsetAsync(d.samples, 0xFF, need_s * sizeof(double), h->stream));
-        for (double* p : {d.d_step_size, d.d_lar, d.d_target, d.d_energy, d.d_beta}) MAGI_HIP_CHECK(h, hipMemsetAsync(p, 0xFF, need_d * sizeof(double), h->stream));
-        for (int* p : {d.d_leapfrogs, d.d_depth, d.d_flags}) MAGI_HIP_CHECK(h, hipMemsetAsync(p, 0xFF, need_d * sizeof(int), h->stream));
-    }
-    drop_graph(h);   // kernel arguments (cfg, buffers) are baked into the captured graph
+    // output buffers (grow-only); the eight diagnostics arrays share a capacity that is down while they grow: a failure part-way leaves each null or valid
+    const size_t need_s = (size_t)n_chains * std::max(1, cfg->num_results) * pb.dimp, need_d = (size_t)n_chains * c.total;
+    DevChains& d = h->ch;
+    if ((rc = magi_grow(h, d.samples, h->samples_cap, need_s, "sample buffer"))) return rc;
+    const size_t had_d = h->diag_cap;
+    h->diag_cap = 0;
+    auto grow_d = [&](auto*& p) { size_t cap = had_d; return magi_grow(h, p, cap, need_d, "sampler diagnostics"); };
+    if ((rc = grow_d(d.d_step_size)) || (rc = grow_d(d.d_lar)) || (rc = grow_d(d.d_target)) || (rc = grow_d(d.d_energy)) || (rc = grow_d(d.d_beta)) ||
+        (rc = grow_d(d.d_leapfrogs)) || (rc = grow_d(d.d_depth)) || (rc = grow_d(d.d_flags)))
+        return rc;
+    h->diag_cap = std::max(had_d, need_d);
+    // steps not taken yet read as NaN / -1, not as whatever the allocation held
+    MAGI_HIP_CHECK(h, hipMemsetAsync(d.samples, 0xFF, need_s * sizeof(double), h->stream));
+    for (double* p : {d.d_step_size, d.d_lar, d.d_target, d.d_energy, d.d_beta}) MAGI_HIP_CHECK(h, hipMemsetAsync(p, 0xFF, need_d * sizeof(double), h->stream));
+    for (int* p : {d.d_leapfrogs, d.d_depth, d.d_flags}) MAGI_HIP_CHECK(h, hipMemsetAsync(p, 0xFF, need_d * sizeof(int), h->stream));
     h->ch.scale = nullptr;       // a fresh sampler: identity metric, no metric window
     h->ch.macc = nullptr;
     h->window_k0.clear();
@@ -998,7 +967,7 @@ int magi_sampler_run(magi_handle* h, int n_steps, int64_t* leapfrogs_done, doubl
             std::string where;
             for (int i = 0; i < h->n_chains; ++i)
                 if (ctl[i].phase != PH_IDLE || ctl[i].k < g.stop_k) { where = " (chain " + std::to_string(i) + ": k=" + std::to_string(ctl[i].k) + ", phase=" + std::to_string(ctl[i].phase) + ", depth=" + std::to_string(ctl[i].depth) + ")"; break; }
-            h->sampler_ready = false;
+            magi_stale(h, STALE_SAMPLER);
             return magi_fail(h, MAGI_E_STATE, "sampler did not finish within its slot budget" + where);
         }
         while (issued - retired < depth && issued < max_graphs) {
@@ -1094,7 +1063,7 @@ int magi_sampler_profile(magi_handle* h, int n_slots, double* stream_us, double*
     if (leapfrogs_done) *leapfrogs_done = lf1 - lf0;
     // the chains stand somewhere inside a transition: the sampler state is no longer at a transition boundary a later
     // magi_sampler_run could be compared against anything from -- the handle must be re-initialised
-    h->sampler_ready = false;
+    magi_stale(h, STALE_SAMPLER);
     return MAGI_OK;
 }
 
@@ -1174,15 +1143,7 @@ static double ckpt_tag(const magi_handle* h, long long chain_id) {
     const int ints[9] = {c.total, c.burnin, c.n_adapt, c.max_depth, c.mode, c.mode == MAGI_MODE_HMC ? c.hmc_L : 0, c.anneal, c.stale, h->pb.dimp};
     const double dbl[4] = {c.step_size, c.target_accept, c.max_energy_diff, c.min_temp};
     mix(ints, sizeof(ints)); mix(dbl, sizeof(dbl)); mix(&c.seed, sizeof(c.seed)); mix(&chain_id, sizeof(chain_id));
-    // (the parameters' supports, when any is set: without one the tag is what it was before supports existed)
-    if (h->pb.tsup) { mix(h->th_kind, sizeof(int) * h->pb.P); mix(h->th_bound, sizeof(double) * h->pb.P); }
-    // (likewise the priors, when any is set)
-    if (h->pb.prior) { const int n = h->pb.D + h->pb.P; mix(h->pr_kind, sizeof(int) * n); mix(h->pr_a, sizeof(double) * n); mix(h->pr_b, sizeof(double) * n); }
-    // (and the observation model, when one is set)
-    if (h->pb.obs_links || h->pb.obsw) {
-        mix(h->ob_link, sizeof(int) * h->pb.D);
-        if (!h->obs_w.empty()) mix(h->obs_w.data(), sizeof(double) * h->obs_w.size());
-    }
+    magi_model_mix(h->model, h->pb, mix);      // (supports, priors, observation model: each while it is set)
     return (double)(x & ((1ull << 52) - 1));
 }
 
@@ -1238,9 +1199,10 @@ int magi_sampler_set_checkpoint(magi_handle* h, const double* scalars) {
 // the three device buffers, sized for the chains the handle has room for (freed with them: free_chains)
 static int metric_buffers(magi_handle* h) {
     const size_t n = (size_t)h->cap_chains, dimp = (size_t)h->pb.dimp;
-    if (!h->d_scale) MAGI_HIP_CHECK(h, hipMalloc(&h->d_scale, sizeof(double) * n * dimp));
-    if (!h->d_macc) MAGI_HIP_CHECK(h, hipMalloc(&h->d_macc, sizeof(double) * n * 3 * dimp));
-    if (!h->d_mwork) MAGI_HIP_CHECK(h, hipMalloc(&h->d_mwork, sizeof(double) * n * (dimp + 4)));
+    // (cap_chains and dimp cannot change while the chains live: a buffer that exists has its size)
+    auto once = [h](double*& p, size_t need) { size_t cap = p ? need : 0; return magi_grow(h, p, cap, need, "metric buffers"); };
+    int rc;
+    if ((rc = once(h->d_scale, n * dimp)) || (rc = once(h->d_macc, n * 3 * dimp)) || (rc = once(h->d_mwork, n * (dimp + 4)))) return rc;
     return MAGI_OK;
 }
 
@@ -1265,7 +1227,7 @@ int magi_sampler_set_metric(magi_handle* h, const double* inv_mass_X, const doub
     const int given = (inv_mass_X ? 1 : 0) + (inv_mass_sig ? 1 : 0) + (inv_mass_th ? 1 : 0);
     if (given != 0 && given != 3) return magi_fail(h, MAGI_E_BADARG, "magi_sampler_set_metric: give all three arrays, or none for the identity metric");
     if (given == 0) {
-        if (h->ch.scale) { h->ch.scale = nullptr; drop_graph(h); }
+        if (h->ch.scale) { h->ch.scale = nullptr; magi_stale(h, STALE_GRAPH); }
         return MAGI_OK;
     }
     int rc;
@@ -1288,7 +1250,7 @@ int magi_sampler_set_metric(magi_handle* h, const double* inv_mass_X, const doub
     }
     if ((rc = metric_buffers(h))) return rc;
     MAGI_HIP_CHECK(h, metric_copy(h, h->d_scale, s.data(), sizeof(double) * s.size(), hipMemcpyHostToDevice));
-    if (!h->ch.scale) { h->ch.scale = h->d_scale; drop_graph(h); }
+    if (!h->ch.scale) { h->ch.scale = h->d_scale; magi_stale(h, STALE_GRAPH); }
     return MAGI_OK;
 }
 
@@ -1311,7 +1273,7 @@ int magi_sampler_metric_window(magi_handle* h, int on) {
     if (!h->sampler_ready) return magi_fail(h, MAGI_E_STATE, "sampler not initialised");
     (void)hipSetDevice(h->device);
     if (!on) {
-        if (h->ch.macc) { h->ch.macc = nullptr; drop_graph(h); }
+        if (h->ch.macc) { h->ch.macc = nullptr; magi_stale(h, STALE_GRAPH); }
         h->window_k0.clear();
         return MAGI_OK;
     }
@@ -1327,7 +1289,7 @@ int magi_sampler_metric_window(magi_handle* h, int on) {
     MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));
     h->window_k0.resize(h->n_chains);
     for (int c = 0; c < h->n_chains; ++c) h->window_k0[c] = ctl[c].k;
-    if (!h->ch.macc) { h->ch.macc = h->d_macc; drop_graph(h); }
+    if (!h->ch.macc) { h->ch.macc = h->d_macc; magi_stale(h, STALE_GRAPH); }
     return MAGI_OK;
 }
 
@@ -1381,7 +1343,7 @@ int magi_sampler_adapt_metric(magi_handle* h, int n, double kappa, double rel_fl
     h->ch.scale = h->d_scale;
     h->ch.macc = nullptr;              // the window is closed
     h->window_k0.clear();
-    drop_graph(h);
+    magi_stale(h, STALE_GRAPH);
     return kept;
 }
 
@@ -1502,7 +1464,7 @@ int magi_time_gradient(magi_handle* h, int n_chains, int reps, double* total_ms_
     MAGI_HIP_CHECK(h, hipMemsetAsync(h->ch.gctl, 0, sizeof(GlobalCtl), h->stream));
     if ((rc = magi_launch_prepare(h, n_chains, h->stream))) return rc;
     if ((rc = magi_launch_plan_eval(h, n_chains, h->stream))) return rc;
-    h->sampler_ready = false;          // the chain state is clobbered by the timing launches
+    magi_stale(h, STALE_SAMPLER);          // the chain state is clobbered by the timing launches
     float ms = 0.f;
     // warm
     for (int i = 0; i < 3; ++i) {

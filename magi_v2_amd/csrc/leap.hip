@@ -906,7 +906,7 @@ extern "C" int magi_debug_wg_trace(magi_handle* h, int n_chains, int warm, int w
     MAGI_HIP_CHECK(h, hipMemsetAsync(h->ch.gctl, 0, sizeof(GlobalCtl), h->stream));
     if ((rc = magi_launch_prepare(h, n_chains, h->stream))) return rc;
     if ((rc = magi_launch_plan_eval(h, n_chains, h->stream))) return rc;
-    h->sampler_ready = false;
+    magi_stale(h, STALE_SAMPLER);
     void* sym = nullptr;
     MAGI_HIP_CHECK(h, hipGetSymbolAddress(&sym, HIP_SYMBOL(g_wg_trace)));
     for (int i = 0; i <= warm; ++i) {

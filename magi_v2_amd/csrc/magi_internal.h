@@ -1071,6 +1071,52 @@ struct BuildProfile {
     hipEvent_t e0 = nullptr, e1 = nullptr;      // created on the handle's device by the first profiled build
 };
 
+// The model a problem carries: supports of theta (magi_set_theta_support), priors of the D + P parameter entries (magi_set_prior), observation
+// model (magi_set_obs_model) -- the host copies the getters and the checkpoint tag read, and the device tables pb.tsup / pb.prior / pb.obsw
+// point at while the model is not the default.  A feature that adds model state adds it HERE: a member, its default in magi_model_default,
+// its bytes in magi_model_mix; its setter ends in model_upload (capi.hip), which raises the sampler level of magi_stale.
+struct MagiModel {
+    int th_kind[MAGI_MAX_P] = {};
+    double th_bound[MAGI_MAX_P] = {};
+    int pr_kind[MAGI_MAX_D + MAGI_MAX_P] = {};
+    double pr_a[MAGI_MAX_D + MAGI_MAX_P] = {}, pr_b[MAGI_MAX_D + MAGI_MAX_P] = {};
+    double lb_orig[MAGI_MAX_D] = {};  // LB as magi_set_problem gave it (pb.LB holds the constant of a fixed sigma^2 instead)
+    // the data as magi_set_problem gave them -- entry d N + i and UNtransformed value of observation k, so that the observation model can be
+    // changed or reset without a new magi_set_problem --, the links and the weights (empty: none given)
+    std::vector<int64_t> obs_e;
+    std::vector<double> obs_y, obs_w;
+    int ob_link[MAGI_MAX_D] = {};
+    // allocated once and freed with the handle (a group's device table may hold their addresses): [MAGI_MAX_P], [MAGI_MAX_D + MAGI_MAX_P]
+    double2* dTsup = nullptr;
+    double4* dPrior = nullptr;
+    double* dObsw = nullptr;          // [D][N] like dYobs: allocated on first use, freed with the problem (magi_model_default)
+};
+
+// THE default: every theta positive, every prior flat (LB as given), identity links, no weights -- the kernels' default paths.  The data
+// (obs_e, obs_y, lb_orig) are the problem's, not the model's, and stay.  m == nullptr: the DevProblem half alone (a group's copy of a shape).
+inline void magi_model_default(DevProblem& pb, MagiModel* m) {
+    pb.tsup = nullptr; pb.prior = nullptr; pb.fixed_mask = 0; pb.obs_links = 0; pb.obsw = nullptr;
+    if (!m) return;
+    for (int p = 0; p < MAGI_MAX_P; ++p) { m->th_kind[p] = MAGI_THETA_POSITIVE; m->th_bound[p] = 0.0; }
+    for (int j = 0; j < MAGI_MAX_D + MAGI_MAX_P; ++j) { m->pr_kind[j] = MAGI_PRIOR_FLAT; m->pr_a[j] = m->pr_b[j] = 0.0; }
+    for (int d = 0; d < MAGI_MAX_D; ++d) { m->ob_link[d] = MAGI_LINK_IDENTITY; pb.LB[d] = m->lb_orig[d]; }
+    m->obs_w.clear();
+    if (m->dObsw) (void)hipFree(m->dObsw);
+    m->dObsw = nullptr;
+}
+
+// What of the model a checkpoint's tag covers (capi.hip: ckpt_tag), through mix(pointer, bytes): each part only while it is set, so that a
+// tag without a model is what it was before models existed.  Bytes and order are part of the checkpoint format.
+template <typename Mix>
+void magi_model_mix(const MagiModel& m, const DevProblem& pb, Mix&& mix) {
+    if (pb.tsup) { mix(m.th_kind, sizeof(int) * pb.P); mix(m.th_bound, sizeof(double) * pb.P); }
+    if (pb.prior) { const int n = pb.D + pb.P; mix(m.pr_kind, sizeof(int) * n); mix(m.pr_a, sizeof(double) * n); mix(m.pr_b, sizeof(double) * n); }
+    if (pb.obs_links || pb.obsw) {
+        mix(m.ob_link, sizeof(int) * pb.D);
+        if (!m.obs_w.empty()) mix(m.obs_w.data(), sizeof(double) * m.obs_w.size());
+    }
+}
+
 struct magi_handle {
     int device = 0;
     MagiOptions opt;
@@ -1085,24 +1131,7 @@ struct magi_handle {
     double* dTimes = nullptr;        // pb.tgrid: the times of the grid points (magi_set_times), [times_cap >= pb.Np]
     int times_N = 0;                 // the N they were set for (0: not set; forgotten when the matrices change to another N)
     size_t times_cap = 0;
-    // supports of the parameters (magi_set_theta_support): the host copy, and the device table pb.tsup points at while any parameter is
-    // not positive (allocated once, MAGI_MAX_P entries, freed with the handle: a group's device table may hold the pointer)
-    int th_kind[MAGI_MAX_P] = {};
-    double th_bound[MAGI_MAX_P] = {};
-    double2* dTsup = nullptr;
-    // priors of the D + P parameter entries (magi_set_prior): the host copy, and the device table pb.prior points at while any is not flat
-    // (allocated once, MAGI_MAX_D + MAGI_MAX_P entries, freed with the handle, as dTsup)
-    int pr_kind[MAGI_MAX_D + MAGI_MAX_P] = {};
-    double pr_a[MAGI_MAX_D + MAGI_MAX_P] = {}, pr_b[MAGI_MAX_D + MAGI_MAX_P] = {};
-    double4* dPrior = nullptr;
-    double lb_orig[MAGI_MAX_D] = {};  // LB as magi_set_problem gave it (pb.LB holds the constant of a fixed sigma^2 instead)
-    // observation model (magi_set_obs_model): the data as magi_set_problem gave them -- entry d N + i and UNtransformed value of observation k,
-    // so that the model can be changed or reset without a new magi_set_problem -- the links, the weights (empty: none given) and the device
-    // copy of the weights pb.obsw points at while any was given ([D][N] like dYobs; allocated on first use, freed with dYobs)
-    std::vector<int64_t> obs_e;
-    std::vector<double> obs_y, obs_w;
-    int ob_link[MAGI_MAX_D] = {};
-    double* dObsw = nullptr;
+    MagiModel model;                 // supports, priors, observation model (above)
     size_t mat_elems = 0;
     // dense C^-1, m, K^-1 ([D][N][N], unmasked) as built or uploaded: authoritative until the caller uploads others; packed
     // (band mask, symmetrised / transposed copies, single-phase operator blocks) by magi_pack_matrices
@@ -1143,7 +1172,8 @@ struct magi_handle {
     double* d_macc = nullptr;        // [cap_chains][3][dimp]
     double* d_mwork = nullptr;       // [cap_chains][dimp + 4] k_metric_adapt: variances | median, min s, status
     std::vector<int> window_k0;      // transition index of every chain when the open window was opened (empty: no window)
-    size_t samples_cap = 0, diag_cap = 0, vop_elems = 0;
+    size_t samples_cap = 0, diag_cap = 0;
+    size_t tpart_elems = 0, vop_elems = 0;      // doubles of ch.tpart / ch.vop as allocated (magi_ensure_chains: allocation and later memsets)
     // magi_sampler_profile: when set, the launchers of k_stream / k_point attach these events to the launch (hipExtLaunchKernel:
     // they take the kernel's own begin / end time stamps, what rocprofv3's kernel trace reports)
     hipEvent_t prof_e0 = nullptr, prof_e1 = nullptr;
@@ -1166,12 +1196,36 @@ struct magi_handle {
     int group_per = 0;                   // chains per member (n_chains / group_n)
 };
 
-// work-space slot `k` with room for n doubles (grow-only; freed by magi_destroy); nullptr + error on failure
-double* magi_workspace(magi_handle* h, int k, size_t n);
-
 // error helpers -------------------------------------------------------------------------------
 extern thread_local std::string g_magi_last_error;
 int magi_fail(magi_handle* h, int code, const std::string& msg);
+
+// What a call makes stale, in levels that each include the ones before: the captured graph; + the sampler (magi_sampler_init comes next);
+// + the chain buffers, with the metric's; + the problem and its model (magi_set_problem comes next); + the packed matrices.
+// capi.hip: magi_stale, under the table of who raises which -- the one place that clears these flags and destroys the graph.
+enum MagiStale { STALE_GRAPH, STALE_SAMPLER, STALE_CHAINS, STALE_PROBLEM, STALE_MATRICES };
+void magi_stale(magi_handle* h, MagiStale level);
+
+// THE rule of a grow-only device buffer p with room for cap elements: enough room -> nothing happens; else the old block is freed and p,
+// cap are cleared BEFORE the allocation, and cap is set only after it succeeded -- a failure leaves {nullptr, 0}, never a freed address or
+// a capacity without memory.  Pointers that alias p (in a DevProblem, in DevChains) are the caller's to clear first.
+template <typename T>
+int magi_grow(magi_handle* h, T*& p, size_t& cap, size_t need, const char* what) {
+    if (need <= cap) return MAGI_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr; cap = 0;
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&p), need * sizeof(T));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        p = nullptr;
+        return magi_fail(h, MAGI_E_HIP, std::string(what) + " allocation failed (" + std::to_string(need * sizeof(T) >> 20) + " MiB): " + hipGetErrorString(e));
+    }
+    cap = need;
+    return MAGI_OK;
+}
+
+// work-space slot `k` with room for n doubles (magi_grow; freed by magi_destroy); nullptr + error on failure
+double* magi_workspace(magi_handle* h, int k, size_t n);
 
 #define MAGI_HIP_CHECK(h, expr)                                                                   \
     do {                                                                                          \

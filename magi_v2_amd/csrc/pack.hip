@@ -134,17 +134,19 @@ int magi_pack_matrices(magi_handle* h, int N, int D, int bandsize, const double*
     const int W = banded ? 2 * bandsize + 1 : N;
     const int ld = (W + 1) & ~1;
     const size_t elems = (size_t)D * N * ld;
-    const bool shape_changed = !h->have_matrices || pb.N != N || pb.D != D;
-    if (!h->have_matrices || elems != h->mat_elems) {
-        if (h->dCsym) (void)hipFree(h->dCsym);
-        if (h->dM) (void)hipFree(h->dM);
-        if (h->dMt) (void)hipFree(h->dMt);
-        if (h->dKsym) (void)hipFree(h->dKsym);
-        h->dCsym = h->dM = h->dMt = h->dKsym = nullptr;
-        MAGI_HIP_CHECK(h, hipMalloc(&h->dCsym, elems * sizeof(double)));
-        MAGI_HIP_CHECK(h, hipMalloc(&h->dM, elems * sizeof(double)));
-        MAGI_HIP_CHECK(h, hipMalloc(&h->dMt, elems * sizeof(double)));
-        MAGI_HIP_CHECK(h, hipMalloc(&h->dKsym, elems * sizeof(double)));
+    // Nothing evaluates on this handle until the pack has succeeded: have_matrices is down from here to the end of the function, and the
+    // sampler and its graph (which holds the operand pointers by value) are stale either way.  Another shape forgets the problem as well --
+    // yobs and dim depend on N, D --; at an unchanged shape the problem and its model stay in force on the new operands (magi_hip.h).
+    const bool had = h->have_matrices, shape_changed = !had || pb.N != N || pb.D != D;
+    magi_stale(h, shape_changed ? STALE_MATRICES : STALE_SAMPLER);
+    h->have_matrices = false;
+    pb.Csym = pb.M = pb.Mt = pb.Ksym = nullptr;
+    pb.tiles = nullptr; pb.tasks = pb.stasks = nullptr;
+    if (!had || elems != h->mat_elems) {     // (sized exactly, the four together: all null and mat_elems 0 before the first allocation)
+        double** const stacks[4] = {&h->dCsym, &h->dM, &h->dMt, &h->dKsym};
+        for (double** s : stacks) { if (*s) (void)hipFree(*s); *s = nullptr; }
+        h->mat_elems = 0;
+        for (double** s : stacks) MAGI_HIP_CHECK(h, hipMalloc(s, elems * sizeof(double)));
         h->mat_elems = elems;
     }
     const int mask = bandsize >= 0 ? bandsize : -1;
@@ -238,29 +240,17 @@ int magi_pack_matrices(magi_handle* h, int N, int D, int bandsize, const double*
         const size_t n_task_ints = tasks.size();
         tasks.insert(tasks.end(), stasks.begin(), stasks.end());
         const size_t telems = (size_t)n_tasks * MAGI_TB * MAGI_TB;
-        if (telems > h->tiles_cap) {
-            if (h->dTiles) (void)hipFree(h->dTiles);
-            h->dTiles = nullptr; h->tiles_cap = 0;
-            MAGI_HIP_CHECK(h, hipMalloc(&h->dTiles, telems * sizeof(double)));
-            h->tiles_cap = telems;
-        }
-        if (tasks.size() > h->tasks_cap) {
-            if (h->dTasks) (void)hipFree(h->dTasks);
-            h->dTasks = nullptr; h->tasks_cap = 0;
-            MAGI_HIP_CHECK(h, hipMalloc(&h->dTasks, tasks.size() * sizeof(int)));
-            h->tasks_cap = tasks.size();
-        }
+        int rc;
+        if ((rc = magi_grow(h, h->dTiles, h->tiles_cap, telems, "operator blocks")) || (rc = magi_grow(h, h->dTasks, h->tasks_cap, tasks.size(), "task table"))) return rc;
         MAGI_HIP_CHECK(h, hipMemcpyAsync(h->dTasks, tasks.data(), tasks.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
         const size_t nn = (size_t)D * N * N;
         double *tCs = magi_workspace(h, magi_handle::WS_TCS, nn), *tM = magi_workspace(h, magi_handle::WS_TM, nn),
                *tKs = magi_workspace(h, magi_handle::WS_TKS, nn), *tE = magi_workspace(h, magi_handle::WS_TE, nn);
         if (!tCs || !tM || !tKs || !tE) return MAGI_E_HIP;
-        dim3 gd((N + 255) / 256, N, D);
-        (void)gd;
         hipLaunchKernelGGL(k_pack_dense<PACK_SYM>, dgrid(N), dblock, 0, h->stream, dC_inv, tCs, N, N, mask);
         hipLaunchKernelGGL(k_pack_dense<PACK_COPY>, dgrid(N), dblock, 0, h->stream, dM, tM, N, N, mask);
         hipLaunchKernelGGL(k_pack_dense<PACK_SYM>, dgrid(N), dblock, 0, h->stream, dK_inv, tKs, N, N, mask);
-        int rc = magi_fused_operators(h, N, D, tCs, tM, tKs, tE);
+        rc = magi_fused_operators(h, N, D, tCs, tM, tKs, tE);
         if (rc == MAGI_OK) {
             hipLaunchKernelGGL(k_pack_tiles, dim3(n_tasks), dim3(256), 0, h->stream, tCs, tKs, tE, h->dTasks, h->dTiles, N, fb);
             e = hipGetLastError();
@@ -290,11 +280,5 @@ int magi_pack_matrices(magi_handle* h, int N, int D, int bandsize, const double*
     pb.Mt = h->dMt;
     pb.Ksym = h->dKsym;
     h->have_matrices = true;
-    if (shape_changed) h->have_problem = false;   // yobs / dim depend on N, D
-    // kernel arguments are captured by value in the leapfrog graph
-    if (h->graph_exec) { (void)hipGraphExecDestroy(h->graph_exec); h->graph_exec = nullptr; }
-    if (h->graph) { (void)hipGraphDestroy(h->graph); h->graph = nullptr; }
-    h->graph_valid = false;
-    h->sampler_ready = false;
     return MAGI_OK;
 }

@@ -73,6 +73,45 @@ def test_the_states_of_a_batch_are_pairwise_apart():
     assert worst >= MARGIN, worst
 
 
+def test_a_stale_output_row_would_be_seen_under_a_capacity_larger_than_the_need():
+    """The grow-only history of tests/test_reuse_gpu.py: a NUTS run of 3 chains x (8 + 6) transitions to its end, then REUSE_NUTS on 2 chains
+    paused after 3 of its 4 + 3 -- the output buffers keep the first run's capacity, and the second run's rows lie over the first's.  The
+    diagnostics are [chain][total]: entry f of the second run (chain f // 7, transition f % 7) lies where the first run left chain 0's
+    transition f.  On the oracle: wherever the second run has a value of its own there, the first run's differs by >= MARGIN in step size,
+    energy and target (the log acceptance ratio is 0 and -inf in the first two transitions of this configuration and has no scale);
+    everywhere else the second run expects the NaN fill over a finite number, and its sample rows (no transition behind burn-in taken) the
+    fill over the first run's draws.  The one exception is by construction: chain 0's transitions 0 .. 2 are the same chain from the same
+    state under the same seed in both runs, while both still adapt -- equal, asserted as such: a stale entry there IS the right entry.
+    Smallest margin found: 0.124."""
+    from tests import metric_reference as M
+    from tests.util import REUSE_GROW, REUSE_NUTS, REUSE_SEED
+    st = reuse_state("C41")
+    X, sp, tp = st.states(3)
+    floats = ("step_size", "energy", "target_log_prob")
+
+    def run(cfg, chain):
+        kw = {k: v for k, v in cfg.items() if k not in ("num_results", "num_burnin_steps", "stale_cache")}
+        out = M.sample_chain(st.pr, None, None, None, cfg["num_results"], cfg["num_burnin_steps"], seed=REUSE_SEED, chain=20 + chain,
+                             initial=(X[chain], sp[chain], tp[chain]), stale_cache=bool(cfg["stale_cache"]), **kw)
+        return out[0], out[4]["all"]
+
+    draws, first = run(REUSE_GROW, 0)                           # (what lies under the second run's 2 x 7 entries is chain 0's alone)
+    assert np.isfinite(draws).all() and all(np.isfinite(first[k]).all() and len(first[k]) == 14 for k in floats)
+    total, taken = REUSE_NUTS["num_burnin_steps"] + REUSE_NUTS["num_results"], 3
+    assert taken < REUSE_NUTS["num_burnin_steps"]                # no draw of the second run is stored: its sample rows are all fill
+    worst = np.inf
+    for c in range(2):
+        second = run(REUSE_NUTS, c)[1]
+        for k in range(taken):
+            gaps = [abs(first[f][c * total + k] - second[f][k]) / abs(second[f][k]) for f in floats]
+            if c == 0:
+                assert max(gaps) == 0.0, (k, gaps)
+            else:
+                worst = min(worst, min(gaps))
+    print(f"smallest margin of a stale diagnostics entry: {worst:.3g}")
+    assert worst >= MARGIN, worst
+
+
 @pytest.mark.parametrize("name,band", REUSE_BYTES)
 def test_block_counts_of_the_band_tables_against_the_masked_index_sets(name, band):
     pr = reuse_state(name).pr

@@ -234,11 +234,11 @@ def test_chain_count_and_kernel_family_change_on_one_problem():
 
 # ---- 5: a sampler after a sampler -------------------------------------------------------------------------------------------------
 
-def _fresh_run(st, n, cfg_kw, seed=REUSE_SEED):
+def _fresh_run(st, n, cfg_kw, seed=REUSE_SEED, steps=None):
     eng = _engine(st)
     try:
         _load(eng, st)
-        return _run(eng, st, n, cfg_kw, seed)
+        return _run(eng, st, n, cfg_kw, seed, steps)
     finally:
         eng.close()
 
@@ -264,6 +264,45 @@ def test_sampler_after_sampler_and_checkpoint_resumed_in_the_same_handle():
         eng.sampler_resume(eng.default_cfg(**REUSE_NUTS), ck, seed=REUSE_SEED, chain_ids=[20, 21, 22])
         eng.sampler_run(4)
         _assert_same(_collect(eng), whole, "checkpoint resumed in the same handle", sl=(slice(None), slice(3, None)))
+    finally:
+        eng.close()
+
+
+def test_grow_only_buffers_under_a_capacity_larger_than_the_need():
+    """The buffers that grow and never shrink (csrc/magi_internal.h: magi_grow) and that no other history compares, at N = 41: the sample
+    buffer and the eight diagnostics arrays sized by a NUTS run of 3 chains x (8 + 6) transitions, then REUSE_NUTS on 2 chains paused after
+    3 of its 7 -- every transition not taken reads as the NaN / -1 fill over the first run's rows, as on a fresh handle paused at the same
+    place (tests/test_reuse_cpu.py: the rows differ wherever they could be stale); dense_apply with 1, 8 and 1 vectors, the work-space
+    slot and the pinned staging growing and then re-used under a larger capacity, each call against a fresh handle's; the first run again."""
+    from tests.util import REUSE_GROW
+    st = reuse_state("C41")
+    total, taken = REUSE_NUTS["num_burnin_steps"] + REUSE_NUTS["num_results"], 3
+    rng = np.random.default_rng(11)
+    eng = _engine(st)
+    try:
+        _load(eng, st)
+        whole = _run(eng, st, 3, REUSE_GROW)
+        assert whole["diag.step_size"].shape == (3, 14) and np.isfinite(whole["X"]).all() and np.isfinite(whole["diag.energy"]).all()
+        paused = _run(eng, st, 2, REUSE_NUTS, steps=taken)
+        assert list(eng.sampler_steps_done()) == [taken] * 2
+        _assert_same(paused, _fresh_run(st, 2, REUSE_NUTS, steps=taken), "a paused run under a larger capacity")
+        assert paused["diag.energy"].shape == (2, total) and np.isfinite(paused["diag.energy"][:, :taken]).all()
+        assert np.isnan(paused["diag.energy"][:, taken:]).all() and np.isnan(paused["diag.step_size"][:, taken:]).all()
+        assert (paused["diag.leapfrogs_taken"][:, taken:] == -1).all() and (paused["diag.tree_depth"][:, taken:] == -1).all()
+        assert all(np.isnan(paused[k]).all() for k in ("X", "sig_pre", "th_pre"))         # (three burn-in transitions: no draw stored)
+        for nv in (1, 8, 1):
+            V = rng.standard_normal((eng.D, eng.N, nv))
+            fresh = _engine(st)
+            try:
+                fresh.set_matrices(*st.matrices, bandsize=None)
+                for which in ("C_inv", "m", "K_inv"):
+                    for tr in (False, True):
+                        a, b = eng.dense_apply(which, V, transpose=tr), fresh.dense_apply(which, V, transpose=tr)
+                        assert a.shape == (eng.D, eng.N, nv) and np.array_equal(_bits(a), _bits(b)), (nv, which, tr)
+            finally:
+                fresh.close()
+        _assert_same(_run(eng, st, 3, REUSE_GROW), whole, "the first run again")
+        _assert_same(whole, _fresh_run(st, 3, REUSE_GROW), "the first run against a fresh handle's")
     finally:
         eng.close()
 

@@ -590,6 +590,7 @@ REUSE_BYTES = (("A", None), ("A", 20), ("A", 43), ("A", 0), ("C161", 20))   # tr
 REUSE_TIME_SHIFT = 0.37
 REUSE_NUTS = dict(num_burnin_steps=4, num_results=3, step_size=2e-3, max_tree_depth=6, stale_cache=0)
 REUSE_HMC = dict(num_burnin_steps=3, num_results=2, step_size=2e-3, mode=1, hmc_leapfrogs=8, stale_cache=0)
+REUSE_GROW = dict(REUSE_NUTS, num_burnin_steps=8, num_results=6)      # the run that sizes the grow-only output buffers: 3 chains, to its end
 REUSE_SEED = 808
 
 
