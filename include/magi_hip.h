@@ -612,6 +612,62 @@ int magi_sampler_gp_predict(magi_handle* h, int chain0, int n_sel, const double*
  * transposes and downloads of x_new / dx_new are not among them).  ms: 5 entries. */
 int magi_gp_profile(magi_handle* h, double* ms);
 
+/* ---- posterior predictive checks ---------------------------------------------------------------- */
+
+/* Could the model have produced the data (unit csrc/ppc.hip): replicated observations y_rep, their per-column
+ * statistics, the PIT of every observation and the posterior predictive p-values of four realised discrepancies.
+ * Draw s = c R + r (chain c, result r) of S = C R pooled draws; column k belongs to component d = comp[k]; g_d is the component's link
+ * (MAGI_LINK_*), w_k > 0 the column's weight (1 without one), sigma^2_d(s) the draw's variance on the link's scale, y_k the observation
+ * (NaN: none -- the column is a pure prediction).
+ * Noise.  One Philox4x32-10 block per (s, k): (x, y, z, w) = philox4x32_10(k, r, chain_id[c], STREAM_PPC = 5, seed), a stream of its own
+ * beside the sampler's five; u1 = u01_53(x, y), u2 = u01_53(z, w), rad = sqrt(-2 log u1), ang = 2 pi u2, z0 = rad cos(ang), z1 = rad sin(ang).
+ * k is the column's index in the call; chain_id[c] is the chain's Philox id (magi_sampler_init's chain_ids) on the sampler route and the
+ * caller's chain_ids[c] (c when NULL) on the host route: a result does not depend on how chains are selected or sharded.
+ * Replicate.
+ *   x_lat  = x[s][k] + sqrt(extra_var[k]) z1           (x[s][k] itself when extra_var is NULL)
+ *   gy_rep = g_d(x_lat) + sqrt(sigma^2_d(s) / w_k) z0
+ *   y_rep  = g_d^-1(gy_rep) on the data's scale: gy_rep (identity), exp(gy_rep) (log), max(gy_rep, 0)^2 (sqrt: a negative root has no
+ *            datum; the map stays monotone, so quantiles commute with it).
+ * The link is evaluated as the observation model evaluates it; where g_d(x_lat) is not finite (x_lat <= 0 under log, < 0 under sqrt)
+ * y_rep[s][k] is NaN.
+ * Per column.  mean, sd, quant [n_q][K] of y_rep over the S draws: bit for bit what magi_summarize gives for the same matrix.
+ *   pit[k] = 1/S sum_s 1/2 erfc(-u_obs[s][k] / sqrt 2),   u_obs[s][k] = (g_d(y_k) - g_d(x_lat)) sqrt(w_k / sigma^2_d(s)):
+ * the PIT with the observation noise integrated analytically; NaN where y_k is NaN and where any term is not finite.
+ * Per draw and component: realised discrepancies of u_1 .. u_n, the values over the columns of component d with a y that is not NaN, in
+ * ascending column order, once for u = u_obs[s][.] (T_obs) and once for u = z0[s][.] (T_rep: the replicate's standardised residual IS
+ * z0, used directly and not recovered through g^-1):
+ *   T[0] = sum u^2 (chi2)   T[1] = sum u / n (mean)   T[2] = max |u| (maxabs)   T[3] = sum_{j<n} u_j u_{j+1} / sum u_j^2 (acf1; NaN for n < 2)
+ *   pval[d][t] = #{s: T_rep >= T_obs} / #{s: both finite};  n_T_excluded[d] = #{s: a T of (s, d) is not finite though defined} -- T[3] of
+ *   a component with n < 2 is undefined for every draw and excludes none.  A component without such a column has NaN p-values and NaN T.
+ * Every floating-point sum runs in one fixed order (columns ascending for T, one workgroup's fixed reduction for pit) and there are no
+ * floating-point atomics: the results are bit-identical from run to run and do not depend on the chunking (summary_chunk_cols).
+ * x: host [C R][K]; comp [K]; sigma_sq [C R][D]; link [D] or NULL (identity); weight, y, extra_var [K] or NULL; chain_ids [C] or NULL.
+ * y_rep [C R][K]; mean, sd, pit [K]; quant [n_q][K]; T_obs, T_rep [C R][D][4]; pval [D][4]; n_T_excluded [D]; *n_nonfinite counts the
+ * columns of y_rep with a non-finite draw (their mean, sd and quantiles are NaN).  Every output is optional.
+ * MAGI_E_BADARG (handle stays usable): C, R, C R as magi_summarize; K outside [1, 2^24]; D outside [1, MAGI_MAX_D (4; 8 in a library built
+ * for a wider traced drift)]; a comp outside [0, D); a link that is none of MAGI_LINK_*; a weight or sigma_sq not positive and finite; a
+ * negative or non-finite extra_var; a y outside its link's domain; n_q / probs as magi_summarize; a NULL x, comp or sigma_sq.  Needs a
+ * handle only for its device and stream, as magi_summarize.  Device memory of a call: three chunks [columns][C R] of together at most 64
+ * MiB (3 C R doubles where a single column of the three exceeds that: up to 96 MiB at C R = 2^22), the staging of the strided upload, 18 C R D doubles of discrepancy accumulators and statistics, and the results. */
+int magi_ppc(magi_handle* h, int C, int R, int K, int D, const double* x, const int* comp, const double* sigma_sq, const int* link,
+             const double* weight, const double* y, const double* extra_var, uint64_t seed, const int64_t* chain_ids,
+             int n_q, const double* probs,
+             double* y_rep, double* mean, double* sd, double* quant, double* pit,
+             double* T_obs, double* T_rep, double* pval, int* n_T_excluded, int* n_nonfinite);
+
+/* The same for the observations of the finished sampler run, from its device-resident samples of the chains [chain0, chain0 + n_sel) read
+ * in place: no draw crosses to the host.  One column per observed entry e = d N + i in ascending e -- obs_index, *n_obs_out and the call
+ * that returns only the count exactly as magi_sampler_elpd -- with x = X_s[e], sigma^2_d(s) = softplus(sig_pre_d) + LB[d] or the constant
+ * of a MAGI_PRIOR_FIXED entry, and the links and weights of the handle's -- on a group handle the member's own -- observation model; no
+ * extra_var.  Bit for bit what magi_ppc returns for the downloaded draws with these sigma^2, which sigma_sq_out, optional, host
+ * [n_sel num_results][D], returns as the kernel formed them (asked for alone, nothing else is computed).  y_rep: host [n_sel num_results][n_obs]; the other outputs as magi_ppc with K =
+ * n_obs.  MAGI_E_STATE / MAGI_E_BADARG as magi_sampler_summarize (sampler initialised, every selected chain finished, the chain range
+ * inside the sampler's chains and inside one member of a group), n_q / probs as magi_summarize.  Changes nothing of the handle's state. */
+int magi_sampler_ppc(magi_handle* h, int chain0, int n_sel, uint64_t seed, int n_q, const double* probs,
+                     double* y_rep, double* mean, double* sd, double* quant, double* pit,
+                     double* T_obs, double* T_rep, double* pval, int* n_T_excluded, int* n_nonfinite,
+                     int* obs_index, int* n_obs_out, double* sigma_sq_out);
+
 /* ---- multi-GPU ---------------------------------------------------------------------------------
  * There is deliberately NO magi_gather in this ABI (SURVEY 8b had listed one).  The path shards by independent (dataset, chain) units with
  * no exchange while sampling (one handle per GPU, one process per GPU); its only collective is ONE gather of the post-burn-in samples at

@@ -352,7 +352,7 @@ class MAGI_v2:
                 n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[int]] = None,
                 stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
                 family_chains: Optional[int] = None, summary: bool = False, keep_samples: bool = True, adapt_metric: bool = False,
-                theta_support=None, theta_prior=None, sigma_sq_prior=None, obs_link=None, obs_weight=None, elpd: bool = False):
+                theta_support=None, theta_prior=None, sigma_sq_prior=None, obs_link=None, obs_weight=None, elpd: bool = False, ppc: bool = False):
         """magi_v2.py:286-425.  Returns the reference's results dictionary; with n_chains > 1 every
         sample array gains a leading chain axis.  ``family_chains``: in a job sharded over GPUs, the largest per-GPU share
         (shard.family_chains_for) -- every rank then samples with the same kernel family whatever its own share.
@@ -385,9 +385,12 @@ class MAGI_v2:
         ``elpd=True`` adds ``results["elpd"]``: the pointwise log predictive density of the observations, WAIC and PSIS-LOO with the
         Pareto-khat diagnostic, computed on the GPU from the device-resident samples (``posterior_elpd``, on the scale of the data) -- what
         ``host.compare_elpd`` compares two models of the same data by.  Legal with ``keep_samples=False``.
+        ``ppc=True`` adds ``results["ppc"]``: the posterior predictive check of the fitted observations -- replicated data, PIT values and
+        discrepancy p-values, computed on the GPU from the device-resident samples (``posterior_predictive``, its noise seeded with this
+        call's ``seed``).  Legal with ``keep_samples=False``.
         Many datasets on one GPU: ``predict_many``."""
-        if not keep_samples and not (summary or elpd):
-            raise ValueError("keep_samples=False needs summary=True or elpd=True: the call would return nothing of the posterior")
+        if not keep_samples and not (summary or elpd or ppc):
+            raise ValueError("keep_samples=False needs summary=True, elpd=True or ppc=True: the call would return nothing of the posterior")
         sigma_sqs_LB, sig_pre0, th_pre0 = self._predict_prepare(sigma_sqs_LB, family_chains, theta_support, theta_prior, sigma_sq_prior, obs_link, obs_weight)
         eng = self.engine
         if seed is None:                 # the reference calls sample_chain unseeded (magi_v2.py:389-395)
@@ -406,6 +409,7 @@ class MAGI_v2:
         else:
             eng.sampler_run(num_results + num_burnin_steps)
         self._predicted = True
+        self._predict_seed = seed
         X_samps, sig_pre, th_pre = eng.sampler_samples() if keep_samples else (None, None, None)
         end = time.time()
         minutes = np.round((end - start) / 60, 2)
@@ -420,6 +424,8 @@ class MAGI_v2:
             results["summary"] = _warn_if_stuck(self.posterior_summary())
         if elpd:
             results["elpd"] = self.posterior_elpd()
+        if ppc:
+            results["ppc"] = self.posterior_predictive(seed=seed)
         return results
 
     def posterior_summary(self, probs=DEFAULT_PROBS, max_lag: int = 0):
@@ -463,6 +469,52 @@ class MAGI_v2:
         r = self.engine.sampler_gp_predict(self.I, self.phi1s, self.phi2s, t_new, nu=2.01, probs=probs, max_lag=max_lag, derivative=derivative,
                                            return_draws=return_draws)
         return self._posterior_at_result(r, derivative, return_draws)
+
+    def posterior_predictive(self, t_new=None, y_new=None, probs=DEFAULT_PROBS, seed: Optional[int] = None, return_draws: bool = False):
+        """Could the model have produced the data?  The posterior predictive check of the last ``predict``, all its chains pooled, computed
+        on the GPU (include/magi_hip.h: magi_ppc).  Without ``t_new`` the fitted observations are checked against replicates
+        drawn from the device-resident samples under the model's links, weights and fixed variances (MagiEngine.sampler_ppc): no draw
+        crosses to the host, legal after ``keep_samples=False``.  Returns the dictionary of ``host.ppc_result``: ``obs_index`` [(grid
+        point, component)], per observation ``mean``, ``sd``, ``quantiles`` [len(probs), n_obs] of the replicated data y_rep on the data's
+        scale (the predictive band of the OBSERVATIONS, noise included) and ``pit`` (uniform under a calibrated model), ``pvalues`` {chi2,
+        mean, maxabs, acf1: [D]}, the posterior predictive p-values of four discrepancies of the standardised residuals per component
+        (near 0 or 1: the data are not like the replicates in that respect), ``pit_ks`` [D], ``n_T_excluded``, ``n_nonfinite``;
+        ``return_draws`` adds ``y_rep`` [chains, draws, n_obs].
+        ``t_new`` [T] (times that need not be grid points) gives the predictive band of observations THERE, and with ``y_new`` [T, D] (NaN:
+        none) the PIT and p-values of held-out measurements: the draws are conditioned to ``t_new`` on the GPU (``posterior_at``'s
+        conditional means and their variance) and checked with that variance added to the latent state (MagiEngine.ppc with extra_var =
+        cond_var), links the model's, weight 1.  One column per (time, component), component-major; ``obs_index`` then holds (index into
+        t_new, component).  This route moves the conditioned draws x_new through the host.
+        ``seed``: the Philox seed of the replicates' noise, a stream of its own; None: the seed of the last ``predict``."""
+        if not getattr(self, "_predicted", False):
+            raise RuntimeError("posterior_predictive checks the samples of the last predict: run predict first")
+        eng = self.engine
+        seed = getattr(self, "_predict_seed", 0) if seed is None else seed
+        if t_new is None:
+            if y_new is not None:
+                raise ValueError("y_new are held-out measurements at the times t_new: give t_new")
+            return eng.sampler_ppc(seed=seed, probs=probs, return_draws=return_draws)
+        return self._ppc_at(eng, t_new, y_new, probs, seed, return_draws)
+
+    def _ppc_at(self, eng, t_new, y_new, probs, seed, return_draws):
+        """posterior_predictive at new times: the conditioned draws of all chains and their cond_var into MagiEngine.ppc."""
+        t_new = np.asarray(t_new, dtype=np.float64).reshape(-1)
+        T, D = t_new.shape[0], self.D
+        r = eng.sampler_gp_predict(self.I, self.phi1s, self.phi2s, t_new, nu=2.01, probs=(), derivative=False, return_draws=True)
+        xd = r["X_draws"]                                                   # [chains, draws, T, D]
+        x = np.ascontiguousarray(xd.transpose(0, 1, 3, 2)).reshape(xd.shape[0], xd.shape[1], D * T)
+        y = None
+        if y_new is not None:
+            y = np.asarray(y_new, dtype=np.float64)
+            if y.shape != (T, D):
+                raise ValueError(f"y_new: expected shape {(T, D)}, got {y.shape}")
+            y = np.ascontiguousarray(y.T).reshape(-1)
+        out = eng.ppc(x, np.repeat(np.arange(D), T), eng.sampler_sigma_sq(), link=getattr(self, "_obs_link", None), y=y,
+                      extra_var=np.ascontiguousarray(r["cond_var"].T).reshape(-1), seed=seed, chain_ids=eng._chain_ids, probs=probs,
+                      return_draws=return_draws)
+        out["obs_index"] = np.stack([np.tile(np.arange(T), D), np.repeat(np.arange(D), T)], axis=1)
+        out["t"] = t_new
+        return out
 
     def posterior_elpd(self, scale: str = "data", loglik: bool = False, loo: Optional[bool] = None):
         """Pointwise log predictive density, WAIC and PSIS-LOO of the last ``predict``, all its chains pooled, computed on the GPU from the
@@ -667,7 +719,7 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
                  n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[Sequence[int]]] = None,
                  stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
                  summary: bool = False, keep_samples: bool = True, theta_support=None, theta_prior=None, sigma_sq_prior=None,
-                 obs_link=None, obs_weight=None, elpd: bool = False, posterior_at=None):
+                 obs_link=None, obs_weight=None, elpd: bool = False, posterior_at=None, ppc: bool = False):
     """``predict`` for several models (after their ``initial_fit``) at once.  Models of one library, device and problem shape are sampled
     as one problem group on their GPU -- one captured graph, one kernel pair per leapfrog slot for all their chains -- and the others by
     their own ``predict``.  ``sigma_sqs_LB``: None (each model's default) or one entry per model; ``chain_ids``: None (0 .. n_chains - 1
@@ -681,9 +733,10 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
     specifications / of arrays or None); the members of one group may differ.  ``elpd`` as in ``predict``: one ``results["elpd"]`` per
     model, a grouped model's from its own chains and observation model.  ``posterior_at``: None, or times t_new [T]: adds
     ``results["posterior_at"]`` = that model's ``MAGI_v2.posterior_at(t_new)`` (a grouped model's through the group's handle and its
-    member index, from its own chains, matrices and mu); legal with ``keep_samples=False``."""
-    if not keep_samples and not (summary or elpd or posterior_at is not None):
-        raise ValueError("keep_samples=False needs summary=True, elpd=True or posterior_at: the call would return nothing of the posterior")
+    member index, from its own chains, matrices and mu); legal with ``keep_samples=False``.  ``ppc`` as in ``predict``: one
+    ``results["ppc"]`` per model, a grouped model's from its own chain range and observation model."""
+    if not keep_samples and not (summary or elpd or ppc or posterior_at is not None):
+        raise ValueError("keep_samples=False needs summary=True, elpd=True, ppc=True or posterior_at: the call would return nothing of the posterior")
     models = list(models)
     n = len(models)
     lbs = [None] * n if sigma_sqs_LB is None else list(sigma_sqs_LB)
@@ -722,9 +775,9 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
     for grp in partition_for_groups([group_key(m, n_chains) for m in models]):
         if len(grp) == 1:
             k = grp[0]
-            only_at = not (keep_samples or summary or elpd)          # (predict wants a reason of its own to drop the draws)
+            only_at = not (keep_samples or summary or elpd or ppc)          # (predict wants a reason of its own to drop the draws)
             out[k] = models[k].predict(num_results, num_burnin_steps, lbs[k], verbose, chain_ids=ids[k], summary=summary or only_at, keep_samples=keep_samples,
-                                        theta_support=sups[k], theta_prior=tpri[k], sigma_sq_prior=spri[k], obs_link=olnk[k], obs_weight=owts[k], elpd=elpd, **kw)
+                                        theta_support=sups[k], theta_prior=tpri[k], sigma_sq_prior=spri[k], obs_link=olnk[k], obs_weight=owts[k], elpd=elpd, ppc=ppc, **kw)
             if only_at:
                 del out[k]["summary"]
             if posterior_at is not None:
@@ -752,6 +805,7 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
             summaries = [g.sampler_summary(member=j) for j in range(len(grp))] if summary else None
             elpds = [g.sampler_elpd(member=j, loo=host.elpd_wants_loo(n_chains * num_results))
                      for j in range(len(grp))] if elpd else None
+            ppcs = [g.sampler_ppc(member=j, seed=seed) for j in range(len(grp))] if ppc else None
             ats = [g.sampler_gp_predict(models[k].I, models[k].phi1s, models[k].phi2s, posterior_at, member=j)
                    for j, k in enumerate(grp)] if posterior_at is not None else None
         finally:
@@ -765,6 +819,8 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
                 out[k]["summary"] = _warn_if_stuck(summaries[j])
             if elpd:
                 out[k]["elpd"] = models[k]._elpd_on_scale(elpds[j], "data")
+            if ppc:
+                out[k]["ppc"] = ppcs[j]
             if posterior_at is not None:
                 out[k]["posterior_at"] = MAGI_v2._posterior_at_result(ats[j], True, False)
     return out

@@ -227,6 +227,8 @@ void magi_options_from_env(MagiOptions& o) {
 //                                                                     when N or D change"
 //   magi_set_matrices, magi_build_dense                     MATRICES  "forget the problem, whatever the shape"; the packed operands describe the OLD
 //                                                                     dense stacks until a pack has succeeded
+//   magi_sampler_ppc, magi_ppc                              none      they read the samples, the problem and its model in place; the scratch is
+//                                                                     the call's own (MagiScratch) and the noise has a Philox stream of its own
 //
 // "SAMPLER includes GRAPH" drops a graph that some of these calls could have kept (the log-posterior and timing calls, the end of
 // magi_sampler_profile, the budget exit).  That cannot be observed: a graph is replayed by magi_sampler_run alone, which needs sampler_ready,

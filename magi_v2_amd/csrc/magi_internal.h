@@ -356,7 +356,8 @@ __host__ __device__ inline double u01_53(unsigned int hi, unsigned int lo) {
     return ((double)x + 0.5) * 1.1102230246251565e-16;   // 2^-53
 }
 
-enum { STREAM_MOMENTUM = 0, STREAM_DIRECTION = 1, STREAM_LEAF = 2, STREAM_MERGE = 3, STREAM_HMC = 4 };
+enum { STREAM_MOMENTUM = 0, STREAM_DIRECTION = 1, STREAM_LEAF = 2, STREAM_MERGE = 3, STREAM_HMC = 4,
+       STREAM_PPC = 5 /* ppc.hip: the noise of the replicated observations, one block per (draw, column) */ };
 
 __device__ inline double rng_uniform(unsigned int index, unsigned int step, unsigned int chain,
                                      unsigned int stream, unsigned long long key) {

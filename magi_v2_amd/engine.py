@@ -12,7 +12,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
-from .host import ELPD_POINTWISE, elpd_result, obs_model_spec, prior_spec, theta_support
+from .host import ELPD_POINTWISE, elpd_result, obs_model_spec, ppc_result, prior_spec, theta_support
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libmagi_hip.so")
@@ -103,6 +103,9 @@ _SYMBOLS = {
     "magi_gp_profile": (C.c_int, [C.c_void_p, _dp]),
     "magi_elpd": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp] + [_dp] * 6 + [_ip]),
     "magi_sampler_elpd": (C.c_int, [C.c_void_p, C.c_int, C.c_int] + [_dp] * 6 + [_ip, _ip, _dp, _ip]),
+    "magi_ppc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _dp, _ip, _dp, _ip, _dp, _dp, _dp, C.c_uint64, _lp, C.c_int, _dp]
+                 + [_dp] * 8 + [_ip, _ip]),
+    "magi_sampler_ppc": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, _dp] + [_dp] * 8 + [_ip, _ip, _ip, _ip, _dp]),
 }
 
 SUMMARY_STATS = ("mean", "sd", "quantiles", "rhat", "ess", "mcse_mean")       # the order of the six outputs in include/magi_hip.h
@@ -466,6 +469,92 @@ class MagiEngine:
         e = idx[:n].astype(np.int64)
         return elpd_result(outs, np.stack([e % self.N, e // self.N], axis=1), nf.value, loglik=ll)
 
+    @staticmethod
+    def _ppc_outputs(S, K, D, n_q, y_rep, discrepancies):
+        return {"y_rep": np.empty((S, K)) if y_rep else None, "mean": np.empty(K), "sd": np.empty(K), "quant": np.empty((n_q, K)), "pit": np.empty(K),
+                "T_obs": np.empty((S, D, 4)) if discrepancies else None, "T_rep": np.empty((S, D, 4)) if discrepancies else None,
+                "pval": np.empty((D, 4)), "excl": np.zeros(D, dtype=np.int32)}
+
+    @staticmethod
+    def _ppc_pointers(o):
+        return [_ptr(o[s]) for s in ("y_rep", "mean", "sd", "quant", "pit", "T_obs", "T_rep", "pval")] + [o["excl"].ctypes.data_as(_ip)]
+
+    def ppc(self, x, comp, sigma_sq, link=None, weight=None, y=None, extra_var=None, seed=0, chain_ids=None, probs=DEFAULT_PROBS,
+            return_draws=False, discrepancies=False):
+        """Posterior predictive check of ``x`` [C chains, R draws, K columns], the latent state at K observation points, on the device
+        (magi_ppc; the definitions are in include/magi_hip.h): column k belongs to component ``comp[k]`` of D = sigma_sq.shape[-1],
+        ``sigma_sq`` [C, R, D] is the draws' noise variance on the link's scale, ``link`` [D] codes or names (None: identity), ``weight``,
+        ``y`` (NaN: no datum, a pure prediction) and ``extra_var`` (a latent variance added per column, e.g. the GP's cond_var) are [K] or
+        None.  ``seed`` and ``chain_ids`` [C] (None: 0 .. C - 1) select the Philox noise.  Any draws serve: those of ``gp_predict``, or the
+        ODE solutions of ``posterior_trajectories`` at the observation times.  Returns the dictionary of ``host.ppc_result``;
+        ``return_draws`` adds ``y_rep`` [C, R, K], ``discrepancies`` adds ``T_obs`` and ``T_rep`` [C, R, D, 4]."""
+        x, sigma_sq = _f64(x), _f64(sigma_sq)
+        if x.ndim != 3 or sigma_sq.ndim != 3 or sigma_sq.shape[:2] != x.shape[:2]:
+            raise ValueError(f"expected x (chains, draws, columns) and sigma_sq (chains, draws, components), got {x.shape} and {sigma_sq.shape}")
+        n_c, n_r, K = x.shape
+        D = sigma_sq.shape[2]
+        comp = np.ascontiguousarray(np.asarray(comp).reshape(-1), dtype=np.int32)
+        if comp.shape[0] != K:
+            raise ValueError(f"comp: expected {K} entries, got {comp.shape[0]}")
+        lk = None if link is None else np.ascontiguousarray(obs_model_spec(link, D), dtype=np.int32)
+        opt = lambda a: None if a is None else _f64(np.asarray(a, dtype=np.float64).reshape(-1), (K,))
+        weight, y, extra_var = opt(weight), opt(y), opt(extra_var)
+        ids = None if chain_ids is None else np.ascontiguousarray(np.asarray(chain_ids).reshape(-1), dtype=np.int64)
+        if ids is not None and ids.shape[0] != n_c:
+            raise ValueError(f"chain_ids: expected {n_c} entries, got {ids.shape[0]}")
+        probs, n_q = self._probs(probs)
+        o = self._ppc_outputs(n_c * n_r, K, D, n_q, return_draws, discrepancies)
+        nf = C.c_int32(0)
+        self._check(self._lib.magi_ppc(self._h, n_c, n_r, K, D, _ptr(x), comp.ctypes.data_as(_ip), _ptr(sigma_sq),
+                                       None if lk is None else lk.ctypes.data_as(_ip), _ptr(weight), _ptr(y), _ptr(extra_var), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                       None if ids is None else ids.ctypes.data_as(_lp), n_q, _ptr(probs), *self._ppc_pointers(o), C.byref(nf)))
+        shape = lambda a, *s: None if a is None else a.reshape(n_c, n_r, *s)
+        return ppc_result(comp, D, o["mean"], o["sd"], o["quant"], o["pit"], o["pval"], o["excl"], nf.value, probs=probs,
+                          y_rep=shape(o["y_rep"], K), T_obs=shape(o["T_obs"], D, 4), T_rep=shape(o["T_rep"], D, 4))
+
+    def sampler_ppc(self, chains=None, member=None, seed=0, probs=DEFAULT_PROBS, return_draws=False, discrepancies=False, sigma_sq=False):
+        """Posterior predictive check of the fitted observations of the finished sampler run, computed on the device-resident samples
+        (magi_sampler_ppc): no draw is copied to the host.  One column per observation, in the order of ``obs_index`` [n_obs, 2] = (grid
+        point i, component d), ascending in d N + i, under the handle's (a group member's own) links, weights, LB and fixed variances.
+        ``chains`` / ``member`` as in ``sampler_summary``; ``seed`` selects the Philox noise (a stream of its own: the sampler's draws are
+        not touched).  Returns the dictionary of ``host.ppc_result``; ``return_draws`` adds ``y_rep`` [chains, draws, n_obs],
+        ``discrepancies`` ``T_obs`` / ``T_rep`` [chains, draws, D, 4], ``sigma_sq`` the draws' ``sigma_sq`` [chains, draws, D] as the kernel
+        formed them."""
+        chain0, n_sel = self._chain_range(chains, member)
+        group = getattr(self, "members", None)
+        cap = (group[chain0 // (self.n_chains // len(group))] if group else self)._n_obs      # observations given to set_problem: n_obs is at most that
+        R = self._cfg.num_results if self._cfg is not None else 0
+        D = self.D
+        probs, n_q = self._probs(probs)
+        idx = np.zeros(max(cap, 1), dtype=np.int32)
+        n_obs, nf = C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.magi_sampler_ppc(self._h, chain0, n_sel, int(seed) & 0xFFFFFFFFFFFFFFFF, n_q, _ptr(probs), *([None] * 10), idx.ctypes.data_as(_ip),
+                                               C.byref(n_obs), None))
+        K = int(n_obs.value)
+        e = idx[:K].astype(np.int64)
+        o = self._ppc_outputs(n_sel * R, K, D, n_q, return_draws, discrepancies)
+        s2 = np.empty((n_sel, R, D)) if sigma_sq else None
+        if K:
+            self._check(self._lib.magi_sampler_ppc(self._h, chain0, n_sel, int(seed) & 0xFFFFFFFFFFFFFFFF, n_q, _ptr(probs), *self._ppc_pointers(o), C.byref(nf), None,
+                                                   None, _ptr(s2)))
+        else:
+            o["pval"][:] = np.nan
+        shape = lambda a, *s: None if a is None else a.reshape(n_sel, R, *s)
+        out = ppc_result(e // self.N, D, o["mean"], o["sd"], o["quant"], o["pit"], o["pval"], o["excl"], nf.value,
+                         obs_index=np.stack([e % self.N, e // self.N], axis=1), probs=probs, y_rep=shape(o["y_rep"], K),
+                         T_obs=shape(o["T_obs"], D, 4), T_rep=shape(o["T_rep"], D, 4))
+        if sigma_sq:
+            out["sigma_sq"] = s2
+        return out
+
+    def sampler_sigma_sq(self, chains=None, member=None):
+        """The noise variances sigma_sq [chains, draws, D] of the finished sampler run's draws as the device forms them (softplus(sig_pre)
+        + LB, or a fixed variance's constant; magi_sampler_ppc's sigma_sq_out): what ``ppc`` takes beside draws derived from the run's."""
+        chain0, n_sel = self._chain_range(chains, member)
+        s2 = np.empty((n_sel, self._cfg.num_results if self._cfg is not None else 0, self.D))
+        self._check(self._lib.magi_sampler_ppc(self._h, chain0, n_sel, 0, 0, None, *([None] * 12), _ptr(s2)))      # asked for alone: nothing else is computed
+        return s2
+
     def selftest(self, drift=None, force=False):
         """Self-test of the library this engine runs (magi_v2_amd.selftest.ensure: cached verdict, or a run on handles of its own);
         returns the Report, raises MagiSelfTestError.  The base library is tested for ``drift`` (a built-in name) or, None, all three."""
@@ -701,6 +790,7 @@ class MagiEngine:
                                                 None if ids is None else ids.ctypes.data_as(_lp)))
         self.n_chains = n
         self._cfg = cfg
+        self._chain_ids = np.arange(n, dtype=np.int64) if ids is None else ids.copy()      # the chains' Philox ids (sampler_sigma_sq / ppc of derived draws)
 
     def sampler_run(self, n_steps: int):
         """Advance all chains by n_steps transitions; returns (leapfrogs taken, device ms)."""

@@ -467,6 +467,53 @@ def compare_elpd(models, kind="loo"):
 
 
 # --------------------------------------------------------------------------------------------
+# posterior predictive checks: the host side (replicates, PIT and discrepancies are the device's, csrc/ppc.hip)
+# --------------------------------------------------------------------------------------------
+
+PPC_STATS = ("chi2", "mean", "maxabs", "acf1")       # the order of T[0..3] in include/magi_hip.h
+
+
+def pit_ks(pit, comp, D):
+    """Kolmogorov distance of the PIT values from the uniform distribution, per component: sup_t |F_n(t) - t| over the finite ``pit`` of
+    the columns with ``comp == d`` -- max_i max(i / n - p_(i), p_(i) - (i - 1) / n) over the sorted values.  NaN for a component without
+    one.  Against a calibrated model it stays below about 1.95 / sqrt(n) (alpha = 0.001), PIT values of one fit being nearly independent."""
+    pit, comp = np.asarray(pit, dtype=np.float64).reshape(-1), np.asarray(comp, dtype=np.int64).reshape(-1)
+    out = np.full(int(D), np.nan)
+    for d in range(int(D)):
+        p = np.sort(pit[(comp == d) & np.isfinite(pit)])
+        n = p.shape[0]
+        if n:
+            i = np.arange(1, n + 1, dtype=np.float64)
+            out[d] = float(max(np.max(i / n - p), np.max(p - (i - 1.0) / n)))
+    return out
+
+
+def ppc_result(comp, D, mean, sd, quantiles, pit, pval, n_T_excluded, n_nonfinite=0, obs_index=None, probs=None, y_rep=None, T_obs=None,
+               T_rep=None):
+    """The dictionary ``MagiEngine.ppc`` / ``sampler_ppc`` / ``MAGI_v2.posterior_predictive`` return, from the device's arrays
+    (include/magi_hip.h: magi_ppc).  ``comp`` [K]: the component of every column.  Holds ``obs_index`` ([K, 2] pairs (grid point,
+    component), None for plain columns), ``comp``, ``n_obs`` (= K), ``y_rep`` [chains, draws, K] when given, then ``mean``, ``sd`` [K],
+    ``quantiles`` [n_q, K] with their ``probs``, ``pit`` [K], ``pvalues`` {chi2, mean, maxabs, acf1}: each [D], the posterior predictive
+    p-value of that discrepancy per component, ``T_obs`` / ``T_rep`` [chains, draws, D, 4] when given, ``n_T_excluded`` [D],
+    ``n_nonfinite`` and ``pit_ks`` [D], the Kolmogorov distance of each component's PIT values from uniform (``pit_ks``)."""
+    comp = np.asarray(comp, dtype=np.int64).reshape(-1)
+    D = int(D)
+    pval = np.asarray(pval, dtype=np.float64).reshape(D, len(PPC_STATS))
+    out = {"obs_index": None if obs_index is None else np.asarray(obs_index, dtype=np.int64).reshape(-1, 2), "comp": comp, "n_obs": int(comp.shape[0])}
+    if y_rep is not None:
+        out["y_rep"] = y_rep
+    pit = np.asarray(pit, dtype=np.float64).reshape(-1)
+    out.update(mean=mean, sd=sd, quantiles=quantiles, probs=probs, pit=pit,
+               pvalues={s: pval[:, t].copy() for t, s in enumerate(PPC_STATS)})
+    if T_obs is not None:
+        out["T_obs"] = T_obs
+    if T_rep is not None:
+        out["T_rep"] = T_rep
+    out.update(n_T_excluded=np.asarray(n_T_excluded, dtype=np.int64).reshape(D), n_nonfinite=int(n_nonfinite), pit_ks=pit_ks(pit, comp, D))
+    return out
+
+
+# --------------------------------------------------------------------------------------------
 # drifts
 # --------------------------------------------------------------------------------------------
 
