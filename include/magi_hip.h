@@ -705,6 +705,15 @@ int magi_sampler_profile(magi_handle* h, int n_slots, double* stream_us, double*
  * [6] = k_point; [7] = the algorithmic bytes of one gradient evaluation as SURVEY 8d counts them (3 D N W 8 + C 10 N D 8). */
 int magi_gradient_bytes(magi_handle* h, int n_chains, double* phase_bytes);
 
+/* Storage formats of the packed operator blocks (option "tile_demote"): n_blocks = the 128 x 128 blocks of the current
+ * matrices, n_demoted = those of them the packing certified and stores a second time as fp32 -- an off-diagonal block whose row and
+ * column abs-sums are at most 2^-29 of the abs-sums of the same rows / columns of the diagonal blocks that feed the same outputs, so
+ * that its fp32 rounding (2^-24) moves an output by no more than the fp64 rounding of the diagonal block's own product.  The VALU
+ * streaming kernels read a demoted block's fp32 copy; its fp64 entries hold the same (rounded) values, so every kernel family
+ * multiplies one operator.  No block is skipped and all arithmetic is fp64.  block_bytes = the operator bytes one launch of the
+ * streaming kernel that serves n_chains reads (the first term of magi_gradient_bytes' [4]).  Any pointer may be null. */
+int magi_tile_formats(magi_handle* h, int n_chains, int64_t* n_blocks, int64_t* n_demoted, double* block_bytes);
+
 /* Name of the streaming kernel a batch of n_chains runs on with the current matrices, problem and options:
  * "k_stream<1>", "k_stream<2>" (VALU), "k_stream_sep<CW=8|16>" (matrix cores, separable drift), "k_stream_mc". */
 int magi_stream_kernel_name(magi_handle* h, int n_chains, char* buf, int cap);
@@ -720,7 +729,7 @@ int magi_stream_kernel_name(magi_handle* h, int n_chains, char* buf, int cap);
  *                                                   chain's samples do not depend on how many chains share its GPU
  *   "sep_pair_min"        MAGI_SEP_PAIR_MIN         clamped to 0..2^30; read at the next packing
  *   "fused_parity"        MAGI_FUSED_PARITY         1: magi_logpost_grad_fused evaluates as an odd leapfrog slot
- *   "gemm_remap_min"      MAGI_GEMM_REMAP_MIN       clamped to 0..2^30
+ *   "gemm_remap_min"     MAGI_GEMM_REMAP_MIN       clamped to 0..2^30
  *   "potrf_panels"        MAGI_POTRF_PANELS         1..16
  *   "potrf_lookahead_min" MAGI_POTRF_LOOKAHEAD_MIN  >= 0
  *   "no_graph"            MAGI_NO_GRAPH             flag
@@ -732,7 +741,9 @@ int magi_stream_kernel_name(magi_handle* h, int n_chains, char* buf, int cap);
  * > 0: magi_summarize / magi_sampler_summarize and magi_elpd / magi_sampler_elpd gather at most this many columns per chunk (0 = what the
  * work space allows).  Likewise the two of the GP conditioning: gp_chunk_rows, 0..2^16; > 0: magi_gp_predict / magi_sampler_gp_predict work on
  * at most this many rows of t_new per chunk (no effect on any result); gp_profile, a flag: they time their stages (magi_gp_profile; a
- * synchronisation per stage). */
+ * synchronisation per stage).  And the storage switch of the packing, tile_demote, 0 or 1 (default 1; the variable MAGI_TILE_DEMOTE = 0 or 1 is
+ * read by magi_create): 1: the packing stores the operator blocks it can certify a second time as fp32 for the VALU streaming kernels
+ * (magi_tile_formats); 0: every block fp64, as before the format existed; read at the next packing. */
 int magi_set_option(magi_handle* h, const char* name, int64_t value);
 
 /* Diagnostics: per-class device time of the last magi_build_matrices run with option "build_profile" set

@@ -37,13 +37,14 @@ void free_matrices(magi_handle* h) {
     magi_model_default(h->pb, &h->model);          // (frees dObsw)
     free_dev(h->dTimes);
     h->dTimes = nullptr; h->times_N = 0; h->times_cap = 0; h->pb.tgrid = nullptr;
-    free_dev(h->dTiles); free_dev(h->dTasks);
+    free_dev(h->dTiles); free_dev(h->dTasks); free_dev(h->dTiles32);
     for (int k = 0; k < 3; ++k) { free_dev(h->dDense[k]); h->dDense[k] = nullptr; }
     h->dense_N = h->dense_D = 0;
     for (int k = 0; k < magi_handle::WS_COUNT; ++k) { free_dev(h->ws[k]); h->ws[k] = nullptr; h->ws_cap[k] = 0; }
     h->dCsym = h->dM = h->dMt = h->dKsym = h->dYobs = nullptr;
-    h->dTiles = nullptr; h->dTasks = nullptr;
-    h->tiles_cap = h->tasks_cap = 0;
+    h->dTiles = nullptr; h->dTasks = nullptr; h->dTiles32 = nullptr;
+    h->tiles_cap = h->tasks_cap = h->tiles32_cap = 0;
+    h->n_demoted = 0; h->pb.tiles32 = nullptr;
     h->have_matrices = h->have_problem = false;
 }
 
@@ -143,6 +144,13 @@ int refuse_group(magi_handle* h, const char* what) {
     return magi_fail(h, MAGI_E_STATE, std::string(what) + " needs a handle with matrices of its own: this handle is a problem group (magi_group_create)");
 }
 
+// Operator bytes one launch of streaming kernel k reads: every block as 128 x 128 doubles, except that the VALU kernels read the
+// demoted blocks' fp32 copies (pack.hip); the matrix-core kernels read the fp64 entries of every block.
+double block_bytes(const magi_handle* h, StreamKernel k) {
+    const bool narrow = k == StreamKernel::Valu1 || k == StreamKernel::Valu2;
+    return ((double)h->pb.n_tasks * 8.0 - (narrow ? (double)h->n_demoted * 4.0 : 0.0)) * MAGI_TB * MAGI_TB;
+}
+
 // "" when handle m can join a group whose shape is `ref`, else why not
 std::string member_mismatch(const DevProblem& ref, const magi_handle* m) {
     if (!m->have_matrices || !m->have_problem) return "has no problem set (magi_set_matrices / magi_build_matrices, then magi_set_problem)";
@@ -201,6 +209,9 @@ void magi_options_from_env(MagiOptions& o) {
     for (const OptRow& r : kOptions)
         if (const char* e = r.env ? getenv(r.env) : nullptr)
             (void)set_option(o, r, r.rule == FLAG ? 1 : r.rule == FAMILY ? (!strcmp(e, "mc") ? 1 : !strcmp(e, "valu") ? 2 : 0) : atoll(e));
+    // the storage switch of csrc/pack.hip (below, magi_set_option: no row of the table): 0 or 1, any other value keeps the default
+    if (const char* e = getenv("MAGI_TILE_DEMOTE"))
+        if (!strcmp(e, "0") || !strcmp(e, "1")) o.tile_demote = e[0] - '0';
 }
 
 // What makes which state of a handle stale.  Every level includes the ones before it; the call, the level it raises, and why -- the code's
@@ -400,6 +411,7 @@ int magi_group_create(magi_handle* const* members, int n_members, magi_handle** 
     g->pb = members[0]->pb;                        // the shape; the data of every member is read from the device table
     g->pb.Csym = g->pb.M = g->pb.Mt = g->pb.Ksym = g->pb.yobs = g->pb.tiles = nullptr;
     g->pb.tasks = g->pb.stasks = nullptr;
+    g->pb.tiles32 = nullptr;
     g->pb.tgrid = nullptr;
     magi_model_default(g->pb, nullptr);            // (every member brings its own supports, priors and observation model)
     size_t cap = 0;
@@ -1146,6 +1158,9 @@ static double ckpt_tag(const magi_handle* h, long long chain_id) {
     const double dbl[4] = {c.step_size, c.target_accept, c.max_energy_diff, c.min_temp};
     mix(ints, sizeof(ints)); mix(dbl, sizeof(dbl)); mix(&c.seed, sizeof(c.seed)); mix(&chain_id, sizeof(chain_id));
     magi_model_mix(h->model, h->pb, mix);      // (supports, priors, observation model: each while it is set)
+    // (fp32 copies of operator blocks, option tile_demote: while the pack made any -- a resume with the other setting would continue on
+    //  operators that differ in rounding; a tag at a shape where nothing is demoted is what it was before the format existed)
+    if (h->n_demoted) mix(&h->n_demoted, sizeof(h->n_demoted));
     return (double)(x & ((1ull << 52) - 1));
 }
 
@@ -1387,6 +1402,13 @@ int magi_set_option(magi_handle* h, const char* name, int64_t value) {
         h->opt.gp_chunk_rows = (int)value;
         return MAGI_OK;
     }
+    // the storage switch of csrc/pack.hip: fp32 copies of the operator blocks the criterion certifies (1, the default) or none (0); read at
+    // the next packing.  It changes the storage format of a pack, not how a kernel is tuned: kept beside the table like the switches above
+    if (std::strcmp(name, "tile_demote") == 0) {
+        if (value < 0 || value > 1) return magi_fail(h, MAGI_E_BADARG, "tile_demote in [0, 1]");
+        h->opt.tile_demote = (int)value;
+        return MAGI_OK;
+    }
     if (std::strcmp(name, "gp_profile") == 0) {
         h->opt.gp_profile = value != 0;
         return MAGI_OK;
@@ -1426,11 +1448,11 @@ int magi_gradient_bytes(magi_handle* h, int n_chains, double* phase_bytes) {
     phase_bytes[2] = 1.0 * mat + 5.0 * vec;   // Mt      ; read Kr, X, Cx, yobs, write gX
     phase_bytes[3] = 5.0 * vec;               // reduce  ; read X, Cx, r, Kr, yobs
     const double nslot = (double)std::min(pb.nb, 2 * pb.wb + 1);
-    const double tiles = (double)pb.n_tasks * MAGI_TB * MAGI_TB * 8.0;      // packed blocks of FH, FK (lower block triangle), FE
+    const StreamKernel k = magi_stream_kernel(h, n_chains);
+    const double tiles = block_bytes(h, k);                                 // packed blocks of FH, FK (lower block triangle), FE, at the width this kernel reads them
     phase_bytes[4] = tiles + 2.0 * (double)n_chains * pb.n_tasks * MAGI_TB * 8.0;   // k_stream / k_stream_mc: + 2 TB partials per block and chain
     phase_bytes[5] = (double)n_chains * magi_leap_wgs(pb) * PART_K * 8.0; // tail: the workgroup partials
     phase_bytes[6] = 4.0 * vec * nslot + 10.0 * vec;                       // k_point: block partials of the four products; X, yobs, p, rho, g, p_leaf, p', x'
-    const StreamKernel k = magi_stream_kernel(h, n_chains);
     if (h->have_problem && (k == StreamKernel::Sep8 || k == StreamKernel::Sep16)) {
         // k_stream_sep writes a block vector per (task, product, matrix-core column in use) and reads its operands from the mirror planes
         // (once per XCD at the fabric); its point kernel re-reads the product slots and writes the next slot's mirror
@@ -1440,6 +1462,16 @@ int magi_gradient_bytes(magi_handle* h, int n_chains, double* phase_bytes) {
         phase_bytes[6] = pr + 10.0 * vec + mw;
     }
     phase_bytes[7] = 3.0 * (double)pb.D * pb.N * W * 8.0 + 10.0 * vec;    // SURVEY 8d algorithmic bytes of one gradient evaluation
+    return MAGI_OK;
+}
+
+int magi_tile_formats(magi_handle* h, int n_chains, int64_t* n_blocks, int64_t* n_demoted, double* bytes) {
+    if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_tile_formats");
+    if (!h->have_matrices) return magi_fail(h, MAGI_E_STATE, "no matrices");
+    if (n_blocks) *n_blocks = h->pb.n_tasks;
+    if (n_demoted) *n_demoted = h->n_demoted;
+    if (bytes) *bytes = block_bytes(h, magi_stream_kernel(h, n_chains));
     return MAGI_OK;
 }
 

@@ -93,7 +93,7 @@ void k_stream_mc(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
     const int tix = (int)blockIdx.x - n_dec;
     typedef const int __attribute__((address_space(4))) * const_int_ptr;
     const_int_ptr tk = (const_int_ptr)(unsigned long long)(pb.tasks + 4 * (size_t)tix);
-    const int d = tk[0], kind = tk[1], bi = tk[2], bj = tk[3];
+    const int d = tk[0], kind = task_kind(tk[1]), bi = tk[2], bj = tk[3];      // (a demoted block's fp64 entries hold the rounded values: read as any other)
     const int nch = ch.n_chains;
 
     // Tile stream.  Wave w owns rows [32 w, 32 w + 32); its eight steps are ordered by column group: phase p = s >> 1 works on
@@ -680,13 +680,21 @@ __global__ __launch_bounds__(PT_THREADS) void k_point(DevProblem pb, DevChains c
 }
 
 // load-only twin of k_stream's tile stream (bench.py's ceiling leg): every workgroup reads its 128 KB block with the same
-// 16-B-per-lane pattern and does nothing else -- what the memory system delivers for this layout and working set
-__global__ __launch_bounds__(256) void k_read_tiles(const double2* __restrict__ p, double* out, int rev) {
-    const double2* q = p + (size_t)blockIdx.x * (MAGI_TB * MAGI_TB / 2) + threadIdx.x;
+// 16-B-per-lane pattern and does nothing else -- what the memory system delivers for this layout and working set.  The bytes are k_stream's:
+// a demoted block's 64 KB fp32 copy (one direction: k_stream takes it in one round), 128 KB of every other.
+__global__ __launch_bounds__(256) void k_read_tiles(const double2* __restrict__ p, const double2* __restrict__ p32, const int* __restrict__ tasks, double* out, int rev) {
+    const int s32 = p32 ? task_slot32(tasks[4 * blockIdx.x + 1]) : 0;      // (p32 null: the twin of a matrix-core kernel, which reads every block's doubles)
     double a = 0.0;
     constexpr int R = MAGI_TB * MAGI_TB / 2 / 256;
+    if (s32) {
+        const double2* q = p32 + (size_t)(s32 - 1) * (MAGI_TB * MAGI_TB / 4) + threadIdx.x;
 #pragma unroll
-    for (int r = 0; r < R; ++r) { const double2 v = q[(rev ? R - 1 - r : r) * 256]; a += v.x + v.y; }     // (odd launches walk backwards, as k_stream does)
+        for (int r = 0; r < R / 2; ++r) { const double2 v = q[r * 256]; a += v.x + v.y; }
+    } else {
+        const double2* q = p + (size_t)blockIdx.x * (MAGI_TB * MAGI_TB / 2) + threadIdx.x;
+#pragma unroll
+        for (int r = 0; r < R; ++r) { const double2 v = q[(rev ? R - 1 - r : r) * 256]; a += v.x + v.y; }     // (odd launches walk backwards, as k_stream does)
+    }
     if (a == 12345.678) out[0] = a;
 }
 
@@ -881,7 +889,9 @@ int magi_launch_point(magi_handle* h, int n_chains, int parity, hipStream_t s) {
 }
 
 int magi_launch_read_tiles(magi_handle* h, int rev, hipStream_t s) {
-    return magi_launch(h, "read_tiles launch: ", k_read_tiles, dim3(h->pb.n_tasks), dim3(256), s, reinterpret_cast<const double2*>(h->pb.tiles), h->d_fin, rev);
+    const bool narrow = h->stream_kernel == StreamKernel::Valu1 || h->stream_kernel == StreamKernel::Valu2;      // (of the batch last set up, as magi_launch_stream)
+    return magi_launch(h, "read_tiles launch: ", k_read_tiles, dim3(h->pb.n_tasks), dim3(256), s, reinterpret_cast<const double2*>(h->pb.tiles),
+                       reinterpret_cast<const double2*>(narrow ? h->pb.tiles32 : nullptr), h->pb.tasks, h->d_fin, rev);
 }
 
 int magi_launch_plan_eval(magi_handle* h, int n_chains, hipStream_t s, int parity) {

@@ -38,7 +38,14 @@
     task.x = tk[0]; task.y = tk[1]; task.z = tk[2]; task.w = tk[3];
     // the wave's rows in chunks of 8, two chunks in flight (a0 / a1): 16 KB per wave on the wire while one chunk is in the ALUs.
     // tile loads need nothing but the block index: on the wire before the plan-dependent loads (except in the waves that derive theta')
-    const double2* A = reinterpret_cast<const double2*>(pb.tiles + (size_t)tix * TB * TB + (size_t)((threadIdx.x >> 6) * ST_RW) * TB) + (threadIdx.x & 63);
+    // A DEMOTED block (pack.hip: the criterion; workgroup-uniform, known from the descriptor alone) is read from its fp32 copy instead: the wave's
+    // strip of 32 rows is 16 KB there -- [row pair][lane][2 rows x 2 columns], tile32_index -- which is exactly the two chunks a wave has in flight:
+    // the same sixteen 16-B loads into the same registers (a0 = row pairs 0..7, a1 = 8..15, held as raw bits), no refill round and no walk
+    // direction.  Only the addresses differ up to the loop; the loop converts to fp64 on use and runs the same butterflies and accumulators.
+    const int s32 = task_slot32(task.y);
+    static_assert(ST_RW == 32, "tile32_index lays a block out for 32-row wave strips");
+    const double2* A = (s32 ? reinterpret_cast<const double2*>(pb.tiles32 + (size_t)(s32 - 1) * TB * TB + (size_t)((threadIdx.x >> 6) * ST_RW) * TB)
+                            : reinterpret_cast<const double2*>(pb.tiles + (size_t)tix * TB * TB + (size_t)((threadIdx.x >> 6) * ST_RW) * TB)) + (threadIdx.x & 63);
     constexpr int NCK = ST_RW / 8;
     // Odd slots walk the wave's row chunks backwards: what a slot read LAST is what the next one reads FIRST, so the tail of the
     // block stream is still in the XCD's L2 (4 MB against 9 MB of blocks per XCD; tools/micro/readshape.hip: 5-15 % on the
@@ -47,15 +54,16 @@
     static_assert(NC <= 2, "three or more chains per pass run k_stream_mc");
     constexpr bool ALT = true;
     const int pc0 = (ALT && (parity & 1)) ? NCK - 1 : 0, pcs = (ALT && (parity & 1)) ? -1 : 1;
+    const int ld0 = s32 ? 0 : pc0 * 8, ld1 = s32 ? 8 : (pc0 + pcs) * 8;      // first 1-KB line of the two chunks in flight (fp32: the whole strip)
     double2 a0[8], a1[8];
     if ((threadIdx.x >> 6) >= NC) {
 #pragma unroll
-        for (int r = 0; r < 8; ++r) a0[r] = A[(size_t)(pc0 * 8 + r) * (TB / 2)];
+        for (int r = 0; r < 8; ++r) a0[r] = A[(size_t)(ld0 + r) * (TB / 2)];
 #pragma unroll
-        for (int r = 0; r < 8; ++r) a1[r] = A[(size_t)((pc0 + pcs) * 8 + r) * (TB / 2)];
+        for (int r = 0; r < 8; ++r) a1[r] = A[(size_t)(ld1 + r) * (TB / 2)];
     }
     __builtin_amdgcn_sched_barrier(0);
-    const int d = task.x, kind = task.y, bi = task.z, bj = task.w;
+    const int d = task.x, kind = task_kind(task.y), bi = task.z, bj = task.w;
     const int N = pb.N;
 
     // What to evaluate for each chain, from the plan the point phase executed LAST (the decisions that complete it run
@@ -124,9 +132,9 @@
     })
     if (wave < NC) {                 // (the waves that derived theta' issue their first chunks now)
 #pragma unroll
-        for (int r = 0; r < 8; ++r) a0[r] = A[(size_t)(pc0 * 8 + r) * (TB / 2)];
+        for (int r = 0; r < 8; ++r) a0[r] = A[(size_t)(ld0 + r) * (TB / 2)];
 #pragma unroll
-        for (int r = 0; r < 8; ++r) a1[r] = A[(size_t)((pc0 + pcs) * 8 + r) * (TB / 2)];
+        for (int r = 0; r < 8; ++r) a1[r] = A[(size_t)(ld1 + r) * (TB / 2)];
     }
     __builtin_amdgcn_sched_barrier(0);
     double thv[NC][P];
@@ -165,6 +173,43 @@
 #pragma unroll
         for (int k = 0; k < NACC; ++k) { cacc[c][k].x = 0.0; cacc[c][k].y = 0.0; }
     }
+    if (s32) {
+        // the fp32 copy: physical chunk pk = row pairs 4 pk .. 4 pk + 3 of the strip, already in a0 (pk < 2) / a1; each register pair holds
+        // (row 2 k: columns 2 l, 2 l + 1 | row 2 k + 1: the same columns) as four floats.  Converted on use; the products, the butterfly and
+        // the per-physical-chunk column sums are the fp64 path's, so the result has no slot parity in it at all.
+#pragma unroll
+        for (int pk = 0; pk < NCK; ++pk) {
+            double2 (&a)[8] = pk < NCK / 2 ? a0 : a1;
+            const int row0 = wave * ST_RW + pk * 8;
+            double p[NC][8];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const double2 w = a[(pk & 1) * 4 + j];
+                const double e0 = (double)__int_as_float(__double2loint(w.x)), e1 = (double)__int_as_float(__double2hiint(w.x));
+                const double o0 = (double)__int_as_float(__double2loint(w.y)), o1 = (double)__int_as_float(__double2hiint(w.y));
+#pragma unroll
+                for (int c = 0; c < NC; ++c) {
+                    double2& acc = cacc[c][pk];
+                    p[c][2 * j] = fma(e1, vc[c].y, e0 * vc[c].x);
+                    const double xe = vrow[c][row0 + 2 * j];
+                    acc.x = fma(e0, xe, acc.x);
+                    acc.y = fma(e1, xe, acc.y);
+                    p[c][2 * j + 1] = fma(o1, vc[c].y, o0 * vc[c].x);
+                    const double xo = vrow[c][row0 + 2 * j + 1];
+                    acc.x = fma(o0, xo, acc.x);
+                    acc.y = fma(o1, xo, acc.y);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < NC; ++c) rowout[c][row0 + (lane >> 3)] = tsum8(p[c], lane);        }
+#pragma unroll
+        for (int c = 0; c < NC; ++c) {
+            double2 tot = cacc[c][0];
+#pragma unroll
+            for (int k = 1; k < NACC; ++k) { tot.x += cacc[c][k].x; tot.y += cacc[c][k].y; }
+            *reinterpret_cast<double2*>(&colacc[wave][c][2 * lane]) = tot;
+        }
+    } else {
 #pragma unroll
     for (int ck = 0; ck < NCK; ++ck) {
         double2 (&a)[8] = (ck & 1) ? a1 : a0;
@@ -208,6 +253,7 @@
         }
         *reinterpret_cast<double2*>(&colacc[wave][c][2 * lane]) = tot;
     }
+    }       // (fp64 blocks)
     MAGI_STAMP(stream, 5);
     __syncthreads();
     MAGI_STAMP(stream, 6);

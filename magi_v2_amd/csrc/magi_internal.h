@@ -85,7 +85,20 @@ struct DevProblem {
     const double* obsw;    // [D][N] known weight of every observation, laid out like yobs (1 where none was given, and at unobserved entries);
                            // nullptr: every weight is 1.  With obs_links == 0 and no weights the kernels run the instructions they ran without a model;
                            // otherwise yobs holds g_d(y)
+    const float* tiles32;  // [demoted blocks][TB][TB] fp32 copies of the blocks the pack certified (pack.hip: the criterion), in the in-block order
+                           // of tile32_index; a task names its copy in the upper bits of `kind` (task_slot32).  The same blocks in `tiles` hold the
+                           // same rounded values as doubles.  Read by the VALU streaming kernels and their load-only twin only; nullptr: none demoted
 };
+
+// A task's `kind` word: TileKind in the low byte; above it 1 + the block's index in tiles32 when the block is demoted, 0 = fp64 only.
+constexpr int TK_SLOT_SHIFT = 8;
+__host__ __device__ inline int task_kind(int word) { return word & ((1 << TK_SLOT_SHIFT) - 1); }
+__host__ __device__ inline int task_slot32(int word) { return word >> TK_SLOT_SHIFT; }
+// Where entry (r, c) of a demoted block sits in its fp32 copy: wave w = r / 32 of k_stream owns rows [32 w, 32 w + 32); a lane holds columns
+// 2 l, 2 l + 1 of two consecutive rows in one 16-B load, and the 64 lanes of a load are contiguous (1 KB): [w][row pair][lane][row & 1][c & 1].
+__host__ __device__ inline int tile32_index(int r, int c) { return ((((r >> 5) * 16 + ((r & 31) >> 1)) * 64 + (c >> 1)) << 2) + ((r & 1) << 1) + (c & 1); }
+// THE threshold of the certified fp32 format (pack.hip): 2^-24 (fp32 rounding) x 2^-29 = 2^-53, the fp64 rounding of the reference sums.
+constexpr double MAGI_DEMOTE_RATIO = 0x1p-29;
 
 // Support of one parameter entry, as a table entry (x, y) = (sign, bound):
 //   sign +1  theta = bound + softplus(pre)    (positive: bound 0; lower)      d theta / d pre =  sg
@@ -1045,6 +1058,7 @@ struct MagiOptions {
                                         // every rank then runs the same kernel family, whatever its own share -- shard.family_chains_for)
     int sep_pair_min = 256;             // pack.hip: pair the diagonal blocks FH_bb + FK_bb when there are more tasks than this
     int fused_parity = 0;               // magi_logpost_grad_fused evaluates as an even (0) / odd (1) leapfrog slot
+    int tile_demote = 1;                // pack.hip: store the operator blocks the criterion certifies as fp32 for the VALU streaming kernels (0: none)
     int gemm_remap_min = MAGI_GEMM_REMAP_MIN_DEFAULT;      // build.hip: super-block tile order from this many super-blocks per launch (24 until round 4;
                                         // while it is at its default, potrf's thin launches keep 24: GemmArgs::remap_min)
     int potrf_panels = 3;               // build.hip: 128-wide panels per block column of the Cholesky factorisation (3: best of 2..8 at N = 1024..8192, profiles/r04_potrf_lookahead_ab.txt)
@@ -1141,9 +1155,12 @@ struct magi_handle {
     double* dTiles = nullptr;
     int* dTasks = nullptr;
     size_t tiles_cap = 0, tasks_cap = 0;
+    float* dTiles32 = nullptr;       // pb.tiles32: fp32 copies of the demoted blocks (grown like dTiles, stale with it)
+    size_t tiles32_cap = 0;
+    int n_demoted = 0;               // blocks of the current pack that have one (0 under the option tile_demote = 0, banded fused storage, N <= 256)
     // work space of the matrix build and the packing, kept between calls (grow-only): a repeated build at N = 8192 otherwise spends
     // more host time in hipMalloc / hipFree of ~35 GB than the GPU spends on the build
-    enum { WS_KAP = 0, WS_P, WS_PP, WS_DINV, WS_PANEL, WS_TCS, WS_TM, WS_TKS, WS_TE, WS_APPLY, WS_TI, WS_COUNT };
+    enum { WS_KAP = 0, WS_P, WS_PP, WS_DINV, WS_PANEL, WS_TCS, WS_TM, WS_TKS, WS_TE, WS_APPLY, WS_TI, WS_TSUM, WS_COUNT };
     double* ws[WS_COUNT] = {};
     size_t ws_cap[WS_COUNT] = {};
 

@@ -61,19 +61,68 @@ __global__ __launch_bounds__(256) void k_pack_dense(const double* __restrict__ s
     }
 }
 
-// one TB x TB block of FH / FK / FE per workgroup -> packed tile storage, zero beyond N and beyond the band
+// one TB x TB block of FH / FK / FE per workgroup -> packed tile storage, zero beyond N and beyond the band.  A demoted block (the task
+// names its fp32 copy, task_slot32) is rounded to fp32 in BOTH buffers: `tiles` then holds fp32-representable doubles, so the kernels that
+// read it (k_stream_mc, k_stream_sep, the fused log posterior at three or more states) and the VALU kernels that read `tiles32` multiply
+// the same operator.
 __global__ __launch_bounds__(256) void k_pack_tiles(const double* __restrict__ H, const double* __restrict__ K, const double* __restrict__ E,
-                                                    const int* __restrict__ tasks, double* __restrict__ tiles, int N, int fb) {
+                                                    const int* __restrict__ tasks, double* __restrict__ tiles, float* __restrict__ tiles32, int N, int fb) {
     const int t = blockIdx.x;
-    const int d = tasks[4 * t], kind = tasks[4 * t + 1], bi = tasks[4 * t + 2], bj = tasks[4 * t + 3];
+    const int d = tasks[4 * t], kind = task_kind(tasks[4 * t + 1]), s32 = task_slot32(tasks[4 * t + 1]), bi = tasks[4 * t + 2], bj = tasks[4 * t + 3];
     const double* A = (kind == TK_FH ? H : kind == TK_FK ? K : E) + (size_t)d * N * N;
     double* T = tiles + (size_t)t * MAGI_TB * MAGI_TB;
+    float* T32 = s32 ? tiles32 + (size_t)(s32 - 1) * MAGI_TB * MAGI_TB : nullptr;
     for (int e = threadIdx.x; e < MAGI_TB * MAGI_TB; e += 256) {
         const int r = e / MAGI_TB, c = e - r * MAGI_TB;
         const int i = bi * MAGI_TB + r, j = bj * MAGI_TB + c;
         double v = 0.0;
         if (i < N && j < N && (fb < 0 || abs(i - j) <= fb)) v = A[(size_t)i * N + j];
+        if (T32) {
+            const float f = (float)v;
+            T32[tile32_index(r, c)] = f;
+            v = (double)f;
+        }
         T[e] = v;
+    }
+}
+
+// The inputs of the demotion criterion (magi_pack_matrices): sums[t][0 .. TB) = the abs-sums of the rows of block t, sums[t][TB .. 2 TB) those
+// of its columns, entries beyond N counting as the zeros they are packed as.  Rows: a wave per row, lane = two columns; columns: a thread
+// per column.  Where fp32 does not round to 2^-24 relative: a non-zero entry of an OFF-diagonal block (a candidate, never a reference) below
+// FLT_MIN = 2^-126 counts as FLT_MIN -- its rounding error is at most 2^-150 = 2^-24 FLT_MIN, so the criterion's error model holds for the
+// sums as counted (the far entries of Matern operators decay through that range to zero) --; a column with an entry above FLT_MAX or not
+// finite reports NaN, which fails every comparison, for the block itself and for the blocks it would be the reference of.
+__global__ __launch_bounds__(256) void k_tile_abs_sums(const double* __restrict__ H, const double* __restrict__ K, const double* __restrict__ E,
+                                                       const int* __restrict__ tasks, double* __restrict__ sums, int N) {
+    const int t = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int d = tasks[4 * t], kind = task_kind(tasks[4 * t + 1]), bi = tasks[4 * t + 2], bj = tasks[4 * t + 3];
+    const double* A = (kind == TK_FH ? H : kind == TK_FK ? K : E) + (size_t)d * N * N;
+    double* S = sums + (size_t)t * 2 * MAGI_TB;
+    const double floor32 = bi != bj ? 0x1p-126 : 0.0;
+    auto counted = [floor32](double v) { v = fabs(v); return v == 0.0 ? 0.0 : fmax(v, floor32); };
+    for (int r = wave; r < MAGI_TB; r += 4) {
+        const int i = bi * MAGI_TB + r;
+        double a = 0.0;
+        for (int c = lane; c < MAGI_TB; c += 64) {
+            const int j = bj * MAGI_TB + c;
+            if (i < N && j < N) a += counted(A[(size_t)i * N + j]);
+        }
+        a = wave_sum(a);
+        if (lane == 0) S[r] = a;
+    }
+    if (threadIdx.x < MAGI_TB) {
+        const int j = bj * MAGI_TB + threadIdx.x;
+        double a = 0.0;
+        bool fits = true;
+        for (int r = 0; r < MAGI_TB; ++r) {
+            const int i = bi * MAGI_TB + r;
+            if (i < N && j < N) {
+                const double v = counted(A[(size_t)i * N + j]);
+                a += v;
+                fits = fits && v <= 3.40282347e+38;          // (false for NaN as well)
+            }
+        }
+        S[MAGI_TB + threadIdx.x] = fits ? a : NAN;
     }
 }
 
@@ -142,6 +191,7 @@ int magi_pack_matrices(magi_handle* h, int N, int D, int bandsize, const double*
     h->have_matrices = false;
     pb.Csym = pb.M = pb.Mt = pb.Ksym = nullptr;
     pb.tiles = nullptr; pb.tasks = pb.stasks = nullptr;
+    pb.tiles32 = nullptr; h->n_demoted = 0;
     if (!had || elems != h->mat_elems) {     // (sized exactly, the four together: all null and mat_elems 0 before the first allocation)
         double** const stacks[4] = {&h->dCsym, &h->dM, &h->dMt, &h->dKsym};
         for (double** s : stacks) { if (*s) (void)hipFree(*s); *s = nullptr; }
@@ -251,8 +301,46 @@ int magi_pack_matrices(magi_handle* h, int N, int D, int bandsize, const double*
         hipLaunchKernelGGL(k_pack_dense<PACK_COPY>, dgrid(N), dblock, 0, h->stream, dM, tM, N, N, mask);
         hipLaunchKernelGGL(k_pack_dense<PACK_SYM>, dgrid(N), dblock, 0, h->stream, dK_inv, tKs, N, N, mask);
         rc = magi_fused_operators(h, N, D, tCs, tM, tKs, tE);
+        // ---- certified fp32 storage of far blocks (option tile_demote) ----
+        // An off-diagonal block (d, kind, bi, bj) is DEMOTED when every row abs-sum is <= MAGI_DEMOTE_RATIO x the abs-sum of the same row of
+        // the diagonal block (bi, bi) of the same operator -- the block that feeds the same rows of the row-type product -- and every column
+        // abs-sum is <= MAGI_DEMOTE_RATIO x the abs-sum of the same column of block (bj, bj), for the column-type product (FE: its own diagonal
+        // blocks).  Rounding the block to fp32 changes an entry by 2^-24 relative; with the ratio 2^-29 the change of an output entry is at most
+        // 2^-53 of the diagonal block's sum of magnitudes, the fp64 rounding that block's own dot product already carries (for operands of
+        // comparable magnitude across blocks).  Padding beyond N is zero on both sides and passes (0 <= 0); a non-zero against a zero reference
+        // fails; diagonal blocks are never demoted; nothing is skipped -- a demoted block is streamed and multiplied in fp64 like every other,
+        // from 64 KB instead of 128.  With Matern operators on a grid that is long against the length scale every block with |bi - bj| >= 2
+        // passes by seven orders of magnitude and no nearer one does.  Banded fused storage is left alone.
+        std::vector<int> slot32((size_t)n_tasks, 0);
+        int n_dem = 0;
+        if (rc == MAGI_OK && h->opt.tile_demote && fb < 0 && nb > 1) {
+            double* dS = magi_workspace(h, magi_handle::WS_TSUM, (size_t)n_tasks * 2 * MAGI_TB);
+            if (!dS) return MAGI_E_HIP;
+            std::vector<double> S((size_t)n_tasks * 2 * MAGI_TB);
+            hipLaunchKernelGGL(k_tile_abs_sums, dim3(n_tasks), dim3(256), 0, h->stream, tCs, tKs, tE, h->dTasks, dS, N);
+            MAGI_HIP_CHECK(h, hipMemcpyAsync(S.data(), dS, S.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+            MAGI_HIP_CHECK(h, hipStreamSynchronize(h->stream));
+            std::vector<int> diag((size_t)D * 3 * nb, -1);
+            for (int t = 0; t < n_tasks; ++t)
+                if (tasks[4 * t + 2] == tasks[4 * t + 3]) diag[((size_t)tasks[4 * t] * 3 + tasks[4 * t + 1]) * nb + tasks[4 * t + 2]] = t;
+            for (int t = 0; t < n_tasks; ++t) {
+                const int d = tasks[4 * t], kind = tasks[4 * t + 1], bi = tasks[4 * t + 2], bj = tasks[4 * t + 3];
+                const int ti = diag[((size_t)d * 3 + kind) * nb + bi], tj = diag[((size_t)d * 3 + kind) * nb + bj];
+                if (bi == bj || ti < 0 || tj < 0) continue;
+                const double *rs = &S[(size_t)t * 2 * MAGI_TB], *cs = rs + MAGI_TB;
+                const double *rref = &S[(size_t)ti * 2 * MAGI_TB], *cref = &S[(size_t)tj * 2 * MAGI_TB + MAGI_TB];
+                bool pass = true;
+                for (int k = 0; k < MAGI_TB && pass; ++k) pass = rs[k] <= MAGI_DEMOTE_RATIO * rref[k] && cs[k] <= MAGI_DEMOTE_RATIO * cref[k];
+                if (pass) slot32[t] = ++n_dem;
+            }
+        }
+        if (rc == MAGI_OK && n_dem) {
+            if ((rc = magi_grow(h, h->dTiles32, h->tiles32_cap, (size_t)n_dem * MAGI_TB * MAGI_TB, "fp32 operator blocks"))) return rc;
+            for (int t = 0; t < n_tasks; ++t) tasks[4 * t + 1] |= slot32[t] << TK_SLOT_SHIFT;
+            MAGI_HIP_CHECK(h, hipMemcpyAsync(h->dTasks, tasks.data(), n_task_ints * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        }
         if (rc == MAGI_OK) {
-            hipLaunchKernelGGL(k_pack_tiles, dim3(n_tasks), dim3(256), 0, h->stream, tCs, tKs, tE, h->dTasks, h->dTiles, N, fb);
+            hipLaunchKernelGGL(k_pack_tiles, dim3(n_tasks), dim3(256), 0, h->stream, tCs, tKs, tE, h->dTasks, h->dTiles, h->dTiles32, N, fb);
             e = hipGetLastError();
         }
         hipError_t se = hipStreamSynchronize(h->stream);     // (also keeps `tasks` alive until the copy is done)
@@ -260,6 +348,8 @@ int magi_pack_matrices(magi_handle* h, int N, int D, int bandsize, const double*
         if (e != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("fused pack launch: ") + hipGetErrorString(e));
         if (se != hipSuccess) return magi_fail(h, MAGI_E_HIP, std::string("fused pack: ") + hipGetErrorString(se));
         pb.tiles = h->dTiles;
+        pb.tiles32 = n_dem ? h->dTiles32 : nullptr;
+        h->n_demoted = n_dem;
         pb.tasks = h->dTasks;
         pb.n_tasks = n_tasks;
         pb.stasks = h->dTasks + n_task_ints;

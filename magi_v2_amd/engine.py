@@ -85,6 +85,7 @@ _SYMBOLS = {
     "magi_sampler_profile": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _lp]),
     "magi_time_gradient": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
     "magi_gradient_bytes": (C.c_int, [C.c_void_p, C.c_int, _dp]),
+    "magi_tile_formats": (C.c_int, [C.c_void_p, C.c_int, _lp, _lp, _dp]),
     "magi_stream_kernel_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int]),
     "magi_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "magi_debug_par": (C.c_int, [C.c_void_p, C.c_int, _dp]),
@@ -949,6 +950,13 @@ class MagiEngine:
         b = np.zeros(8)
         self._check(self._lib.magi_gradient_bytes(self._h, int(n_chains), _ptr(b)))
         return b
+
+    def tile_formats(self, n_chains=1):
+        """(operator blocks, blocks of them with an fp32 copy, operator bytes a launch of the streaming kernel of ``n_chains`` reads) of
+        the current pack -- option ``tile_demote`` (include/magi_hip.h: magi_tile_formats)."""
+        nb, nd, by = C.c_int64(0), C.c_int64(0), C.c_double(0.0)
+        self._check(self._lib.magi_tile_formats(self._h, int(n_chains), C.byref(nb), C.byref(nd), C.byref(by)))
+        return int(nb.value), int(nd.value), float(by.value)
 
     @staticmethod
     def group(engines):
