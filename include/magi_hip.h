@@ -274,9 +274,10 @@ int magi_sampler_init(magi_handle* h, const magi_sampler_cfg* cfg, int n_chains,
  * leapfrogs_done, if not NULL, receives the gradient evaluations taken in this call (sum over
  * chains); kernel_ms the device time between the first and last launch of the call.
  * Between two magi_sampler_run calls of one run the chains stand at a transition boundary, and the calls that need the handle only for
- * its device, its stream or its resident dense matrices may be made: magi_summarize, magi_elpd, magi_gp_predict, magi_matern_cross,
+ * its device, its stream or its resident dense matrices may be made: magi_summarize, magi_rank_diagnostics, magi_elpd, magi_gp_predict, magi_matern_cross,
  * magi_ode_solve, magi_ode_solve_adaptive, magi_dense_apply, magi_theta_init (it captures a graph of its own on the same stream) and
- * magi_fit_hparams.  Each works in memory of its own, touches neither the chains, the problem nor the sampler's captured graph, and has
+ * magi_fit_hparams; magi_sampler_rank_diagnostics too (it answers MAGI_E_STATE while a selected chain is unfinished and touches nothing
+ * either way).  Each works in memory of its own, touches neither the chains, the problem nor the sampler's captured graph, and has
  * finished on the stream when it returns: the continued run is the uninterrupted one bit for bit.  (The calls that end a paused run
  * say so where they are declared: a matrix, problem, times or model change, magi_logpost_grad*, magi_time_gradient and
  * magi_sampler_profile -- the next magi_sampler_run then returns MAGI_E_STATE.)  Option "no_graph" may be switched between two calls
@@ -508,6 +509,53 @@ int magi_sampler_summarize(magi_handle* h, int chain0, int n_sel, int n_q, const
                            double* sig_mean, double* sig_sd, double* sig_quant, double* sig_rhat, double* sig_ess, double* sig_mcse_mean,
                            double* th_mean, double* th_sd, double* th_quant, double* th_rhat, double* th_ess, double* th_mcse_mean,
                            int* n_nonfinite);
+
+/* ---- rank-normalised convergence diagnostics -------------------------------------------------- */
+
+/* Rank-normalised split R-hat, bulk ESS and tail ESS (Vehtari, Gelman, Simpson, Carpenter, Buerkner 2021; unit csrc/rank.hip, DESIGN.md
+ * 4.4b) of K scalar columns of C chains x R draws.  draws: host [C][R][K]; the limits on C, R, C R and K are magi_summarize's.  Per column
+ * y, with S = C R pooled draws, v = the sorted pooled draws, and rhat / ess the split R-hat and the ESS of magi_summarize (the same split,
+ * Geyer truncation, max_lag and tau floor) applied to a derived series of the same shape:
+ *   rank[s]       (the pooled draws < y[s]) + ((the pooled draws == y[s], itself included) + 1) / 2: the 1-based average rank, exact in a
+ *                 double.  Equality is ==: -0.0 and +0.0 are tied.  The ranks are pooled over all S draws also when R is odd (the split then
+ *                 drops the middle draw; ArviZ ranks the split draws: an O(1/S) difference for odd R).
+ *   z[s]          Phi^-1((rank[s] - 3/8) / (S + 1/4)), Phi^-1 the inverse normal CDF in fp64 (a few ulp of max(1, |z|)).
+ *   z_folded[s]   the same transform of f[s] = |y[s] - med|, med the quantile of magi_summarize at p = 0.5.  For an even S the two middle
+ *                 draws lie equally far from med, and whether their folded values tie -- ranks (1.5, 1.5), (1, 2) or (2, 1) -- is decided
+ *                 in the last place of med: a property of the definition (ArviZ's too).  Draws that differ in their last places, such as
+ *                 a natural-scale transform evaluated by another library, can so move the folded leg of rhat_rank (by 8e-5 at S = 1000
+ *                 in profiles/r20_exp_rank.json); for an odd S med is a draw and nothing of the kind happens.
+ *   ess_bulk      ess(z).
+ *   rhat_rank     max(rhat(z), rhat(z_folded)); NaN when either is NaN.
+ *   ess_tail      min(ess(I_lo), ess(I_hi)), I_p[s] = 1 if y[s] <= v[floor((S - 1) p)] else 0 with p = tail_prob for I_lo and 1 - tail_prob
+ *                 (formed in fp64) for I_hi: the lower order statistic stands where ArviZ interpolates the quantile.  NaN when either leg is
+ *                 NaN, which it is when its indicator is a constant column.
+ * All three are NaN for a constant column and when R < 4.  A series without a split R-hat has no ESS either: the constant series, and the
+ * series whose split chains are all one constant while the dropped middle draw of an odd R differs (there magi_summarize's ess is that of
+ * tau at its floor).  A column with a non-finite draw has NaN everywhere (rank, z, z_folded too) and
+ * counts in *n_nonfinite.  rhat_rank, ess_bulk, ess_tail [K]; rank, z, z_folded [C][R][K] (for rank plots; the legs of rhat_rank are
+ * magi_summarize's rhat of the z and z_folded returned here bit for bit, and so is ess_bulk its ess of z -- with one deviation from "the
+ * ess of magi_summarize applied to z": where that series has no split R-hat, the rule above returns NaN and magi_summarize the ess of tau at
+ * its floor); n_nonfinite: each optional (NULL: not copied).  Results are bit-identical from run to run.  MAGI_E_BADARG (handle stays usable): as magi_summarize, and a tail_prob outside
+ * (0, 0.5] or not finite.  Needs a handle only for its device and stream.  Device memory of a call: the columns go in chunks of at most
+ * 64 MiB; a call holds the chunk, its sorted columns, one derived series and the staging of the upload (and of the series on their way
+ * down) -- four buffers of that size, three without the host's draws -- and four sets of split-chain means of at most 32 MiB: 384 MiB
+ * whatever K is, plus 3 K doubles of results and the chunk-local statistics of the four series, 36 doubles per column of a chunk (a
+ * chunk has min(K, 2^23 / (C R), 2^21) columns: 0.1 MB at the sampler's shapes, 576 MiB where K >= 2^21 columns have four draws each). */
+int magi_rank_diagnostics(magi_handle* h, int C, int R, int K, const double* draws, int max_lag, double tail_prob,
+                          double* rhat_rank, double* ess_bulk, double* ess_tail,
+                          double* rank, double* z, double* z_folded, int* n_nonfinite);
+
+/* The same three diagnostics of the sampler's device-resident post-burn-in samples, pooled over the chains [chain0, chain0 + n_sel): the
+ * blocks, layouts and natural-scale transforms of magi_sampler_summarize (X [N][D], sigma_sqs [D], thetas [P]; a group member's own bounds,
+ * supports and fixed variances); *n_nonfinite counts the columns of all three.  Every output is optional.  MAGI_E_STATE / MAGI_E_BADARG as
+ * magi_sampler_summarize (sampler initialised, every selected chain finished, the chain range inside the sampler's chains and inside one
+ * member of a group), then tail_prob as magi_rank_diagnostics.  Changes nothing of the handle's state. */
+int magi_sampler_rank_diagnostics(magi_handle* h, int chain0, int n_sel, int max_lag, double tail_prob,
+                                  double* X_rhat_rank, double* X_ess_bulk, double* X_ess_tail,
+                                  double* sig_rhat_rank, double* sig_ess_bulk, double* sig_ess_tail,
+                                  double* th_rhat_rank, double* th_ess_bulk, double* th_ess_tail,
+                                  int* n_nonfinite);
 
 /* ---- pointwise log-likelihood, WAIC and PSIS-LOO ----------------------------------------------- */
 

@@ -352,13 +352,16 @@ class MAGI_v2:
                 n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[int]] = None,
                 stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
                 family_chains: Optional[int] = None, summary: bool = False, keep_samples: bool = True, adapt_metric: bool = False,
-                theta_support=None, theta_prior=None, sigma_sq_prior=None, obs_link=None, obs_weight=None, elpd: bool = False, ppc: bool = False):
+                theta_support=None, theta_prior=None, sigma_sq_prior=None, obs_link=None, obs_weight=None, elpd: bool = False, ppc: bool = False,
+                rank_diagnostics: bool = False):
         """magi_v2.py:286-425.  Returns the reference's results dictionary; with n_chains > 1 every
         sample array gains a leading chain axis.  ``family_chains``: in a job sharded over GPUs, the largest per-GPU share
         (shard.family_chains_for) -- every rank then samples with the same kernel family whatever its own share.
         ``summary=True`` adds ``results["summary"]``: the posterior summaries and convergence diagnostics of all chains pooled, computed
         on the GPU from the device-resident samples (``posterior_summary``, which also takes other ``probs`` / ``max_lag``).  ``keep_samples=False`` (only with ``summary=True``) skips
         the download of the draws: ``X_samps``, ``sigma_sqs_samps``, ``thetas_samps`` and ``sample_results`` are then None.
+        ``rank_diagnostics=True`` (with ``summary=True``): each block of the summary gains ``rhat_rank``, ``ess_bulk`` and ``ess_tail``, the
+        rank-normalised diagnostics of ``posterior_summary(rank=True)``, and one warning names the columns beyond their thresholds.
         ``adapt_metric=True`` (the reference, like TFP's NoUTurnSampler, has the identity metric only): a per-chain diagonal mass matrix is
         adapted during the ``int(0.8 * num_burnin_steps)`` adaptation transitions over Stan's windows (``host.warmup_schedule``), dual
         averaging restarting after each window; ``results["metric"]`` = dict(inv_mass_X, inv_mass_sigma_pre, inv_mass_theta_pre: the
@@ -391,6 +394,8 @@ class MAGI_v2:
         Many datasets on one GPU: ``predict_many``."""
         if not keep_samples and not (summary or elpd or ppc):
             raise ValueError("keep_samples=False needs summary=True, elpd=True or ppc=True: the call would return nothing of the posterior")
+        if rank_diagnostics and not summary:
+            raise ValueError("rank_diagnostics=True adds its keys to results['summary']: it needs summary=True")
         sigma_sqs_LB, sig_pre0, th_pre0 = self._predict_prepare(sigma_sqs_LB, family_chains, theta_support, theta_prior, sigma_sq_prior, obs_link, obs_weight)
         eng = self.engine
         if seed is None:                 # the reference calls sample_chain unseeded (magi_v2.py:389-395)
@@ -421,21 +426,29 @@ class MAGI_v2:
             mX, ms, mt = eng.sampler_metric()
             results["metric"] = {"inv_mass_X": sq(mX), "inv_mass_sigma_pre": sq(ms), "inv_mass_theta_pre": sq(mt), "windows": windows}
         if summary:
-            results["summary"] = _warn_if_stuck(self.posterior_summary())
+            results["summary"] = _warn_if_stuck(self.posterior_summary(rank=rank_diagnostics))
+            if rank_diagnostics:
+                host.warn_rank_diagnostics(results["summary"], n_chains)
         if elpd:
             results["elpd"] = self.posterior_elpd()
         if ppc:
             results["ppc"] = self.posterior_predictive(seed=seed)
         return results
 
-    def posterior_summary(self, probs=DEFAULT_PROBS, max_lag: int = 0):
+    def posterior_summary(self, probs=DEFAULT_PROBS, max_lag: int = 0, rank: bool = False, tail_prob: float = 0.05):
         """Posterior summaries and convergence diagnostics of the last ``predict``, all its chains pooled, computed on the GPU from the
         samples the sampler left there (MagiEngine.sampler_summary): dict(X, sigma_sqs, thetas, probs, n_nonfinite), where X [N, D],
         sigma_sqs [D] and thetas [P] each hold mean, sd (ddof = 1), quantiles [len(probs), ...], rhat (split), ess and mcse_mean.  What the
-        reference's notebooks compute on the host as ``X_samps.mean(axis=0)`` and ``np.quantile(X_samps, [0.025, 0.975], axis=0)``."""
+        reference's notebooks compute on the host as ``X_samps.mean(axis=0)`` and ``np.quantile(X_samps, [0.025, 0.975], axis=0)``.
+        ``rank=True`` adds to each of the three blocks ``rhat_rank``, ``ess_bulk`` and ``ess_tail``: the rank-normalised split R-hat, bulk
+        ESS and tail ESS (at ``tail_prob``) of Vehtari et al. (2021), what Stan, ``posterior`` and ArviZ print
+        (MagiEngine.sampler_rank_diagnostics; include/magi_hip.h has the definitions).  Without it the dictionary is as before."""
         if not getattr(self, "_predicted", False):
             raise RuntimeError("posterior_summary summarises the samples of the last predict: run predict first")
-        return self.engine.sampler_summary(probs=probs, max_lag=max_lag)
+        out = self.engine.sampler_summary(probs=probs, max_lag=max_lag)
+        if rank:
+            host.merge_rank_diagnostics(out, self.engine.sampler_rank_diagnostics(max_lag=max_lag, tail_prob=tail_prob))
+        return out
 
     @staticmethod
     def _posterior_at_result(r, derivative, return_draws):
@@ -719,7 +732,7 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
                  n_chains: int = 1, seed: Optional[int] = None, chain_ids: Optional[Sequence[Sequence[int]]] = None,
                  stale_cache: bool = True, anneal: bool = True, max_tree_depth: int = 10, step_size: float = 0.1,
                  summary: bool = False, keep_samples: bool = True, theta_support=None, theta_prior=None, sigma_sq_prior=None,
-                 obs_link=None, obs_weight=None, elpd: bool = False, posterior_at=None, ppc: bool = False):
+                 obs_link=None, obs_weight=None, elpd: bool = False, posterior_at=None, ppc: bool = False, rank_diagnostics: bool = False):
     """``predict`` for several models (after their ``initial_fit``) at once.  Models of one library, device and problem shape are sampled
     as one problem group on their GPU -- one captured graph, one kernel pair per leapfrog slot for all their chains -- and the others by
     their own ``predict``.  ``sigma_sqs_LB``: None (each model's default) or one entry per model; ``chain_ids``: None (0 .. n_chains - 1
@@ -734,9 +747,12 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
     model, a grouped model's from its own chains and observation model.  ``posterior_at``: None, or times t_new [T]: adds
     ``results["posterior_at"]`` = that model's ``MAGI_v2.posterior_at(t_new)`` (a grouped model's through the group's handle and its
     member index, from its own chains, matrices and mu); legal with ``keep_samples=False``.  ``ppc`` as in ``predict``: one
-    ``results["ppc"]`` per model, a grouped model's from its own chain range and observation model."""
+    ``results["ppc"]`` per model, a grouped model's from its own chain range and observation model.  ``rank_diagnostics`` as in ``predict``
+    (with ``summary=True``): a grouped model's from its own chains."""
     if not keep_samples and not (summary or elpd or ppc or posterior_at is not None):
         raise ValueError("keep_samples=False needs summary=True, elpd=True, ppc=True or posterior_at: the call would return nothing of the posterior")
+    if rank_diagnostics and not summary:
+        raise ValueError("rank_diagnostics=True adds its keys to results['summary']: it needs summary=True")
     models = list(models)
     n = len(models)
     lbs = [None] * n if sigma_sqs_LB is None else list(sigma_sqs_LB)
@@ -777,7 +793,8 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
             k = grp[0]
             only_at = not (keep_samples or summary or elpd or ppc)          # (predict wants a reason of its own to drop the draws)
             out[k] = models[k].predict(num_results, num_burnin_steps, lbs[k], verbose, chain_ids=ids[k], summary=summary or only_at, keep_samples=keep_samples,
-                                        theta_support=sups[k], theta_prior=tpri[k], sigma_sq_prior=spri[k], obs_link=olnk[k], obs_weight=owts[k], elpd=elpd, ppc=ppc, **kw)
+                                        theta_support=sups[k], theta_prior=tpri[k], sigma_sq_prior=spri[k], obs_link=olnk[k], obs_weight=owts[k], elpd=elpd, ppc=ppc,
+                                        rank_diagnostics=rank_diagnostics, **kw)
             if only_at:
                 del out[k]["summary"]
             if posterior_at is not None:
@@ -803,6 +820,9 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
                 print(f"Finished sampling in {minutes} minutes.")
             diag = g.sampler_diag()
             summaries = [g.sampler_summary(member=j) for j in range(len(grp))] if summary else None
+            if rank_diagnostics:
+                for j in range(len(grp)):
+                    host.merge_rank_diagnostics(summaries[j], g.sampler_rank_diagnostics(member=j))
             elpds = [g.sampler_elpd(member=j, loo=host.elpd_wants_loo(n_chains * num_results))
                      for j in range(len(grp))] if elpd else None
             ppcs = [g.sampler_ppc(member=j, seed=seed) for j in range(len(grp))] if ppc else None
@@ -817,6 +837,8 @@ def predict_many(models: Sequence[MAGI_v2], num_results: int = 1000, num_burnin_
             out[k] = models[k]._predict_results(*part, dk, prep[k][0], seed, n_chains, num_burnin_steps, minutes)
             if summary:
                 out[k]["summary"] = _warn_if_stuck(summaries[j])
+                if rank_diagnostics:
+                    host.warn_rank_diagnostics(summaries[j], n_chains)
             if elpd:
                 out[k]["elpd"] = models[k]._elpd_on_scale(elpds[j], "data")
             if ppc:

@@ -48,6 +48,12 @@ __device__ __forceinline__ double wave_bsum(double v) {
     return v;
 }
 
+// where column j of a block goes in the caller's arrays: the X block is walked in the samples' order [D][N] and reported in the host
+// layout [N][D]
+__device__ __forceinline__ long long out_index(int mode, long long j, int N, int D) {
+    return mode == MODE_X ? (j % N) * (long long)D + j / N : j;
+}
+
 // order-preserving key of a finite double and its inverse
 __device__ __forceinline__ unsigned long long to_key(double v) {
     const unsigned long long b = (unsigned long long)__double_as_longlong(v);
@@ -137,3 +143,7 @@ void magi_colstats_take(MagiScratch& s, MagiColStats& st, int C, int R, long lon
                         bool want_ess, bool want_quant);
 int magi_colstats_chunk(magi_handle* h, const char* who, const MagiColStats& st, const double* dchunk, int nc, long long k0, int mode, int N, int D);
 void magi_colstats_down(MagiScratch& s, MagiColStats& st, double* mean, double* sd, double* quant, double* rhat, double* ess, double* mcse);
+// summary.hip: k_sum_gather on nc columns of S rows (column j of row r at src[r ld + j]) -> chunk[nc][S], on the natural scale of `mode`
+// (lb0: the block's first column in lb / tsup / prior), for the units that work on the same chunks (rank.hip)
+int magi_sum_gather(magi_handle* h, int S, int nc, const double* src, long long ld, int mode, int lb0, const colstat::SumLB& lb, const double2* tsup,
+                    const double4* prior, double* chunk);

@@ -50,12 +50,6 @@ __global__ __launch_bounds__(G_TILE * 4) void k_sum_gather(int S, int nc, const 
         if (c0 + c < nc && r0 + tx < S) chunk[(size_t)(c0 + c) * S + r0 + tx] = tile[tx][c];
 }
 
-// where column j of a block goes in the caller's arrays: the X block is walked in the samples' order [D][N] and reported in the host
-// layout [N][D]
-__device__ __forceinline__ long long out_index(int mode, long long j, int N, int D) {
-    return mode == MODE_X ? (j % N) * (long long)D + j / N : j;
-}
-
 // first row of split chain m in a column of C chains x R draws (n = R / 2: an odd R drops the middle draw)
 __device__ __forceinline__ int split_start(int m, int R, int n) { return (m >> 1) * R + ((m & 1) ? R - n : 0); }
 
@@ -344,9 +338,7 @@ int summarize_block(magi_handle* h, const char* who, const double* dsrc, const d
         if (hsrc)
             s.note(hipMemcpy2DAsync(stage, (size_t)nc * sizeof(double), hsrc + c0, (size_t)K * sizeof(double), (size_t)nc * sizeof(double), S,
                                     hipMemcpyHostToDevice, h->stream));
-        if (s.ok())
-            s.note(magi_launch(h, "k_sum_gather: ", k_sum_gather, dim3((unsigned)((S + G_TILE - 1) / G_TILE), (unsigned)((nc + G_TILE - 1) / G_TILE)),
-                               dim3(G_TILE, 4), h->stream, (int)S, nc, src, sld, mode, (int)c0, lb, tsup, prior, chunk));
+        if (s.ok()) s.note(magi_sum_gather(h, (int)S, nc, src, sld, mode, (int)c0, lb, tsup, prior, chunk));
         if (s.ok()) s.note(magi_colstats_chunk(h, who, st, chunk, nc, (long long)c0, mode, N, D));
     }
     magi_colstats_down(s, st, o.mean, o.sd, o.quant, o.rhat, o.ess, o.mcse);
@@ -364,6 +356,12 @@ int magi_ode_stats(magi_handle* h, int S, int S_pad, int R, const double* trj, c
 int magi_transpose(magi_handle* h, int rows, int cols, const double* in, size_t ld_in, double* out, size_t ld_out) {
     return magi_launch(h, "k_transpose: ", k_transpose, dim3((unsigned)((cols + G_TILE - 1) / G_TILE), (unsigned)((rows + G_TILE - 1) / G_TILE)), dim3(G_TILE, 4),
                        h->stream, rows, cols, in, ld_in, out, ld_out);
+}
+
+int magi_sum_gather(magi_handle* h, int S, int nc, const double* src, long long ld, int mode, int lb0, const SumLB& lb, const double2* tsup,
+                    const double4* prior, double* chunk) {
+    return magi_launch(h, "k_sum_gather: ", k_sum_gather, dim3((unsigned)((S + G_TILE - 1) / G_TILE), (unsigned)((nc + G_TILE - 1) / G_TILE)), dim3(G_TILE, 4),
+                       h->stream, S, nc, src, ld, mode, lb0, lb, tsup, prior, chunk);
 }
 
 int magi_ode_transpose(magi_handle* h, int S, int S_pad, int R, const double* trj, double* out) {

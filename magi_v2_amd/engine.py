@@ -97,6 +97,8 @@ _SYMBOLS = {
                                           C.c_int, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip]),
     "magi_summarize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int] + [_dp] * 6 + [_ip]),
     "magi_sampler_summarize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int] + [_dp] * 18 + [_ip]),
+    "magi_rank_diagnostics": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double] + [_dp] * 6 + [_ip]),
+    "magi_sampler_rank_diagnostics": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_double] + [_dp] * 9 + [_ip]),
     "magi_matern_cross": (C.c_int, [C.c_void_p, _dp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_double, _dp, _dp]),
     "magi_gp_predict": (C.c_int, [C.c_void_p, _dp, C.c_int, C.c_int, _dp, _dp, C.c_double, _dp, C.c_int, _dp, C.c_int, _dp] + [_dp] * 4),
     "magi_sampler_gp_predict": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, C.c_double, C.c_int, _dp, C.c_int, _dp, C.c_int]
@@ -111,6 +113,8 @@ _SYMBOLS = {
 
 SUMMARY_STATS = ("mean", "sd", "quantiles", "rhat", "ess", "mcse_mean")       # the order of the six outputs in include/magi_hip.h
 DEFAULT_PROBS = (0.025, 0.5, 0.975)
+RANK_STATS = ("rhat_rank", "ess_bulk", "ess_tail")       # the order of the three outputs of magi_rank_diagnostics, and of its optional series
+RANK_SERIES = ("rank", "z", "z_folded")
 
 
 def _summary_arrays(shape, n_q):
@@ -360,6 +364,42 @@ class MagiEngine:
                                                      *[_ptr(o) for b in ("X", "sigma_sqs", "thetas") for o in blocks[b]], C.byref(nf)))
         out = {b: dict(zip(SUMMARY_STATS, arrs)) for b, arrs in blocks.items()}
         out.update(probs=probs, n_nonfinite=int(nf.value))
+        return out
+
+    def rank_diagnostics(self, draws, max_lag=0, tail_prob=0.05, return_z=False):
+        """Rank-normalised split R-hat, bulk ESS and tail ESS (Vehtari et al. 2021) of ``draws`` [C chains, R draws, ...] on the device
+        (magi_rank_diagnostics; the definitions are in include/magi_hip.h): dict(rhat_rank, ess_bulk, ess_tail -- each of the trailing
+        shape --, n_nonfinite).  ``tail_prob`` in (0, 0.5]: the tail ESS is that of the lower and upper ``tail_prob`` quantile indicators.
+        ``return_z=True`` adds rank, z and z_folded, each of the shape of ``draws``: the pooled average ranks and the normal scores the
+        diagnostics are the ``summarize`` rhat / ess of (for rank plots)."""
+        draws = _f64(draws)
+        if draws.ndim < 2:
+            raise ValueError(f"expected draws of shape (chains, draws, ...), got {draws.shape}")
+        n_c, n_r, shape = draws.shape[0], draws.shape[1], draws.shape[2:]
+        K = int(np.prod(shape, dtype=np.int64))
+        outs = [np.empty(shape) for _ in RANK_STATS]
+        series = [np.empty(draws.shape) if return_z else None for _ in RANK_SERIES]
+        nf = C.c_int32(0)
+        self._check(self._lib.magi_rank_diagnostics(self._h, n_c, n_r, K, _ptr(draws), int(max_lag), float(tail_prob), *[_ptr(o) for o in outs],
+                                                    *[None if a is None else _ptr(a) for a in series], C.byref(nf)))
+        out = dict(zip(RANK_STATS, outs))
+        if return_z:
+            out.update(zip(RANK_SERIES, series))
+        out["n_nonfinite"] = int(nf.value)
+        return out
+
+    def sampler_rank_diagnostics(self, chains=None, member=None, max_lag=0, tail_prob=0.05):
+        """``rank_diagnostics`` of the finished sampler run, computed on the device-resident samples (magi_sampler_rank_diagnostics): no
+        draw is copied to the host.  Returns dict(X, sigma_sqs, thetas, n_nonfinite); the three blocks, on the natural scale as in
+        ``sampler_summary``, each dict(rhat_rank, ess_bulk, ess_tail) of shapes [N, D], [D] and [P].  ``chains`` / ``member`` as in
+        ``sampler_summary``."""
+        chain0, n_sel = self._chain_range(chains, member)
+        blocks = {b: [np.empty(shape) for _ in RANK_STATS] for b, shape in (("X", (self.N, self.D)), ("sigma_sqs", (self.D,)), ("thetas", (self.P,)))}
+        nf = C.c_int32(0)
+        self._check(self._lib.magi_sampler_rank_diagnostics(self._h, chain0, n_sel, int(max_lag), float(tail_prob),
+                                                            *[_ptr(o) for b in ("X", "sigma_sqs", "thetas") for o in blocks[b]], C.byref(nf)))
+        out = {b: dict(zip(RANK_STATS, arrs)) for b, arrs in blocks.items()}
+        out["n_nonfinite"] = int(nf.value)
         return out
 
     def matern_cross(self, t_new, I, phi1, phi2, nu=2.01):

@@ -514,6 +514,47 @@ def ppc_result(comp, D, mean, sd, quantiles, pit, pval, n_T_excluded, n_nonfinit
 
 
 # --------------------------------------------------------------------------------------------
+# rank-normalised diagnostics: the host side (the diagnostics themselves are the device's, csrc/rank.hip)
+# --------------------------------------------------------------------------------------------
+RANK_KEYS = ("rhat_rank", "ess_bulk", "ess_tail")
+RANK_BLOCKS = ("X", "sigma_sqs", "thetas")
+RHAT_RANK_MAX = 1.01              # the thresholds of Vehtari et al. (2021): rhat_rank above 1.01,
+ESS_PER_CHAIN_MIN = 100.0         # a bulk or tail ESS under 100 per chain
+
+
+def merge_rank_diagnostics(summary, rank):
+    """Adds the three keys of every block of ``rank`` (MagiEngine.sampler_rank_diagnostics) to the same block of ``summary``
+    (MagiEngine.sampler_summary), in place; returns ``summary``."""
+    for b in RANK_BLOCKS:
+        for k in RANK_KEYS:
+            summary[b][k] = rank[b][k]
+    return summary
+
+
+def rank_diagnostics_flags(summary, n_chains: int):
+    """Per block of a summary that carries the rank diagnostics: the number of columns with rhat_rank > 1.01, ess_bulk < 100 n_chains and
+    ess_tail < 100 n_chains (a NaN diagnostic -- a constant column, fewer than four draws -- is not counted)."""
+    need = ESS_PER_CHAIN_MIN * n_chains
+    with np.errstate(invalid="ignore"):
+        return {b: {"rhat_rank": int(np.sum(np.asarray(summary[b]["rhat_rank"]) > RHAT_RANK_MAX)),
+                    "ess_bulk": int(np.sum(np.asarray(summary[b]["ess_bulk"]) < need)),
+                    "ess_tail": int(np.sum(np.asarray(summary[b]["ess_tail"]) < need))} for b in RANK_BLOCKS}
+
+
+def warn_rank_diagnostics(summary, n_chains: int):
+    """One warning that names, per block, how many columns miss a threshold; none when every column passes.  Called only where the
+    rank diagnostics were asked for.  Returns the counts of ``rank_diagnostics_flags``."""
+    flags = rank_diagnostics_flags(summary, n_chains)
+    parts = [f"{b}: {f['rhat_rank']} with rhat_rank > {RHAT_RANK_MAX}, {f['ess_bulk']} with ess_bulk and {f['ess_tail']} with ess_tail < "
+             f"{ESS_PER_CHAIN_MIN * n_chains:g}" for b, f in flags.items() if any(f.values())]
+    if parts:
+        import warnings
+        warnings.warn("rank diagnostics: columns beyond the thresholds of Vehtari et al. (2021) -- " + "; ".join(parts)
+                      + " (run longer chains, or more of them)")
+    return flags
+
+
+# --------------------------------------------------------------------------------------------
 # drifts
 # --------------------------------------------------------------------------------------------
 

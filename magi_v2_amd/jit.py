@@ -17,7 +17,7 @@ from . import build as _build
 
 # MAGI_JIT_CACHE relocates the cache (e.g. when the package directory is read-only)
 CACHE = os.environ.get("MAGI_JIT_CACHE") or os.path.join(_build.HERE, "jit_cache")
-_DRIFT_FREE = ("build.hip", "pack.hip", "summary.hip", "elpd.hip", "gp.hip", "ppc.hip")       # translation units without drift-dependent code
+_DRIFT_FREE = ("build.hip", "pack.hip", "summary.hip", "elpd.hip", "gp.hip", "ppc.hip", "rank.hip")       # translation units without drift-dependent code
 
 
 def _hipcc() -> str:
