@@ -467,6 +467,63 @@ int magi_ode_solve_adaptive(magi_handle* h, int drift_id, int P, int S,
                             double* traj, double* mean, double* sd, int* status, int* reason,
                             int* n_accepted, int* n_rejected, int* n_failed);
 
+/* ---- forward sensitivities and Fisher information ---------------------------------------------- */
+
+/* Forward sensitivities of the trajectories of magi_ode_solve, and the Fisher information of a list of observations, per draw (unit
+ * csrc/sens.hip): which parameters and initial states the solution depends on, through which components and times.  x0, theta, T,
+ * t_out, substeps, traj, status and n_failed mean what they mean in magi_ode_solve (status looks at the state alone).
+ * Columns: cols[c] in [0, P + D), distinct; q < P is theta_q, q >= P is component q - P of x0.  One lane per (draw, column).
+ * Scheme: the variational equations beside the state, on the RK4 steps of magi_ode_solve restated: h = (t[j+1] - t[j]) / substeps,
+ * stages at s, s + h/2, s + h/2, s + h, x += h/6 (k1 + 2 k2 + 2 k3 + k4).  With y_i = x + a_i h k_{i-1} the stage state and
+ * z_i = s + a_i h l_{i-1} the stage sensitivity (a = 0, 1/2, 1/2, 1),
+ *   l_i[d] = sum_k J_x[d][k](t_i, y_i) z_i[k] (k ascending) + dF[d](t_i, y_i),    s += h/6 (l1 + 2 l2 + 2 l3 + l4),
+ * J_x = df/dx; dF = df/dtheta_q for q < P with s(t_0) = 0, and dF = 0 for q = P + e with s(t_0) = the unit vector e.  Rows of J_x and
+ * df/dtheta come from DriftT<>::jt with unit vectors, at the stage's own y and time.  This is the exact derivative of the discrete map
+ * that magi_ode_solve computes, not an approximation of it.  relative != 0: the stored value is s times the draw's own theta_q or x0
+ * component (one multiply; the sensitivity to the log parameter); the integration itself is not scaled.
+ * sens[S][T][D][n_col]; sens_mean / sens_sd [T][D][n_col]: mean and sd (ddof = 1) over the draws with status 0, as magi_ode_solve's.
+ * Fisher information of n_obs observations (j_k, d_k, w_k) = (obs_j, obs_comp, obs_weight; obs_weight NULL: 1), links g_d = link[d]
+ * (MAGI_LINK_*; NULL: identity) and the draw's variances sigma_sq[s][d] on the link's scale:
+ *   F[s][a][b] = sum_k ((w_k / sigma_sq[s][d_k]) g'(x)^2) sens[s][j_k][d_k][a] sens[s][j_k][d_k][b],   x = traj[s][j_k][d_k],
+ * g' = 1 (identity), 1 / x (log), 0.5 / sqrt(x) (sqrt); k ascending, no atomics; computed for a <= b and mirrored; the sens are the stored
+ * ones (scaled when relative).  A draw with status != 0 or with a non-finite entry has NaN in all of F[s] and counts in
+ * *n_fim_excluded; fim_mean[n_col][n_col] is the mean over the other draws in the fixed order of magi_ode_solve's mean.  n_obs = 0: no
+ * Fisher information (fim, fim_mean, n_fim_excluded are not written).
+ * traj, sens, sens_mean, sens_sd, fim [S][n_col][n_col], fim_mean, status, n_failed, n_fim_excluded: each optional.
+ * MAGI_E_BADARG (handle stays usable): the cases of magi_ode_solve; n_col outside [1, P + D], cols NULL, a column out of range or
+ * repeated; roundup(S, 64) T D n_col > 2^28; n_obs < 0 or > 2^24; with n_obs > 0: obs_j or obs_comp NULL, an obs_j outside [0, T), an
+ * obs_comp outside [0, D), a weight or sigma_sq that is not a finite number > 0, sigma_sq NULL, a link that is none of MAGI_LINK_*.
+ * Needs a handle only for its device and stream: no matrices, no problem; a group handle is fine. */
+int magi_ode_sensitivities(magi_handle* h, int drift_id, int P, int S,
+                           const double* x0, const double* theta,
+                           int T, const double* t_out, int substeps,
+                           int n_col, const int* cols, int relative,
+                           int n_obs, const int* obs_j, const int* obs_comp, const double* obs_weight /* NULL: 1 */,
+                           const double* sigma_sq /* [S][D] */, const int* link /* [D] or NULL */,
+                           double* traj, double* sens, double* sens_mean, double* sens_sd,
+                           double* fim, double* fim_mean, int* status, int* n_failed, int* n_fim_excluded);
+
+/* magi_ode_sensitivities for the finished run's device-resident samples of the chains [chain0, chain0 + n_sel), every `thin`-th result
+ * of each (results 0, thin, 2 thin, ...: S = n_sel ceil(num_results / thin) draws, chain-major): no draw crosses to the host first.  Draw
+ * inputs: x0 = the draw's X at grid row start_index; theta on its natural scale under the handle's supports (magi_set_theta_support);
+ * sigma_sq exactly what magi_sampler_ppc forms (softplus(sig_pre) + LB, or the MAGI_PRIOR_FIXED constant); links and weights are those of
+ * the handle's observation model (magi_set_obs_model) -- on a group handle all of these are the member's own.  The drift is the
+ * problem's.  grid_out[N]: the index in t_out of grid point i, or -1 (NULL: no Fisher information).  The observation list is the observed
+ * entries e = d N + i in ascending e with grid_out[i] >= 0, as (grid_out[i], d, weight); *n_obs_used and obs_index[n_obs_used] (room for
+ * N D) return it as magi_sampler_elpd does.  x0_out [S][D], theta_out [S][P], sigma_sq_out [S][D]: the draws as they were used.
+ * The result is bit for bit what magi_ode_sensitivities returns for those draws, that list and the same t_out, substeps, cols and
+ * relative.  Every output is optional.  State and argument errors: those of magi_sampler_summarize (MAGI_E_STATE unless the sampler is
+ * initialised and the chains have finished; MAGI_E_BADARG for a chain range outside the sampler's or across two members of a group) and
+ * those of magi_ode_sensitivities; MAGI_E_BADARG also for thin < 1, a start_index outside [0, N), a grid_out entry outside [-1, T).
+ * Nothing of the handle's state changes: a call between two magi_sampler_runs does not disturb the chains. */
+int magi_sampler_sensitivities(magi_handle* h, int chain0, int n_sel, int thin, int start_index,
+                               int T, const double* t_out, int substeps, const int* grid_out,
+                               int n_col, const int* cols, int relative,
+                               double* traj, double* sens, double* sens_mean, double* sens_sd,
+                               double* fim, double* fim_mean, int* status, int* n_failed, int* n_fim_excluded,
+                               int* n_obs_used, int* obs_index,
+                               double* x0_out, double* theta_out, double* sigma_sq_out);
+
 /* ---- posterior summaries and convergence diagnostics ----------------------------------------- */
 
 /* Summaries of K scalar columns of C chains x R draws (unit csrc/summary.hip; what the reference's notebooks do on the host with

@@ -679,6 +679,51 @@ class MAGI_v2:
             res[key] = out[key].reshape(kept)
         return res
 
+    def posterior_sensitivities(self, t_out=None, start_index: int = 0, substeps: int = 4, thin: int = 1, wrt=("theta", "x0"),
+                                relative: bool = False, fisher: bool = True, return_draws: bool = False):
+        """Which parameters do the data determine, and through which states and times?  Forward sensitivities of the fitted ODE for every
+        draw of the last ``predict`` (all chains pooled, every ``thin``-th), and the Fisher information of the fitted observations,
+        computed on the GPU from the device-resident samples (MagiEngine.sampler_sensitivities; include/magi_hip.h has the scheme): legal
+        after ``keep_samples=False``.  Draw k starts at its X at grid row ``start_index`` with its theta and is integrated with the RK4
+        of ``posterior_trajectories``; the sensitivities are the exact derivatives of that discrete solution.  ``t_out``: default
+        ``I[start_index:]``; the observations used are those at grid points whose time is exactly an entry of ``t_out``.  ``wrt``: "theta"
+        and / or "x0", in that order of columns.  ``relative``: sensitivities to the log parameters.
+        Returns dict(t [T], names [Q] (theta names, then x0 names), sens: dict(mean, sd [T, D, Q] over the draws whose trajectory stayed
+        finite, plus draws [S, T, D, Q] with ``return_draws``), fim_mean [Q, Q] and report (``host.fisher_report`` with post_sd = the
+        posterior sd of theta and of X[start_index] from ``posterior_summary``, divided by |posterior mean| under ``relative``) -- both None
+        without ``fisher`` or when no observation is used -- status [S], n_failed, n_fim_excluded, n_obs_used)."""
+        if not getattr(self, "_predicted", False):
+            raise RuntimeError("posterior_sensitivities works from the samples of the last predict: run predict first")
+        wrt = (wrt,) if isinstance(wrt, str) else tuple(wrt)
+        if not wrt or any(w not in ("theta", "x0") for w in wrt) or len(set(wrt)) != len(wrt):
+            raise ValueError(f"wrt: some of ('theta', 'x0'), got {wrt}")
+        P, D = self.D_thetas, self.D
+        cols = ([p for p in range(P)] if "theta" in wrt else []) + ([P + d for d in range(D)] if "x0" in wrt else [])
+        names = [f"theta[{p}]" for p in range(P)] + [f"x0[{d}]" for d in range(D)]
+        I = np.asarray(self.I, dtype=np.float64).reshape(-1)
+        t = I[start_index:] if t_out is None else np.asarray(t_out, dtype=np.float64).reshape(-1)
+        assert t[0] == I[start_index], "t_out must start at I[start_index]"
+        where = {float(v): j for j, v in enumerate(t)}
+        grid_out = np.array([where.get(float(v), -1) for v in I], dtype=np.int32) if fisher else None
+        r = self.engine.sampler_sensitivities(t, grid_out, start_index=start_index, thin=thin, substeps=substeps, wrt=cols, relative=relative,
+                                              return_draws=return_draws)
+        if r["n_failed"] > 0:
+            import warnings
+            warnings.warn(f"posterior_sensitivities: {r['n_failed']} of {r['status'].shape[0]} trajectories left the finite range (status > 0); "
+                          "means, sds and the Fisher information are over the others")
+        out = {"t": t, "names": [names[c] for c in cols], "sens": {"mean": r["sens_mean"], "sd": r["sens_sd"]}, "fim_mean": None, "report": None,
+               "status": r["status"], "n_failed": r["n_failed"], "n_fim_excluded": r.get("n_fim_excluded", 0), "n_obs_used": r["n_obs_used"]}
+        if return_draws:
+            out["sens"]["draws"] = r["sens"]
+        if fisher and r["n_obs_used"] > 0:
+            summ = self.engine.sampler_summary(probs=())
+            sd = np.concatenate([summ["thetas"]["sd"], summ["X"]["sd"][start_index]])
+            if relative:                                     # the sd of log(parameter), to first order
+                sd = sd / np.abs(np.concatenate([summ["thetas"]["mean"], summ["X"]["mean"][start_index]]))
+            out["fim_mean"] = r["fim_mean"]
+            out["report"] = host.fisher_report(r["fim_mean"], out["names"], post_sd=sd[cols])
+        return out
+
     def update_kernel_matrices(self, I_new, phi1s_new, phi2s_new):
         """magi_v2.py:433-462: new grid + hyper-parameters -> rebuild every component's matrices."""
         self.I = np.asarray(I_new, dtype=np.float64).reshape(-1, 1)

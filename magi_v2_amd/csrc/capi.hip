@@ -242,6 +242,8 @@ void magi_options_from_env(MagiOptions& o) {
 //                                                                     the call's own (MagiScratch) and the noise has a Philox stream of its own
 //   magi_sampler_rank_diagnostics, magi_rank_diagnostics    none      they read the samples and the member's bounds, supports and priors in place;
 //                                                                     the scratch is the call's own (MagiScratch)
+//   magi_sampler_sensitivities, magi_ode_sensitivities      none      the first reads the samples, the problem's observations and the member's
+//                                                                     bounds, supports and priors in place; the scratch is the call's own (MagiScratch)
 //
 // "SAMPLER includes GRAPH" drops a graph that some of these calls could have kept (the log-posterior and timing calls, the end of
 // magi_sampler_profile, the budget exit).  That cannot be observed: a graph is replayed by magi_sampler_run alone, which needs sampler_ready,

@@ -30,16 +30,27 @@ int check_ode_common(magi_handle* h, const char* who, int drift_id, int S, const
     return magi_check_drift_id(h, drift_id);
 }
 
+// what depends on the drift: P, and the size of the largest device buffer, S_pad * T * D * width cells (width 1: the trajectories; the
+// sensitivities of sens.hip have one per column); *S_pad = roundup(S, MAGI_ODE_PAD)
+template <class DR>
+int check_ode_shape(magi_handle* h, const char* who, int P, int S, int T, int width, size_t* S_pad) {
+    const std::string me = std::string(who) + ": ";
+    if (P != DR::P) return magi_fail(h, MAGI_E_BADARG, me + "drift expects P=" + std::to_string(DR::P));
+    *S_pad = ((size_t)S + MAGI_ODE_PAD - 1) / MAGI_ODE_PAD * MAGI_ODE_PAD;
+    if (*S_pad * (size_t)T * DR::D * (size_t)width > ((size_t)1 << 28))
+        return magi_fail(h, MAGI_E_BADARG, me + "roundup(S, 64) * T * D" + (width > 1 ? " * n_col" : "") + " exceeds 2^28 (a 2 GiB device buffer)");
+    return MAGI_OK;
+}
+
 // launch(const OdeDev&) starts the integrator of drift DR on h->stream and returns magi_launch's code; extras: the integrator fills
 // reason, n_accepted, n_rejected, downloaded to the three host arrays that are not null
 template <class DR, class Launch>
 int ode_solve_host(magi_handle* h, const char* who, int P, int S, const double* x0, const double* theta, int T, const double* t_out, double* traj,
                    double* mean, double* sd, int* status, int* n_failed, bool extras, int* reason, int* n_accepted, int* n_rejected, Launch launch) {
     constexpr int D = DR::D;
-    const std::string me = std::string(who) + ": ";
-    if (P != DR::P) return magi_fail(h, MAGI_E_BADARG, me + "drift expects P=" + std::to_string(DR::P));
-    const size_t S_pad = ((size_t)S + MAGI_ODE_PAD - 1) / MAGI_ODE_PAD * MAGI_ODE_PAD, R = (size_t)T * D, cells = S_pad * R;
-    if (cells > ((size_t)1 << 28)) return magi_fail(h, MAGI_E_BADARG, me + "roundup(S, 64) * T * D exceeds 2^28 (a 2 GiB device buffer)");
+    size_t S_pad;
+    if (int rc = check_ode_shape<DR>(h, who, P, S, T, 1, &S_pad)) return rc;
+    const size_t R = (size_t)T * D, cells = S_pad * R;
     const size_t n_out = traj ? (size_t)S * R : 0, nx = (size_t)S * D, nth = (size_t)S * P, ni = (size_t)S * sizeof(int);
     MagiScratch s(h, who);
     double *dtrj, *dout /* the draws in host layout, only when asked for */, *dx, *dth, *dt, *dmean, *dsd;

@@ -95,6 +95,10 @@ _SYMBOLS = {
     "magi_ode_solve": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, _dp, _dp, _dp, _ip, _ip]),
     "magi_ode_solve_adaptive": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, C.c_double,
                                           C.c_int, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip]),
+    "magi_ode_sensitivities": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, _ip, C.c_int, C.c_int, _ip, _ip, _dp, _dp,
+                                         _ip, _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip]),
+    "magi_sampler_sensitivities": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _ip, C.c_int, _ip, C.c_int,
+                                             _dp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip, _dp, _dp, _dp]),
     "magi_summarize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int, _dp, C.c_int] + [_dp] * 6 + [_ip]),
     "magi_sampler_summarize": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int] + [_dp] * 18 + [_ip]),
     "magi_rank_diagnostics": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp, C.c_int, C.c_double] + [_dp] * 6 + [_ip]),
@@ -306,6 +310,112 @@ class MagiEngine:
         self._check(self._lib.magi_ode_solve(self._h, drift_id, P, S, _ptr(x0), _ptr(theta), T, _ptr(t_out), int(substeps), _ptr(traj),
                                              _ptr(mean), _ptr(sd), status.ctypes.data_as(_ip), C.byref(nf)))
         return {"trajectories": traj, "mean": mean, "sd": sd, "status": status[:S], "n_failed": int(nf.value)}
+
+    LINKS = {"identity": 0, "log": 1, "sqrt": 2}          # (MAGI_LINK_* of include/magi_hip.h)
+
+    def ode_sensitivities(self, x0, theta, t_out, substeps=4, wrt=None, relative=False, obs=None, return_draws=True, drift=None):
+        """Forward sensitivities of ``ode_solve``'s RK4 trajectories on the device (magi_ode_sensitivities; the scheme and the fixed orders
+        are stated in include/magi_hip.h): the exact derivative of the discrete map, for S draws at once.  x0 [S, D], theta [S, P], t_out,
+        substeps and drift as in ``ode_solve``.  ``wrt``: the columns, distinct indices in [0, P + D) -- q < P is theta_q, q >= P is
+        component q - P of x0; None: all P + D in that order.  ``relative``: every sensitivity times the draw's own theta_q or x0
+        component (the sensitivity to the log parameter).  ``obs``: None, or a dict(j [n] output indices, comp [n] components,
+        sigma_sq [S, D] the draws' variances on the link's scale, weight [n] or None, link [D] of "identity" / "log" / "sqrt" (or
+        MAGI_LINK_* codes) or None) -- the observations whose Fisher information F[s] = sum_k w_k / sigma_sq g'(x)^2 s_a s_b is formed per
+        draw.  Returns dict(trajectories [S, T, D] and sens [S, T, D, Q] (None without ``return_draws``), sens_mean, sens_sd [T, D, Q] over
+        the draws with status 0, status [S], n_failed, cols [Q]; with ``obs`` also fim [S, Q, Q] (None without ``return_draws``),
+        fim_mean [Q, Q] over the draws whose F is finite and whose status is 0, n_fim_excluded)."""
+        if drift is None:
+            drift = self.user_drift if self.user_drift is not None else getattr(self, "_problem_drift", None)
+            if drift is None:
+                raise ValueError("ode_sensitivities on the base library needs drift= (a built-in name) or a problem set before")
+        if isinstance(drift, str):
+            D, drift_id = DRIFT_SHAPES[drift][0], DRIFT_IDS[drift]
+        else:
+            D, drift_id = drift.D, drift.device_id
+        x0, theta = _f64(x0), _f64(theta)
+        S = x0.shape[0]
+        x0 = _f64(x0, (S, D))
+        if theta.ndim != 2 or theta.shape[0] != S:
+            raise ValueError(f"expected theta of shape ({S}, P), got {theta.shape}")
+        P = theta.shape[1]                                   # (a wrong P is the library's to refuse)
+        t_out = _f64(np.asarray(t_out, dtype=np.float64).reshape(-1))
+        T = t_out.shape[0]
+        cols = np.ascontiguousarray(np.arange(P + D) if wrt is None else np.asarray(wrt).reshape(-1), dtype=np.int32)
+        Q = cols.shape[0]
+        i32 = lambda a: None if a is None else a.ctypes.data_as(_ip)
+        n_obs, oj, oc, ow, sig, link = 0, None, None, None, None, None
+        if obs is not None:
+            oj = np.ascontiguousarray(np.asarray(obs["j"]).reshape(-1), dtype=np.int32)
+            oc = np.ascontiguousarray(np.asarray(obs["comp"]).reshape(-1), dtype=np.int32)
+            n_obs = oj.shape[0]
+            if oc.shape[0] != n_obs:
+                raise ValueError(f"obs: {n_obs} output indices for {oc.shape[0]} components")
+            ow = None if obs.get("weight") is None else _f64(np.asarray(obs["weight"], dtype=np.float64).reshape(-1), (n_obs,))
+            sig = None if obs.get("sigma_sq") is None else _f64(obs["sigma_sq"], (S, D))
+            if obs.get("link") is not None:
+                link = np.ascontiguousarray([self.LINKS.get(v, v) if isinstance(v, str) else int(v) for v in obs["link"]], dtype=np.int32)
+                if link.shape[0] != D:
+                    raise ValueError(f"obs: expected {D} links, got {link.shape[0]}")
+        fisher = n_obs > 0
+        traj = np.empty((S, T, D)) if return_draws else None
+        sens = np.empty((S, T, D, Q)) if return_draws else None
+        mean, sd = np.empty((T, D, Q)), np.empty((T, D, Q))
+        fim = np.empty((S, Q, Q)) if (fisher and return_draws) else None
+        fim_mean = np.empty((Q, Q)) if fisher else None
+        status, nf, nex = np.zeros(max(S, 1), dtype=np.int32), C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.magi_ode_sensitivities(self._h, drift_id, P, S, _ptr(x0), _ptr(theta), T, _ptr(t_out), int(substeps), Q, i32(cols),
+                                                     int(bool(relative)), n_obs, i32(oj), i32(oc), _ptr(ow), _ptr(sig), i32(link), _ptr(traj),
+                                                     _ptr(sens), _ptr(mean), _ptr(sd), _ptr(fim), _ptr(fim_mean), i32(status), C.byref(nf),
+                                                     C.byref(nex) if fisher else None))
+        out = {"trajectories": traj, "sens": sens, "sens_mean": mean, "sens_sd": sd, "status": status[:S], "n_failed": int(nf.value), "cols": cols}
+        if fisher:
+            out.update(fim=fim, fim_mean=fim_mean, n_fim_excluded=int(nex.value))
+        return out
+
+    def sampler_sensitivities(self, t_out, grid_out=None, start_index=0, chains=None, member=None, thin=1, substeps=4, wrt=None, relative=False,
+                              return_draws=True):
+        """``ode_sensitivities`` of the finished sampler run's draws, computed from the device-resident samples (magi_sampler_sensitivities):
+        no draw is copied to the host first, so it also serves a run whose samples were never downloaded.  Draw s starts at its X at grid
+        row ``start_index`` with its theta on the natural scale and is reported at ``t_out``; every ``thin``-th result of each chain.
+        ``grid_out`` [N]: the index in ``t_out`` of grid point i, or -1 -- the observed entries with grid_out >= 0 are the observations of
+        the Fisher information, under the handle's (a group member's own) links, weights, LB and fixed variances; None: none.
+        ``chains`` / ``member`` as in ``sampler_summary``; ``wrt`` / ``relative`` as in ``ode_sensitivities``.  Returns its dictionary
+        (fim, fim_mean, n_fim_excluded only when an observation is used) plus n_obs_used, obs_index [n_obs_used, 2] = (grid point i,
+        component d) ascending in d N + i, and x0 [S, D], theta [S, P], sigma_sq [S, D]: the draws as the device formed them, chain-major."""
+        chain0, n_sel = self._chain_range(chains, member)
+        R = self._cfg.num_results if self._cfg is not None else 0
+        thin = int(thin)
+        S = n_sel * (-(-R // thin) if thin >= 1 else 0)
+        D, P = self.D, self.P
+        t_out = _f64(np.asarray(t_out, dtype=np.float64).reshape(-1))
+        T = t_out.shape[0]
+        cols = np.ascontiguousarray(np.arange(P + D) if wrt is None else np.asarray(wrt).reshape(-1), dtype=np.int32)
+        Q = cols.shape[0]
+        i32 = lambda a: None if a is None else a.ctypes.data_as(_ip)
+        go = None
+        if grid_out is not None:
+            go = np.ascontiguousarray(np.asarray(grid_out).reshape(-1), dtype=np.int32)
+            if go.shape[0] != self.N:
+                raise ValueError(f"grid_out: expected {self.N} entries, got {go.shape[0]}")
+        idx = np.zeros(max(self.N * D, 1), dtype=np.int32)
+        traj = np.empty((S, T, D)) if return_draws else None
+        sens = np.empty((S, T, D, Q)) if return_draws else None
+        mean, sd = np.empty((T, D, Q)), np.empty((T, D, Q))
+        fim = np.full((S, Q, Q), np.nan) if return_draws else None
+        fim_mean = np.full((Q, Q), np.nan)
+        x0, th, s2 = np.empty((S, D)), np.empty((S, P)), np.empty((S, D))
+        status = np.zeros(max(S, 1), dtype=np.int32)
+        nf, nex, n_obs = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._check(self._lib.magi_sampler_sensitivities(self._h, chain0, n_sel, thin, int(start_index), T, _ptr(t_out), int(substeps), i32(go), Q, i32(cols),
+                                                         int(bool(relative)), _ptr(traj), _ptr(sens), _ptr(mean), _ptr(sd), _ptr(fim), _ptr(fim_mean),
+                                                         i32(status), C.byref(nf), C.byref(nex), C.byref(n_obs), i32(idx), _ptr(x0), _ptr(th), _ptr(s2)))
+        K = int(n_obs.value)
+        e = idx[:K].astype(np.int64)
+        out = {"trajectories": traj, "sens": sens, "sens_mean": mean, "sens_sd": sd, "status": status[:S], "n_failed": int(nf.value), "cols": cols,
+               "n_obs_used": K, "obs_index": np.stack([e % self.N, e // self.N], axis=1), "x0": x0, "theta": th, "sigma_sq": s2}
+        if K:
+            out.update(fim=fim, fim_mean=fim_mean, n_fim_excluded=int(nex.value))
+        return out
 
     @staticmethod
     def _probs(probs):

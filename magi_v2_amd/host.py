@@ -554,6 +554,60 @@ def warn_rank_diagnostics(summary, n_chains: int):
     return flags
 
 
+def fisher_report(fim_mean, names, post_sd=None, collinearity_warn=15.0):
+    """What a Fisher information matrix F [Q, Q] (MagiEngine.ode_sensitivities' ``fim_mean``) says about the parameters ``names``: pure
+    numpy.  Returns dict(
+      names;
+      eigenvalues [Q] ascending and eigenvectors [Q, Q] (column i belongs to eigenvalue i) of the symmetrised F;
+      condition_number  lambda_max / lambda_min, inf when lambda_min <= 0;
+      positive_definite  lambda_min > Q eps lambda_max;
+      crlb_sd [Q]  sqrt(diag(F^-1)), the Cramer-Rao bound on an unbiased estimate's sd; NaN when F is not numerically positive definite;
+      collinearity_index  gamma = 1 / sqrt(lambda_min of F scaled to unit diagonal) (Brun, Reichert & Kuensch 2001, who treat 10-15 as the
+                   critical range): 1 for orthogonal sensitivities, inf when the scaled lambda_min <= 0 or a diagonal entry is not > 0;
+      weakest_direction  [(name, loading), ...] of the eigenvector of lambda_min, largest |loading| first, signed so that the first is > 0:
+                   the combination of parameters the observations determine least;
+      sd_ratio [Q]  post_sd / crlb_sd (None without ``post_sd``): well below 1 where a posterior is narrower than the data alone allow).
+    One warning, naming the weakest direction, when gamma exceeds ``collinearity_warn``.  A non-finite F gives NaN throughout and no
+    warning."""
+    F = np.array(fim_mean, dtype=np.float64)
+    names = [str(n) for n in names]
+    Q = len(names)
+    if F.shape != (Q, Q):
+        raise ValueError(f"expected a [{Q}, {Q}] matrix for {Q} names, got {F.shape}")
+    nan_q = np.full(Q, np.nan)
+    post_sd = None if post_sd is None else np.asarray(post_sd, dtype=np.float64).reshape(-1)
+    if post_sd is not None and post_sd.shape[0] != Q:
+        raise ValueError(f"expected {Q} posterior sds, got {post_sd.shape[0]}")
+    if not np.isfinite(F).all():
+        return {"names": names, "eigenvalues": nan_q, "eigenvectors": np.full((Q, Q), np.nan), "condition_number": np.nan, "positive_definite": False,
+                "crlb_sd": nan_q.copy(), "collinearity_index": np.nan, "weakest_direction": [], "sd_ratio": None if post_sd is None else nan_q.copy()}
+    F = 0.5 * (F + F.T)
+    lam, vec = np.linalg.eigh(F)
+    eps = np.finfo(np.float64).eps
+    pd = bool(lam[0] > Q * eps * lam[-1]) and bool(lam[-1] > 0.0)
+    cond = float(lam[-1] / lam[0]) if lam[0] > 0.0 else np.inf
+    crlb = np.sqrt(np.diag(np.linalg.inv(F))) if pd else nan_q.copy()
+    dg = np.diag(F)
+    if (dg > 0.0).all():
+        sc = 1.0 / np.sqrt(dg)
+        lmin = np.linalg.eigvalsh(F * sc[:, None] * sc[None, :])[0]
+        gamma = float(1.0 / np.sqrt(lmin)) if lmin > 0.0 else np.inf
+    else:
+        gamma = np.inf
+    v = vec[:, 0]
+    order = np.argsort(-np.abs(v), kind="stable")
+    v = v * (1.0 if v[order[0]] >= 0.0 else -1.0)
+    weakest = [(names[i], float(v[i])) for i in order]
+    if gamma > collinearity_warn:
+        shown = ", ".join(f"{l:+.3g} {n}" for n, l in weakest if abs(l) >= 0.05)
+        warnings.warn(f"Fisher information: collinearity index {gamma:.3g} exceeds {collinearity_warn:g}: the observations hardly determine the "
+                      f"direction {shown}")
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = None if post_sd is None else post_sd / crlb
+    return {"names": names, "eigenvalues": lam, "eigenvectors": vec, "condition_number": cond, "positive_definite": pd, "crlb_sd": crlb,
+            "collinearity_index": gamma, "weakest_direction": weakest, "sd_ratio": ratio}
+
+
 # --------------------------------------------------------------------------------------------
 # drifts
 # --------------------------------------------------------------------------------------------
