@@ -819,6 +819,18 @@ int magi_gradient_bytes(magi_handle* h, int n_chains, double* phase_bytes);
  * streaming kernel that serves n_chains reads (the first term of magi_gradient_bytes' [4]).  Any pointer may be null. */
 int magi_tile_formats(magi_handle* h, int n_chains, int64_t* n_blocks, int64_t* n_demoted, double* block_bytes);
 
+/* Carrier workgroups of the VALU streaming kernels (option "stream_carriers"): the packing weighs a block 2 units of
+ * 64 KB when a VALU kernel reads it as fp64 and 1 when it reads the fp32 copy, and fills carriers of up to three blocks to 3 units -- [fp64 +
+ * fp32] or [fp32 x 3], what does not fill one in the last carriers.  Where the launch is in carriers, k_stream<1 | 2> run one 768-thread
+ * workgroup per carrier, at most one per CU, each block on four waves of its own with the arithmetic and the partial slots of the 256-thread
+ * launch: results are bit-identical and no checkpoint depends on it.  on = whether the current pack launches carriers (the option's resolved
+ * value: off by default; -1 = where one workgroup per block needs more than one round on this device and the carriers fit in one); n_carriers and units[0 ..
+ * n_carriers) = the carriers of the current pack and their units, filled whether they are launched or not (cap = the room in units).  Any
+ * pointer may be null.  The group and matrix-core kernels always run a workgroup per block. */
+int magi_stream_carriers(magi_handle* h, int* on, int* n_carriers, int* units, int cap);
+/* The carrier table itself: tasks[3 c + s] = the block (its index among magi_tile_formats' n_blocks) in slot s of carrier c, -1 = empty. */
+int magi_stream_carrier_tasks(magi_handle* h, int* tasks, int cap);
+
 /* Name of the streaming kernel a batch of n_chains runs on with the current matrices, problem and options:
  * "k_stream<1>", "k_stream<2>" (VALU), "k_stream_sep<CW=8|16>" (matrix cores, separable drift), "k_stream_mc". */
 int magi_stream_kernel_name(magi_handle* h, int n_chains, char* buf, int cap);
@@ -848,7 +860,11 @@ int magi_stream_kernel_name(magi_handle* h, int n_chains, char* buf, int cap);
  * at most this many rows of t_new per chunk (no effect on any result); gp_profile, a flag: they time their stages (magi_gp_profile; a
  * synchronisation per stage).  And the storage switch of the packing, tile_demote, 0 or 1 (default 1; the variable MAGI_TILE_DEMOTE = 0 or 1 is
  * read by magi_create): 1: the packing stores the operator blocks it can certify a second time as fp32 for the VALU streaming kernels
- * (magi_tile_formats); 0: every block fp64, as before the format existed; read at the next packing. */
+ * (magi_tile_formats); 0: every block fp64, as before the format existed; read at the next packing.  And the launch shape of the VALU streaming
+ * kernels, stream_carriers, -1, 0 or 1 (default 0; the variable MAGI_STREAM_CARRIERS is read by magi_create): 0: a workgroup per block; -1: carrier
+ * workgroups (magi_stream_carriers) where they turn a launch of several rounds into one (measured SLOWER than the default at N = 1024 on an
+ * MI355X: profiles/r22_carriers_ab.txt); 1: wherever a CU holds exactly one carrier workgroup
+ * (tests at small shapes); read at the next packing; no result depends on it. */
 int magi_set_option(magi_handle* h, const char* name, int64_t value);
 
 /* Diagnostics: per-class device time of the last magi_build_matrices run with option "build_profile" set

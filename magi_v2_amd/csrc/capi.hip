@@ -45,6 +45,7 @@ void free_matrices(magi_handle* h) {
     h->dTiles = nullptr; h->dTasks = nullptr; h->dTiles32 = nullptr;
     h->tiles_cap = h->tasks_cap = h->tiles32_cap = 0;
     h->n_demoted = 0; h->pb.tiles32 = nullptr;
+    h->pb.ctasks = nullptr; h->pb.n_carriers = 0; h->carrier_units.clear(); h->carrier_slots.clear(); h->carrier_table.clear();
     h->have_matrices = h->have_problem = false;
 }
 
@@ -212,6 +213,9 @@ void magi_options_from_env(MagiOptions& o) {
     // the storage switch of csrc/pack.hip (below, magi_set_option: no row of the table): 0 or 1, any other value keeps the default
     if (const char* e = getenv("MAGI_TILE_DEMOTE"))
         if (!strcmp(e, "0") || !strcmp(e, "1")) o.tile_demote = e[0] - '0';
+    // likewise the launch shape of the VALU streaming kernels (csrc/pack.hip: carriers): -1, 0 or 1
+    if (const char* e = getenv("MAGI_STREAM_CARRIERS"))
+        if (!strcmp(e, "-1") || !strcmp(e, "0") || !strcmp(e, "1")) o.stream_carriers = atoi(e);
 }
 
 // What makes which state of a handle stale.  Every level includes the ones before it; the call, the level it raises, and why -- the code's
@@ -368,6 +372,7 @@ magi_handle* magi_create(int device_id) {
     for (int i = 0; i < 4; ++i) (void)hipEventCreateWithFlags(&h->ev[i], hipEventDisableTiming);
     (void)hipEventCreate(&h->ev_t0);
     (void)hipEventCreate(&h->ev_t1);
+    h->carrier_fits = magi_carrier_one_per_cu();          // (an occupancy query of the carrier kernels, asked once: pack.hip's eligibility)
     return h;
 }
 
@@ -1413,6 +1418,13 @@ int magi_set_option(magi_handle* h, const char* name, int64_t value) {
         h->opt.tile_demote = (int)value;
         return MAGI_OK;
     }
+    // the launch shape of the VALU streaming kernels (csrc/pack.hip: carriers): 0 a workgroup per block (the default), -1 carrier workgroups where they
+    // make one launch round of several, 1 wherever a CU holds exactly one; read at the next packing.  No result depends on it, so it is no part of a checkpoint's tag
+    if (std::strcmp(name, "stream_carriers") == 0) {
+        if (value < -1 || value > 1) return magi_fail(h, MAGI_E_BADARG, "stream_carriers in [-1, 1]");
+        h->opt.stream_carriers = (int)value;
+        return MAGI_OK;
+    }
     if (std::strcmp(name, "gp_profile") == 0) {
         h->opt.gp_profile = value != 0;
         return MAGI_OK;
@@ -1476,6 +1488,30 @@ int magi_tile_formats(magi_handle* h, int n_chains, int64_t* n_blocks, int64_t* 
     if (n_blocks) *n_blocks = h->pb.n_tasks;
     if (n_demoted) *n_demoted = h->n_demoted;
     if (bytes) *bytes = block_bytes(h, magi_stream_kernel(h, n_chains));
+    return MAGI_OK;
+}
+
+int magi_stream_carriers(magi_handle* h, int* on, int* n_carriers, int* units, int cap) {
+    if (!h) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_stream_carriers");
+    if (!h->have_matrices) return magi_fail(h, MAGI_E_STATE, "no matrices");
+    const int n = (int)h->carrier_units.size();
+    if (on) *on = h->pb.n_carriers > 0;
+    if (n_carriers) *n_carriers = n;
+    if (units) {
+        if (cap < n) return magi_fail(h, MAGI_E_BADARG, "magi_stream_carriers: room for " + std::to_string(cap) + " carriers, the pack has " + std::to_string(n));
+        std::copy(h->carrier_units.begin(), h->carrier_units.end(), units);
+    }
+    return MAGI_OK;
+}
+
+int magi_stream_carrier_tasks(magi_handle* h, int* tasks, int cap) {
+    if (!h || !tasks) return MAGI_E_BADARG;
+    if (h->group_n) return refuse_group(h, "magi_stream_carrier_tasks");
+    if (!h->have_matrices) return magi_fail(h, MAGI_E_STATE, "no matrices");
+    const int n = MAGI_CARRIER_TASKS * (int)h->carrier_units.size();
+    if (cap < n) return magi_fail(h, MAGI_E_BADARG, "magi_stream_carrier_tasks: room for " + std::to_string(cap) + " slots, the table has " + std::to_string(n));
+    std::copy(h->carrier_slots.begin(), h->carrier_slots.end(), tasks);
     return MAGI_OK;
 }
 

@@ -28,7 +28,17 @@ namespace {
 template <int NC, int DRIFT>
 __global__ __launch_bounds__(64 * ST_WAVES) __attribute__((amdgpu_waves_per_eu(3)))
 void k_stream(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
-    constexpr int KARGS = sizeof(DevProblem) + sizeof(DevChains) + sizeof(SamplerCfgDev) + sizeof(int);
+    constexpr int KARGS = sizeof(DevProblem) + sizeof(DevChains) + sizeof(SamplerCfgDev) + sizeof(int), CARR = 1;
+#include "leap_stream_body.h"
+}
+
+// The same kernel in CARRIER workgroups (pack.hip: carriers; leap_stream_body.h: CARR): grid (n_carriers + 1, .), block 3 x 64 x ST_WAVES.  Twelve
+// waves at three per SIMD are every wave slot a CU has for this kernel, so a CU hosts ONE carrier and streams the bytes the pack put into it --
+// placement by construction, where the 256-thread launch leaves the co-residence of its workgroups to the dispatcher.
+template <int NC, int DRIFT>
+__global__ __launch_bounds__(MAGI_CARRIER_TASKS * 64 * ST_WAVES) __attribute__((amdgpu_waves_per_eu(3)))
+void k_stream_carrier(DevProblem pb, DevChains ch, SamplerCfgDev cfg, int parity) {
+    constexpr int KARGS = sizeof(DevProblem) + sizeof(DevChains) + sizeof(SamplerCfgDev) + sizeof(int), CARR = MAGI_CARRIER_TASKS;
 #include "leap_stream_body.h"
 }
 
@@ -697,6 +707,24 @@ __global__ __launch_bounds__(256) void k_read_tiles(const double2* __restrict__ 
     }
     if (a == 12345.678) out[0] = a;
 }
+// (the twin of the carrier launch: a carrier workgroup reads the blocks of its three slots, as k_stream_carrier does)
+__global__ __launch_bounds__(MAGI_CARRIER_TASKS * 256) void k_read_tiles_carrier(const double2* __restrict__ p, const double2* __restrict__ p32, const int* __restrict__ ctasks, double* out, int rev) {
+    const int* tk = ctasks + 4 * (MAGI_CARRIER_TASKS * blockIdx.x + (threadIdx.x >> 8));
+    const int tix = ctask_tile(tk[0]), s32 = task_slot32(tk[1]), t = threadIdx.x & 255;
+    double a = 0.0;
+    constexpr int R = MAGI_TB * MAGI_TB / 2 / 256;
+    if (tix < 0) {
+    } else if (s32) {
+        const double2* q = p32 + (size_t)(s32 - 1) * (MAGI_TB * MAGI_TB / 4) + t;
+#pragma unroll
+        for (int r = 0; r < R / 2; ++r) { const double2 v = q[r * 256]; a += v.x + v.y; }
+    } else {
+        const double2* q = p + (size_t)tix * (MAGI_TB * MAGI_TB / 2) + t;
+#pragma unroll
+        for (int r = 0; r < R; ++r) { const double2 v = q[(rev ? R - 1 - r : r) * 256]; a += v.x + v.y; }
+    }
+    if (a == 12345.678) out[0] = a;
+}
 
 // validation plan (magi_logpost_grad_fused / timing): slot 0 evaluates buffer 0 as is, no leapfrog
 __global__ void k_plan_eval(DevChains ch, int parity) {
@@ -733,8 +761,20 @@ __global__ __launch_bounds__(MAGI_TAIL_THREADS) void k_leap_finalize(DevProblem 
 
 template <int NC, int DRIFT>
 int launch_stream_valu(magi_handle* h, int n_chains, int parity, bool with_decisions, hipStream_t s) {
+    if (h->pb.n_carriers) {            // (decided by the pack: magi_pack_matrices)
+        const dim3 grid(h->pb.n_carriers + (with_decisions ? NC : 0), (n_chains + NC - 1) / NC);
+        return magi_launch(h, "stream (carrier) launch: ", k_stream_carrier<NC, DRIFT>, grid, dim3(MAGI_CARRIER_TASKS * 64 * ST_WAVES), s, h->pb, h->ch, h->cfg, parity);
+    }
     const dim3 grid(h->pb.n_tasks + (with_decisions ? NC : 0), (n_chains + NC - 1) / NC);      // + one decision workgroup per chain
     return magi_launch(h, "stream launch: ", k_stream<NC, DRIFT>, grid, dim3(64 * ST_WAVES), s, h->pb, h->ch, h->cfg, parity);
+}
+
+// true when a CU holds exactly ONE workgroup of k_stream_carrier<1 | 2, DRIFT> at a time (false also when the query fails)
+template <int DRIFT> bool carrier_one_per_cu() {
+    int n1 = 0, n2 = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, k_stream_carrier<1, DRIFT>, MAGI_CARRIER_TASKS * 64 * ST_WAVES, 0) != hipSuccess ||
+        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n2, k_stream_carrier<2, DRIFT>, MAGI_CARRIER_TASKS * 64 * ST_WAVES, 0) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return n1 == 1 && n2 == 1;
 }
 
 // (k_stream_sep exists for separable drifts only, k_stream_mc for the others: magi_stream_kernel never picks the missing one)
@@ -879,6 +919,15 @@ int magi_launch_stream(magi_handle* h, int n_chains, int parity, bool with_decis
     return MAGI_OK;
 }
 
+// A CU must hold exactly one carrier workgroup, whichever drift of this library runs (asked once per handle, at its creation; pack.hip: eligibility)
+bool magi_carrier_one_per_cu() {
+#ifdef MAGI_USER_DRIFT_HEADER
+    return carrier_one_per_cu<MAGI_DRIFT_USER>();
+#else
+    return carrier_one_per_cu<MAGI_DRIFT_SEIR3>() && carrier_one_per_cu<MAGI_DRIFT_SEIR4>() && carrier_one_per_cu<MAGI_DRIFT_SIRW>();
+#endif
+}
+
 int magi_launch_point(magi_handle* h, int n_chains, int parity, hipStream_t s) {
     if (h->group_n) return magi_launch_point_group(h, n_chains, parity, s);
     const dim3 g(magi_leap_wgs(h->pb), n_chains), b(PT_THREADS);
@@ -890,6 +939,9 @@ int magi_launch_point(magi_handle* h, int n_chains, int parity, hipStream_t s) {
 
 int magi_launch_read_tiles(magi_handle* h, int rev, hipStream_t s) {
     const bool narrow = h->stream_kernel == StreamKernel::Valu1 || h->stream_kernel == StreamKernel::Valu2;      // (of the batch last set up, as magi_launch_stream)
+    if (narrow && h->pb.n_carriers)    // (the launch of the kernel it is the ceiling of)
+        return magi_launch(h, "read_tiles (carrier) launch: ", k_read_tiles_carrier, dim3(h->pb.n_carriers), dim3(MAGI_CARRIER_TASKS * 256), s,
+                           reinterpret_cast<const double2*>(h->pb.tiles), reinterpret_cast<const double2*>(h->pb.tiles32), h->pb.ctasks, h->d_fin, rev);
     return magi_launch(h, "read_tiles launch: ", k_read_tiles, dim3(h->pb.n_tasks), dim3(256), s, reinterpret_cast<const double2*>(h->pb.tiles),
                        reinterpret_cast<const double2*>(narrow ? h->pb.tiles32 : nullptr), h->pb.tasks, h->d_fin, rev);
 }

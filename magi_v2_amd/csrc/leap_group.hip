@@ -19,7 +19,7 @@ namespace {
 template <int NC, int DRIFT>
 __global__ __launch_bounds__(64 * ST_WAVES) __attribute__((amdgpu_waves_per_eu(3)))
 void k_stream_group(const DevProblem* table, DevChains ch, SamplerCfgDev cfg, int parity, int per) {
-    constexpr int KARGS = sizeof(const DevProblem*) + sizeof(DevChains) + sizeof(SamplerCfgDev) + 2 * sizeof(int);
+    constexpr int KARGS = sizeof(const DevProblem*) + sizeof(DevChains) + sizeof(SamplerCfgDev) + 2 * sizeof(int), CARR = 1;      // (a group keeps single tasks)
     const DevProblem& pb = group_member(table, (int)(blockIdx.y * NC) / per);
 #include "leap_stream_body.h"
 }

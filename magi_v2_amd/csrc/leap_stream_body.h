@@ -1,5 +1,10 @@
 // Body of the streaming kernel k_stream<NC, DRIFT> (leap.hip), included INSIDE the kernel and inside its problem-group twin k_stream_group.
-// The including kernel provides `pb` (const DevProblem&), `ch`, `cfg`, `parity` and the constant KARGS (its kernel-argument bytes).
+// The including kernel provides `pb` (const DevProblem&), `ch`, `cfg`, `parity` and the constants KARGS (its kernel-argument bytes) and CARR: the
+// block tasks a workgroup runs side by side -- 1, or 3 in a CARRIER workgroup (k_stream_carrier: 3 x ST_WAVES waves, one workgroup per CU; pack.hip
+// fills the carriers by bytes).  Sub-group `sub` = threadIdx.x / 256 of a carrier runs its task on its own four waves with the code, the LDS
+// layout (a leading [CARR]) and the partial slots a 256-thread workgroup has for that task; what the sub-groups share is theta' (derived once,
+// by the first NC waves of the carrier) and the barriers, which stay workgroup-wide: an empty slot of the table (tix < 0) loads and stores
+// nothing but reaches every barrier.  With CARR == 1 every carrier term below is a compile-time constant.
 // A textual body and not a force-inlined function: the function form changed the register allocation and wait counts of every existing
 // instantiation (a different order of the optimisations around the inlined call); included, k_stream compiles to the instructions it had.
 // (no include guard: included once per kernel)
@@ -11,10 +16,11 @@
     const int all_done = ch.gctl->all_done;
     kernarg_prefetch<KARGS>();
     const int c0 = blockIdx.y * NC;
-    __shared__ double vcol[NC][TB], vrow[NC][TB], rowout[NC][TB], colacc[ST_WAVES][NC][TB];
+    __shared__ double vcol_s[CARR][NC][TB], vrow_s[CARR][NC][TB], rowout_s[CARR][NC][TB], colacc_s[CARR][ST_WAVES][NC][TB];
     __shared__ double th_s[NC][MAGI_MAX_P];
-    const int n_dec = (int)gridDim.x - pb.n_tasks;        // decision workgroups come FIRST in dispatch order: their one round of
+    const int n_dec = (int)gridDim.x - (CARR == 1 ? pb.n_tasks : pb.n_carriers);        // decision workgroups come FIRST in dispatch order: their one round of
     if ((int)blockIdx.x < n_dec) {                         // loads is then on the wire before the stream saturates the memory system
+        if (CARR > 1 && threadIdx.x >= 64 * ST_WAVES) return;      // (the decisions are written for, and sum in the order of, MAGI_TAIL_THREADS threads)
         // ---- the decisions of the previous slot, one workgroup per chain, next to this slot's stream (decide.h) ----
         __shared__ double dsh[25 * 16], dshs[24];
         __shared__ ChainCtl s_ctl;
@@ -26,16 +32,22 @@
         if (chain < ch.n_chains) decide_block<DRIFT>(pb, ch, cfg, chain, parity, all_done, dsh, dshs, &s_ctl, s_g, s_par, s_ops, s_cst);
         return;
     }
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int tix = (int)blockIdx.x - n_dec;
+    const int sub = CARR == 1 ? 0 : __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 8);      // (wave-uniform: the descriptor stays a scalar load)
+    const int t = CARR == 1 ? (int)threadIdx.x : ((int)threadIdx.x & (64 * ST_WAVES - 1)), lane = t & 63, wave = t >> 6;
+    double (&vcol)[NC][TB] = vcol_s[sub], (&vrow)[NC][TB] = vrow_s[sub], (&rowout)[NC][TB] = rowout_s[sub];
+    double (&colacc)[ST_WAVES][NC][TB] = colacc_s[sub];
     MAGI_STAMPS_DECL(stream, 8);
     MAGI_STAMP(stream, 0);
     // (the descriptor table is read-only for the lifetime of the matrices: fetched through the constant address space it is a
     //  scalar load on its own counter, so waiting for it does not wait for the tile loads issued below and vice versa)
     typedef const int __attribute__((address_space(4))) * const_int_ptr;
-    const_int_ptr tk = (const_int_ptr)(unsigned long long)(pb.tasks + 4 * (size_t)tix);
+    const_int_ptr tk = (const_int_ptr)(unsigned long long)(CARR == 1 ? pb.tasks + 4 * (size_t)((int)blockIdx.x - n_dec)
+                                                                     : pb.ctasks + 4 * (size_t)(CARR * ((int)blockIdx.x - n_dec) + sub));
     int4 task;
     task.x = tk[0]; task.y = tk[1]; task.z = tk[2]; task.w = tk[3];
+    // a carrier's slot: {ctask_word(block index or -1, "a task of this carrier needs theta'", d), kind word, bi, bj} (magi_internal.h)
+    const int tix = CARR == 1 ? (int)blockIdx.x - n_dec : ctask_tile(task.x);
+    const bool live = CARR == 1 || tix >= 0;
     // the wave's rows in chunks of 8, two chunks in flight (a0 / a1): 16 KB per wave on the wire while one chunk is in the ALUs.
     // tile loads need nothing but the block index: on the wire before the plan-dependent loads (except in the waves that derive theta')
     // A DEMOTED block (pack.hip: the criterion; workgroup-uniform, known from the descriptor alone) is read from its fp32 copy instead: the wave's
@@ -44,8 +56,8 @@
     // direction.  Only the addresses differ up to the loop; the loop converts to fp64 on use and runs the same butterflies and accumulators.
     const int s32 = task_slot32(task.y);
     static_assert(ST_RW == 32, "tile32_index lays a block out for 32-row wave strips");
-    const double2* A = (s32 ? reinterpret_cast<const double2*>(pb.tiles32 + (size_t)(s32 - 1) * TB * TB + (size_t)((threadIdx.x >> 6) * ST_RW) * TB)
-                            : reinterpret_cast<const double2*>(pb.tiles + (size_t)tix * TB * TB + (size_t)((threadIdx.x >> 6) * ST_RW) * TB)) + (threadIdx.x & 63);
+    const double2* A = (s32 ? reinterpret_cast<const double2*>(pb.tiles32 + (size_t)(s32 - 1) * TB * TB + (size_t)(wave * ST_RW) * TB)
+                            : reinterpret_cast<const double2*>(pb.tiles + (size_t)(CARR == 1 ? tix : max(tix, 0)) * TB * TB + (size_t)(wave * ST_RW) * TB)) + lane;
     constexpr int NCK = ST_RW / 8;
     // Odd slots walk the wave's row chunks backwards: what a slot read LAST is what the next one reads FIRST, so the tail of the
     // block stream is still in the XCD's L2 (4 MB against 9 MB of blocks per XCD; tools/micro/readshape.hip: 5-15 % on the
@@ -56,14 +68,15 @@
     const int pc0 = (ALT && (parity & 1)) ? NCK - 1 : 0, pcs = (ALT && (parity & 1)) ? -1 : 1;
     const int ld0 = s32 ? 0 : pc0 * 8, ld1 = s32 ? 8 : (pc0 + pcs) * 8;      // first 1-KB line of the two chunks in flight (fp32: the whole strip)
     double2 a0[8], a1[8];
-    if ((threadIdx.x >> 6) >= NC) {
+    if ((threadIdx.x >> 6) >= NC && live) {
 #pragma unroll
         for (int r = 0; r < 8; ++r) a0[r] = A[(size_t)(ld0 + r) * (TB / 2)];
 #pragma unroll
         for (int r = 0; r < 8; ++r) a1[r] = A[(size_t)(ld1 + r) * (TB / 2)];
     }
     __builtin_amdgcn_sched_barrier(0);
-    const int d = task.x, kind = task_kind(task.y), bi = task.z, bj = task.w;
+    const int d = CARR == 1 ? task.x : ctask_d(task.x), kind = task_kind(task.y), bi = task.z, bj = task.w;
+    const bool needth = CARR == 1 ? kind != TK_FH : ctask_theta(task.x);       // workgroup-uniform: some task of the workgroup multiplies f
     const int N = pb.N;
 
     // What to evaluate for each chain, from the plan the point phase executed LAST (the decisions that complete it run
@@ -80,7 +93,7 @@
     // (small loads first, the tile stream behind them: their wait then does not cover the row loads)
     // (blocks of FH multiply xc on both sides: they need no theta and do not wait for it -- their traffic fills the window
     //  in which the other workgroups derive theta')
-    if (wave < NC && kind != TK_FH) {
+    if ((int)(threadIdx.x >> 6) < NC && needth) {
         const int c = wave, cc = min(c0 + c, ch.n_chains - 1);
         const LeafPlan* lp = ch.plan + (size_t)(parity ^ 1) * ch.n_chains + cc;
         const bool derive = lp->active && !lp->skip && lp->leaf;
@@ -125,12 +138,12 @@
     }
 
     if (all_done) return;
-    MAGI_STAMPS_ON(decide, if (tix == 0 && threadIdx.x == 0) {
+    MAGI_STAMPS_ON(decide, if (tix == 0 && t == 0) {
         unsigned long long* st = reinterpret_cast<unsigned long long*>(ch.par + (size_t)c0 * PAR_COUNT + 40 + 11);
         st[1] = __builtin_amdgcn_s_memrealtime();      // [12] first stream workgroup's start
         st[0] = 0ull;                                    // [11] latest stream workgroup end (atomicMax below)
     })
-    if (wave < NC) {                 // (the waves that derived theta' issue their first chunks now)
+    if ((int)(threadIdx.x >> 6) < NC && live) {                 // (the waves that derived theta' issue their first chunks now)
 #pragma unroll
         for (int r = 0; r < 8; ++r) a0[r] = A[(size_t)(ld0 + r) * (TB / 2)];
 #pragma unroll
@@ -139,7 +152,7 @@
     __builtin_amdgcn_sched_barrier(0);
     double thv[NC][P];
     MAGI_STAMP(stream, 2);
-    if (kind != TK_FH) {
+    if (needth) {
         __syncthreads();             // th_s
         MAGI_STAMP(stream, 3);
 #pragma unroll
@@ -173,7 +186,9 @@
 #pragma unroll
         for (int k = 0; k < NACC; ++k) { cacc[c][k].x = 0.0; cacc[c][k].y = 0.0; }
     }
-    if (s32) {
+    if (!live) {
+        // (an empty slot of a carrier: nothing was loaded and nothing is stored; on to the barrier)
+    } else if (s32) {
         // the fp32 copy: physical chunk pk = row pairs 4 pk .. 4 pk + 3 of the strip, already in a0 (pk < 2) / a1; each register pair holds
         // (row 2 k: columns 2 l, 2 l + 1 | row 2 k + 1: the same columns) as four floats.  Converted on use; the products, the butterfly and
         // the per-physical-chunk column sums are the fp64 path's, so the result has no slot parity in it at all.
@@ -266,7 +281,7 @@
     const size_t cstride = (size_t)4 * D * pb.nb * pb.Np;
 #pragma unroll
     for (int c = 0; c < NC; ++c) {
-        if (!act[c] || t >= 2 * TB) continue;
+        if (!act[c] || t >= 2 * TB || !live) continue;
         double* tp = ch.tpart + (size_t)(c0 + c) * cstride;
         if (!isrow) {
             tp[((size_t)(rvec * D + d) * pb.nb + bj) * pb.Np + bi * TB + loc] = rowout[c][loc];
@@ -278,6 +293,6 @@
         }
     }
     MAGI_STAMP(stream, 7);
-    MAGI_STAMPS_FLUSH(stream, tix == MAGI_STAMP_WG && blockIdx.y == 0 && threadIdx.x == 64 * MAGI_STAMP_WAVE, ch.par, 8);
-    MAGI_STAMPS_ON(decide, __syncthreads(); if (threadIdx.x == 0)
+    MAGI_STAMPS_FLUSH(stream, tix == MAGI_STAMP_WG && blockIdx.y == 0 && t == 64 * MAGI_STAMP_WAVE, ch.par, 8);
+    MAGI_STAMPS_ON(decide, __syncthreads(); if (t == 0)
         atomicMax(reinterpret_cast<unsigned long long*>(ch.par + (size_t)c0 * PAR_COUNT + 40 + 11), (unsigned long long)__builtin_amdgcn_s_memrealtime());)

@@ -88,7 +88,19 @@ struct DevProblem {
     const float* tiles32;  // [demoted blocks][TB][TB] fp32 copies of the blocks the pack certified (pack.hip: the criterion), in the in-block order
                            // of tile32_index; a task names its copy in the upper bits of `kind` (task_slot32).  The same blocks in `tiles` hold the
                            // same rounded values as doubles.  Read by the VALU streaming kernels and their load-only twin only; nullptr: none demoted
+    const int* ctasks;     // [n_carriers][3][4]: the carrier table of the VALU streaming kernels (pack.hip: carriers; option stream_carriers) -- a
+                           // carrier workgroup runs the three tasks of its row side by side; a slot is a task's descriptor with ctask_word in
+                           // place of d.  Read by the carrier launch and its load-only twin only
+    int n_carriers;        // 0: the VALU kernels launch a 256-thread workgroup per task (as the group and matrix-core kernels always do)
 };
+
+// First word of a carrier slot: the task's index in `tasks` / `tiles` (-1: the slot is empty), whether ANY task of the carrier needs theta'
+// (its workgroup then derives it and meets at the barrier behind it), and the task's component d.
+__host__ __device__ inline int ctask_word(int tile, bool theta, int d) { return tile * 32 + (theta ? 16 : 0) + d; }
+__host__ __device__ inline int ctask_tile(int word) { return word >> 5; }
+__host__ __device__ inline bool ctask_theta(int word) { return (word & 16) != 0; }
+__host__ __device__ inline int ctask_d(int word) { return word & 15; }
+constexpr int MAGI_CARRIER_TASKS = 3;      // block tasks of a carrier workgroup = its units of 64 KB (an fp64 block weighs 2, a demoted one 1)
 
 // A task's `kind` word: TileKind in the low byte; above it 1 + the block's index in tiles32 when the block is demoted, 0 = fp64 only.
 constexpr int TK_SLOT_SHIFT = 8;
@@ -913,8 +925,8 @@ __device__ __forceinline__ double wave_sum(double v) {
 // Stage 1: per-wave butterflies, one partial per wave.  Stage 2: wave 0 adds the <= 16 partials of
 // each value with a row butterfly and publishes K totals (fixed order -> deterministic).
 template <int K>
-__device__ inline void block_sum(double (&v)[K], double* sh) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+__device__ inline void block_sum(double (&v)[K], double* sh, int nw) {      // nw: the waves that call it (the others of the workgroup have ended)
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int k = 0; k < K; ++k) {
         const double s = wave_sum(v[k]);
@@ -935,6 +947,9 @@ __device__ inline void block_sum(double (&v)[K], double* sh) {
     for (int k = 0; k < K; ++k) v[k] = sh[K * 16 + k];
     __syncthreads();
 }
+
+template <int K>
+__device__ inline void block_sum(double (&v)[K], double* sh) { block_sum<K>(v, sh, (int)(blockDim.x >> 6)); }
 
 // ------------------------------------------------------------------------------------------
 // Reduce step of one gradient evaluation (all threads of the block must call it).
@@ -1058,6 +1073,9 @@ struct MagiOptions {
                                         // every rank then runs the same kernel family, whatever its own share -- shard.family_chains_for)
     int sep_pair_min = 256;             // pack.hip: pair the diagonal blocks FH_bb + FK_bb when there are more tasks than this
     int fused_parity = 0;               // magi_logpost_grad_fused evaluates as an even (0) / odd (1) leapfrog slot
+    int stream_carriers = 0;            // pack.hip: launch the VALU streaming kernels in carrier workgroups, three block tasks on one CU filled by bytes: 0 never
+                                        // (the default: measured slower, profiles/r22_carriers_ab.txt), -1 where that turns a launch of several rounds into
+                                        // one round, 1 wherever a CU holds exactly one carrier
     int tile_demote = 1;                // pack.hip: store the operator blocks the criterion certifies as fp32 for the VALU streaming kernels (0: none)
     int gemm_remap_min = MAGI_GEMM_REMAP_MIN_DEFAULT;      // build.hip: super-block tile order from this many super-blocks per launch (24 until round 4;
                                         // while it is at its default, potrf's thin launches keep 24: GemmArgs::remap_min)
@@ -1157,6 +1175,10 @@ struct magi_handle {
     size_t tiles_cap = 0, tasks_cap = 0;
     float* dTiles32 = nullptr;       // pb.tiles32: fp32 copies of the demoted blocks (grown like dTiles, stale with it)
     size_t tiles32_cap = 0;
+    // carriers of the current pack (pack.hip), decided or not: units of 64 KB per carrier; the block index of every slot (-1: empty); pb.n_carriers says
+    // whether the VALU kernels launch them.  carrier_fits: a CU holds exactly one carrier workgroup (magi_carrier_one_per_cu, asked by magi_create)
+    std::vector<int> carrier_units, carrier_slots, carrier_table;      // (carrier_table: the host copy of pb.ctasks, the source of its upload)
+    bool carrier_fits = false;
     int n_demoted = 0;               // blocks of the current pack that have one (0 under the option tile_demote = 0, banded fused storage, N <= 256)
     // work space of the matrix build and the packing, kept between calls (grow-only): a repeated build at N = 8192 otherwise spends
     // more host time in hipMalloc / hipFree of ~35 GB than the GPU spends on the build
@@ -1292,6 +1314,7 @@ int magi_build_profile_get(const magi_handle* h, double* flops, double* ms, long
 int magi_fit_hparams_device(magi_handle* h, const double* I, int N, int D, const double* X, const double* mu, const double* mu_phi2,
                             const double* sd_phi2, const double* sig_loc, double nu, int iters, double lr, double jitter,
                             double* phi1, double* phi2, double* sig2, double* loss_trace);
+bool magi_carrier_one_per_cu();                                                          // leap.hip: the occupancy query behind magi_handle::carrier_fits
 int magi_launch_read_tiles(magi_handle* h, int rev, hipStream_t s);                     // load-only pass over the packed operator blocks
 int magi_launch_plan_eval(magi_handle* h, int n_chains, hipStream_t s, int parity = 0);        // plan: evaluate buffer 0, no leapfrog                                       // workgroups along the grid axis
 // build.hip: E = Ks M, H = Cs + M^T E for D dense [N][N] components (H overwrites Cs)

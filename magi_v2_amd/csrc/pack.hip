@@ -192,6 +192,7 @@ int magi_pack_matrices(magi_handle* h, int N, int D, int bandsize, const double*
     pb.Csym = pb.M = pb.Mt = pb.Ksym = nullptr;
     pb.tiles = nullptr; pb.tasks = pb.stasks = nullptr;
     pb.tiles32 = nullptr; h->n_demoted = 0;
+    pb.ctasks = nullptr; pb.n_carriers = 0; h->carrier_units.clear(); h->carrier_slots.clear(); h->carrier_table.clear();
     if (!had || elems != h->mat_elems) {     // (sized exactly, the four together: all null and mat_elems 0 before the first allocation)
         double** const stacks[4] = {&h->dCsym, &h->dM, &h->dMt, &h->dKsym};
         for (double** s : stacks) { if (*s) (void)hipFree(*s); *s = nullptr; }
@@ -243,6 +244,9 @@ int magi_pack_matrices(magi_handle* h, int N, int D, int bandsize, const double*
         // (the exact variants of the pattern agree within the noise; this one measured best).  The order has no bearing on the arithmetic: a block's
         // partial sums are addressed by its indices.  Only launches of exactly three rounds are re-ordered: fewer have no third workgroups, more are
         // placed dynamically.
+        // (Measured when every block was 128 KB.  Since the demoted blocks are 64 KB the rule balances kinds, not bytes: CUs stream 128 .. 384 KB and the
+        // launch ends with the heaviest, profiles/r22_wg_trace_1chain_fp32.txt.  Where the carriers below are launched this order decides nothing -- a CU's
+        // bytes are fixed by its carrier --; it still holds for the 256-thread launch: option stream_carriers = 0, the group and matrix-core kernels.)
         {
             int ncu = 0;
             (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device);
@@ -291,7 +295,7 @@ int magi_pack_matrices(magi_handle* h, int N, int D, int bandsize, const double*
         tasks.insert(tasks.end(), stasks.begin(), stasks.end());
         const size_t telems = (size_t)n_tasks * MAGI_TB * MAGI_TB;
         int rc;
-        if ((rc = magi_grow(h, h->dTiles, h->tiles_cap, telems, "operator blocks")) || (rc = magi_grow(h, h->dTasks, h->tasks_cap, tasks.size(), "task table"))) return rc;
+        if ((rc = magi_grow(h, h->dTiles, h->tiles_cap, telems, "operator blocks")) || (rc = magi_grow(h, h->dTasks, h->tasks_cap, tasks.size() + (size_t)4 * MAGI_CARRIER_TASKS * n_tasks, "task table"))) return rc;      // (+ the carrier table: at most a carrier per task)
         MAGI_HIP_CHECK(h, hipMemcpyAsync(h->dTasks, tasks.data(), tasks.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
         const size_t nn = (size_t)D * N * N;
         double *tCs = magi_workspace(h, magi_handle::WS_TCS, nn), *tM = magi_workspace(h, magi_handle::WS_TM, nn),
@@ -338,6 +342,48 @@ int magi_pack_matrices(magi_handle* h, int N, int D, int bandsize, const double*
             if ((rc = magi_grow(h, h->dTiles32, h->tiles32_cap, (size_t)n_dem * MAGI_TB * MAGI_TB, "fp32 operator blocks"))) return rc;
             for (int t = 0; t < n_tasks; ++t) tasks[4 * t + 1] |= slot32[t] << TK_SLOT_SHIFT;
             MAGI_HIP_CHECK(h, hipMemcpyAsync(h->dTasks, tasks.data(), n_task_ints * sizeof(int), hipMemcpyHostToDevice, h->stream));
+        }
+        // ---- carrier workgroups of the VALU streaming kernels (option stream_carriers) ----
+        // A CU ends a launch when it has streamed its bytes (profiles/r22_wg_trace_1chain_fp32.txt), and with a workgroup per block the bytes a CU gets
+        // are whatever blocks the dispatcher puts together: 128 .. 384 KB around a mean of 192 at N = 1024 since the demoted blocks are 64 KB.  A
+        // CARRIER is one workgroup of three block tasks side by side (k_stream_carrier: 12 waves, every wave slot a CU has for the kernel, so one per CU)
+        // and the pack fills it by bytes: a block weighs 2 units of 64 KB as fp64 and 1 demoted; [fp64 + fp32] or [fp32 x 3] make 3 units, blocks of
+        // FH first on both sides so that they meet (a carrier without FK / FE blocks needs no theta' and skips its barrier), and what finds no partner
+        // -- fp64 blocks alone, the last one or two fp32 blocks -- goes into the last carriers.  N = 1024: 208 + 42 carriers of 3 units and one of 2.
+        // Launched (pb.n_carriers > 0) only on request: stream_carriers = -1 where a CU holds exactly one carrier workgroup and the carriers turn a launch of
+        // several rounds into one, 1 + carriers <= CUs < 1 + blocks; 1 wherever a CU holds exactly one.  The default is 0, the 256-thread launch as it always
+        // ran: the same-box A/B of profiles/r22_carriers_ab.txt reads the carrier launch 2 % SLOWER at N = 1024 on an MI355X.  The table is
+        // there to be read either way.
+        if (rc == MAGI_OK) {
+            std::vector<int> w64, w32;
+            std::vector<int>& ctab = h->carrier_table;      // (a member: the copy below is asynchronous and completes at the pack's own synchronisation point)
+            for (int fh = 1; fh >= 0; --fh)
+                for (int t = 0; t < n_tasks; ++t)
+                    if ((task_kind(tasks[4 * t + 1]) == TK_FH) == (fh == 1)) (slot32[t] ? w32 : w64).push_back(t);
+            auto emit = [&](int a, int b, int c) {
+                const int slots[MAGI_CARRIER_TASKS] = {a, b, c};
+                bool theta = false;
+                int units = 0;
+                for (int t : slots)
+                    if (t >= 0) { theta = theta || task_kind(tasks[4 * t + 1]) != TK_FH; units += slot32[t] ? 1 : 2; }
+                for (int t : slots) {
+                    const int e[4] = {ctask_word(t, theta, t >= 0 ? tasks[4 * t] : 0), t >= 0 ? tasks[4 * t + 1] : (int)TK_FH, t >= 0 ? tasks[4 * t + 2] : 0, t >= 0 ? tasks[4 * t + 3] : 0};
+                    ctab.insert(ctab.end(), e, e + 4);
+                    h->carrier_slots.push_back(t);
+                }
+                h->carrier_units.push_back(units);
+            };
+            const size_t np = std::min(w64.size(), w32.size());
+            for (size_t i = 0; i < np; ++i) emit(w64[i], w32[i], -1);
+            for (size_t i = np; i < w64.size(); ++i) emit(w64[i], -1, -1);
+            for (size_t i = np; i < w32.size(); i += 3) emit(w32[i], i + 1 < w32.size() ? w32[i + 1] : -1, i + 2 < w32.size() ? w32[i + 2] : -1);
+            int ncu = 0;
+            (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, h->device);
+            const int nc = (int)h->carrier_units.size();
+            const bool one_round = ncu > 0 && 1 + nc <= ncu && ncu < 1 + n_tasks;
+            MAGI_HIP_CHECK(h, hipMemcpyAsync(h->dTasks + tasks.size(), ctab.data(), ctab.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
+            pb.ctasks = h->dTasks + tasks.size();
+            pb.n_carriers = h->carrier_fits && (h->opt.stream_carriers == 1 || (h->opt.stream_carriers < 0 && one_round)) ? nc : 0;
         }
         if (rc == MAGI_OK) {
             hipLaunchKernelGGL(k_pack_tiles, dim3(n_tasks), dim3(256), 0, h->stream, tCs, tKs, tE, h->dTasks, h->dTiles, h->dTiles32, N, fb);

@@ -86,6 +86,8 @@ _SYMBOLS = {
     "magi_time_gradient": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp]),
     "magi_gradient_bytes": (C.c_int, [C.c_void_p, C.c_int, _dp]),
     "magi_tile_formats": (C.c_int, [C.c_void_p, C.c_int, _lp, _lp, _dp]),
+    "magi_stream_carriers": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.c_int]),
+    "magi_stream_carrier_tasks": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.c_int]),
     "magi_stream_kernel_name": (C.c_int, [C.c_void_p, C.c_int, C.c_char_p, C.c_int]),
     "magi_set_option": (C.c_int, [C.c_void_p, C.c_char_p, C.c_int64]),
     "magi_debug_par": (C.c_int, [C.c_void_p, C.c_int, _dp]),
@@ -1107,6 +1109,19 @@ class MagiEngine:
         nb, nd, by = C.c_int64(0), C.c_int64(0), C.c_double(0.0)
         self._check(self._lib.magi_tile_formats(self._h, int(n_chains), C.byref(nb), C.byref(nd), C.byref(by)))
         return int(nb.value), int(nd.value), float(by.value)
+
+    def stream_carriers(self):
+        """The carrier workgroups of the current pack -- option ``stream_carriers`` (include/magi_hip.h: magi_stream_carriers): a dict of
+        ``on`` (whether the VALU streaming kernels launch them), ``units`` (64-KB units of every carrier) and ``tasks`` ([carriers, 3] block
+        indices, -1 = an empty slot)."""
+        on, n = C.c_int(0), C.c_int(0)
+        self._check(self._lib.magi_stream_carriers(self._h, C.byref(on), C.byref(n), None, 0))
+        units = np.zeros(max(n.value, 1), dtype=np.intc)
+        tasks = np.full(3 * max(n.value, 1), -1, dtype=np.intc)
+        ip = C.POINTER(C.c_int)
+        self._check(self._lib.magi_stream_carriers(self._h, None, None, units.ctypes.data_as(ip), n.value))
+        self._check(self._lib.magi_stream_carrier_tasks(self._h, tasks.ctypes.data_as(ip), 3 * n.value))
+        return {"on": bool(on.value), "units": units[:n.value].copy(), "tasks": tasks[:3 * n.value].reshape(-1, 3).copy()}
 
     @staticmethod
     def group(engines):
